@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: ray casts per second of the path tracer's hot path on BASELINE.json's configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cornell|door_room_sarsa|
-                    archway_dqn|complex_light] [--width .. --height .. --spp .. --spp-split ..]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                    [--workload cornell|door_room_sarsa|archway_dqn|complex_light]
+                    [--width .. --height .. --spp .. --spp-split ..]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, renders W untimed frames, times K frames and prints the result line
+(metric, value, ms_per_step, the configuration).  --full adds, after the timed steps, what the
+headline does not need: the roofline, the parity check against the CPU restatement and the
+CPU baseline (below).  --dump-outputs DIR writes what the last timed step computed (below).
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts the N ranks itself
 under torch.distributed.run, one per GPU of the node, and relays rank 0's line; under a
@@ -22,11 +28,19 @@ buffers, so frame i+1 renders while frame i is exchanged.  The frame is fixed as
 strong scaling.
 
 value = total ray casts (all ranks) / max-over-ranks wall time of the K timed steps, in
-Mrays/s.  rank 0 prints one JSON line with the roofline of the render kernels (HIP events on
-the launch stream; instruction and HBM counts from the committed rocprofv3 profile of the
-same build, profiles/*_bench_pmc.json), the bit-exactness of 8 full 32x32 tiles (image and
-ray casts) vs the CPU restatement, and the CPU baseline (oracle/, this host's cores, bounded
-sample, best of 3).
+Mrays/s.  rank 0 prints one JSON line; with --full it also holds the roofline of the render
+kernels (HIP events on the launch stream; instruction and HBM counts from the committed
+rocprofv3 profile of the same build, profiles/*_bench_pmc.json), the bit-exactness of 8 full
+32x32 tiles (image and ray casts) vs the CPU restatement, and the CPU baseline (oracle/, this
+host's cores, bounded sample, best of 3).  The timed loop is the same with and without --full.
+
+--dump-outputs DIR (rank 0, after the timed steps): DIR/image.npy, the frame of the last timed
+step as a caller receives it (height x width x 3, float32); DIR/ray_casts.npy, the ray-cast
+counter the K timed steps accumulated (float64, one element); Expected SARSA also
+DIR/q_table.npy, the Q-table after the last step (volumes x 144, float32).  An array over its
+share of the 64 MB budget is written as a fixed sample (numpy PCG64, seed 1984, sorted flat
+indices).  Scene, camera, RNG seed and network weights are fixed, so the same arguments give
+the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -153,9 +167,14 @@ def parse():
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--spp-split", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the roofline, the parity check against the CPU restatement "
+                         "and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0,
-                    help="target duration of one CPU-baseline run (best of 3; 0 disables)")
-    ap.add_argument("--no-parity", action="store_true")
+                    help="--full: target duration of one CPU-baseline run (best of 3; 0 disables)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: leave the parity check out")
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="P > 1: on one GPU, run each of the P ranks' tile sets through the timed loop in turn "
                          "(host work included; a device copy stands in for the gather) and predict the P-GPU step")
@@ -164,6 +183,8 @@ def parse():
         args.steps = 20 if args.workload == "cornell" else 10
     if args.warmup is None:
         args.warmup = 10 if args.workload == "cornell" else 1
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     return args
 
 
@@ -553,6 +574,35 @@ def parity_tiles(ctx, scene, geom, params, cam, cam_pos, image):
             "pixels": px, "frac_of_frame": round(px / (W * H), 4)}
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes, all of a run's dumped arrays together
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """--dump-outputs: each array as path/<name>.npy, float32 (float64 kept).  The smallest
+    arrays take their bytes from the budget first; one over an even share of what is left is
+    cut to a fixed sample of its flattened elements (sorted indices from numpy's PCG64 seeded
+    1984: the same elements in every run and build).  Returns what was written, per name."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {n: np.asarray(a) for n, a in arrays.items()}
+    arrays = {n: np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+              for n, a in arrays.items()}
+    left, written = DUMP_BUDGET, {}
+    order = sorted(arrays, key=lambda n: arrays[n].nbytes)
+    for i, name in enumerate(order):
+        a = arrays[name]
+        share = left // (len(order) - i)
+        info = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(1984).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+            info["sampled"] = int(keep)
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = info
+    return written
+
+
 def make_workload(args, ctx):
     scene_kind, preset, sampler, W, H, spp, split, cfg = WORKLOADS[args.workload]
     W = args.width or W
@@ -777,7 +827,7 @@ def main():
         pipe.gather_frame(pipe.render_frame(i))
     pipe.drain()
     q_state = None
-    if sampler == "sarsa" and rank == 0 and args.cpu_seconds > 0 and world == 1:
+    if sampler == "sarsa" and rank == 0 and args.full and args.cpu_seconds > 0 and world == 1:
         q_state = rmap.read()[0]  # (before the timed region) the CPU baseline's starting Q-table
     if rank == 0:
         progress(f"{args.workload}: {args.warmup} warmup frame(s) done, timing {args.steps}")
@@ -818,7 +868,9 @@ def main():
     frame = pipe.frame(args.steps - 1)
     if rank == 0:
         progress(f"timed: {elapsed / args.steps * 1e3:.3f} ms per step")
-        image = rtmi.tiles.assemble(frame.cpu().numpy(), params.width, params.height, TILE, world)
+        image = None
+        if args.full or args.dump_outputs:  # the last timed frame, as rtmi.render returns one
+            image = rtmi.tiles.assemble(frame.cpu().numpy(), params.width, params.height, TILE, world)
         line = {
             "metric": f"Mrays/sec ({WORKLOADS[args.workload][0]} {params.width}^2 {params.spp}spp ray casts)"
             if params.width == params.height else f"Mrays/sec ({args.workload} ray casts)",
@@ -847,8 +899,9 @@ def main():
             },
             "ray_casts_per_step": total_casts // args.steps,
             "frame_ms": round(frame_ms, 4),
-            "roofline": roofline(args, geom, params, rank_casts / args.steps, kt),
         }
+        if args.full:
+            line["roofline"] = roofline(args, geom, params, rank_casts / args.steps, kt)
         # preprocessing outside the timed region, measured in this run: the scene's bounce-ray
         # candidate table (host build + upload on the first render that takes it, like a BVH
         # build; device bytes per rank).  The camera rays' cull runs inside every timed frame.
@@ -861,9 +914,15 @@ def main():
         if sampler == "sarsa":  # a learning run: which of its frames the line times
             line["config"]["frames_warmup"] = [0, args.warmup - 1] if args.warmup else []
             line["config"]["frames_timed"] = [args.warmup, args.warmup + args.steps - 1]
-        if sampler == "uniform" and not args.no_parity and params.width % TILE == 0 and params.height % TILE == 0:
+        if args.dump_outputs:
+            outs = {"image": image, "ray_casts": np.array([total_casts], np.float64)}
+            if sampler == "sarsa":
+                outs["q_table"] = rmap.read()[0]
+            line["outputs"] = dump_outputs(args.dump_outputs, outs)
+        if (args.full and sampler == "uniform" and not args.no_parity and params.width % TILE == 0
+                and params.height % TILE == 0):
             line["parity"] = parity_tiles(ctx, scene, geom, params, cam, cam_pos, image)
-        if args.cpu_seconds > 0 and world == 1:  # the CPU baseline is an N=1 figure
+        if args.full and args.cpu_seconds > 0 and world == 1:  # the CPU baseline is an N=1 figure
             if sampler == "uniform":
                 line["cpu_baseline"], strip_run = cpu_baseline(geom, params, cam_pos, args.cpu_seconds)
                 if "parity" in line and strip_run is not None:  # the baseline's strip is the same frame: check it too

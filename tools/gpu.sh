@@ -8,7 +8,7 @@
 # steps (one shell word each; quote a step that takes arguments):
 #   smoke                    __graft_entry__.smoke()
 #   tests[:<pytest args>]    pytest -m gpu (default: the whole GPU suite)
-#   bench[:<bench args>]     python bench.py --steps 20 --warmup 3 <args>
+#   bench[:<bench args>]     python bench.py --full --steps 20 --warmup 3 <args> (roofline, parity, CPU baseline)
 #   wbench:<workload>        the bench line of a workload with the profiled command's arguments
 #                            (so its roofline takes that profile's frames)
 #   kt:<workload>            counter-free rocprofv3 --kernel-trace --stats of the bench
@@ -65,9 +65,9 @@ for step in "$@"; do
   case $kind in
     smoke) run smoke 240 python3 -u -c "import __graft_entry__ as g; g.smoke()" ;;
     tests) run "tests" 900 python3 -u -m pytest ${arg:-tests} -m gpu -x -q --timeout 240 --timeout-method thread ;;
-    bench) run "bench${arg:+_$(echo "$arg" | tr -c 'a-z0-9' '_')}" 400 python3 -u bench.py --steps 20 --warmup 3 $arg ;;
+    bench) run "bench${arg:+_$(echo "$arg" | tr -c 'a-z0-9' '_')}" 400 python3 -u bench.py --full --steps 20 --warmup 3 $arg ;;
     wbench)
-      run "wbench_$arg" 400 $(bench_cmd "$arg" | sed 's/--cpu-seconds 0//') ;;
+      run "wbench_$arg" 400 $(bench_cmd "$arg" | sed 's/--cpu-seconds 0/--full/') ;;
     kt)
       w=${arg:-cornell}
       steps=""; [ "$w" = cornell ] && steps=40  # (others: the profiled command's own frames)
