@@ -295,6 +295,12 @@ int rt_dqn_trainer_create(rt_ctx* ctx, const float* nn_vertices, int n_in, const
                           float learning_rate, rt_dqn_trainer** out);
 int rt_dqn_trainer_destroy(rt_dqn_trainer* trainer);
 int rt_dqn_trainer_params(const rt_dqn_trainer* trainer, float* const* W /* 4 */, float* const* b /* 4 */);
+/* The gradients of the last training step (d loss / d parameter, as the backward pass wrote
+ * them: before the clipping scale is applied), in the layout of rt_dqn_trainer_params.
+ * Like rt_dqn_trainer_params a blocking copy (it waits for the device); a step left in
+ * flight on another stream must be synchronised by the caller first.  RT_E_INVALID if no
+ * step has run on this trainer. */
+int rt_dqn_trainer_gradients(const rt_dqn_trainer* trainer, float* const* W /* 4 */, float* const* b /* 4 */);
 /* Steps 5-7 of the training loop (neural_q_pathtracer.cu:478-513) on n rays: forward on the
  * current states (network input nn_vertices - loc), pick the taken actions, loss =
  * sum (target - q_a)^2 (sum_batches), backward, trainer.update().  Device arrays:

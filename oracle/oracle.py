@@ -547,3 +547,77 @@ class AdamRef:
 
     def params(self):
         return self.P[:4], self.P[4:]
+
+    def preactivations(self, loc):
+        """the four pre-activation matrices b + W x (n x width each), before the rectifiers"""
+        loc = np.asarray(loc, np.float64).reshape(-1, 3)
+        h = self.v[None, :] - np.tile(loc, (1, self.v.size // 3))
+        zs = []
+        for l in range(4):
+            z = h @ self.P[l].T + self.P[4 + l][None, :]
+            zs.append(z)
+            h = np.maximum(z, 0.0)
+        return zs
+
+
+def train_split_for(M, N, K):
+    """K slices of the device's M x N weight-gradient product over K rays (rt_train.hip
+    split_for): 64 x 64 tiles, slices of at least 256 rays, at most 64 of them."""
+    tiles = ((M + 63) // 64) * ((N + 63) // 64)
+    s = min((1024 + tiles - 1) // tiles, max(1, K // 256))
+    return max(1, min(s, 64))
+
+
+def loss_grads_f32(nn_vertices, W, b, loc, action, target, order="numpy"):
+    """AdamRef.loss_grads restated in float32 with numpy alone: the yardstick for how far a
+    correct single-precision backward pass lies from the fp64 one (no GPU, none of the
+    project's kernels).  The input nn_vertices - loc is built explicitly, every product and
+    sum is float32.  order "numpy": every contraction is numpy's own matmul.  order "chain":
+    each weight-gradient element is a strict chain over the rays in order -- the outer
+    products d_k h_k^T added row by row -- cut into train_split_for(...) slices of
+    ceil(n / slices) rays whose partial sums are then added in order, as the device's
+    split-K does.  Returns (loss, [dW0..dW3, db0..db3]) in float32."""
+    f = np.float32
+    v = np.asarray(nn_vertices, f).ravel()
+    W = [np.asarray(w, f) for w in W]
+    b = [np.asarray(x, f).ravel() for x in b]
+    loc = np.asarray(loc, f).reshape(-1, 3)
+    n = loc.shape[0]
+    hs = [v[None, :] - np.tile(loc, (1, v.size // 3))]
+    for l in range(4):
+        hs.append(np.maximum(hs[l] @ W[l].T + b[l][None, :], f(0)))
+    q = hs[4]
+    act = np.asarray(action, np.int64)
+    ok = (act >= 0) & (act < q.shape[1])
+    rows = np.nonzero(ok)[0]
+    qa = q[rows, act[ok]]
+    diff = np.asarray(target, f)[ok] - qa
+    loss = f(np.sum(diff * diff, dtype=f))
+    d = np.zeros_like(q)
+    d[rows, act[ok]] = np.where(qa > 0, f(-2) * diff, f(0))
+
+    def wgrad(d, h):
+        if order == "numpy":
+            return d.T @ h
+        if order != "chain":
+            raise ValueError(order)
+        M, N = d.shape[1], h.shape[1]
+        sk = train_split_for(M, N, n)
+        kc = (n + sk - 1) // sk
+        total, tmp = None, np.empty((M, N), f)
+        for z in range(sk):
+            acc = np.zeros((M, N), f)
+            for k in range(z * kc, min(n, (z + 1) * kc)):
+                if d[k].any():  # (a row of zeros adds nothing)
+                    np.multiply(d[k][:, None], h[k][None, :], out=tmp)
+                    acc += tmp
+            total = acc if total is None else total + acc
+        return total
+
+    gW, gb = [None] * 4, [None] * 4
+    for l in range(3, -1, -1):
+        gW[l] = wgrad(d, hs[l])
+        gb[l] = d.sum(0, dtype=f)
+        if l > 0:
+            d = (d @ W[l]) * (hs[l] > 0)
+    return loss, gW + gb

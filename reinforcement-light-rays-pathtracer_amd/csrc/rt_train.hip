@@ -307,12 +307,14 @@ __global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ d, int
 }
 
 // out[i] = sum_z slices[z][i], z in order (split-K and column-sum partials); 4 outputs
-// per thread (16-B loads) and 8 slices' loads in flight before their in-order adds
+// per thread (16-B loads) and 8 slices' loads in flight before their in-order adds; one
+// output at a time, the same sums, where len is no multiple of 4 or out is not aligned
 __global__ __launch_bounds__(256) void k_sum_slices(const float* __restrict__ slices, int n_slices, size_t len,
                                                     float* __restrict__ out) {
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= len) return;
-    if (i + 4 <= len && (len & 3) == 0) {
+    // (out is a block of the flat gradient array: 16-byte aligned only when the widths before it are)
+    if (i + 4 <= len && (len & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
         float4 s = *reinterpret_cast<const float4*>(slices + i);
         int z = 1;
         for (; z + 8 <= n_slices; z += 8) {
@@ -595,6 +597,20 @@ int rt_dqn_trainer_params(const rt_dqn_trainer* t, float* const* W, float* const
     RT_HIPE(hipSetDevice(t->device));
     std::vector<float> flat(t->n_par);
     RT_HIPE(hipMemcpy(flat.data(), t->P, sizeof(float) * t->n_par, hipMemcpyDeviceToHost));
+    for (int l = 0; l < 4; ++l) {
+        if (!W[l] || !b[l]) return err(RT_E_INVALID, "NULL layer buffer");
+        memcpy(W[l], flat.data() + t->w_off[l], sizeof(float) * (size_t)t->dims[l + 1] * t->dims[l]);
+        memcpy(b[l], flat.data() + t->b_off[l], sizeof(float) * (size_t)t->dims[l + 1]);
+    }
+    return RT_OK;
+}
+
+int rt_dqn_trainer_gradients(const rt_dqn_trainer* t, float* const* W, float* const* b) {
+    if (!t || !W || !b) return err(RT_E_INVALID, "NULL argument");
+    if (t->updates == 0) return err(RT_E_INVALID, "no training step has run");
+    RT_HIPE(hipSetDevice(t->device));
+    std::vector<float> flat(t->n_par);
+    RT_HIPE(hipMemcpy(flat.data(), t->G, sizeof(float) * t->n_par, hipMemcpyDeviceToHost));
     for (int l = 0; l < 4; ++l) {
         if (!W[l] || !b[l]) return err(RT_E_INVALID, "NULL layer buffer");
         memcpy(W[l], flat.data() + t->w_off[l], sizeof(float) * (size_t)t->dims[l + 1] * t->dims[l]);

@@ -254,6 +254,16 @@ class DqnTrainer:
         check(lib().rt_dqn_trainer_params(self._h, Wp, bp))
         return W, b
 
+    def grads(self) -> Tuple[list, list]:
+        """(dW, db) of the last step, as the backward pass wrote them (before the clipping
+        scale), in the layout of params(); a blocking copy; raises if no step has run."""
+        W = [np.zeros(s, np.float32) for s in self.shapes]
+        b = [np.zeros(s[0], np.float32) for s in self.shapes]
+        Wp = (ctypes.POINTER(ctypes.c_float) * 4)(*[_fp(w) for w in W])
+        bp = (ctypes.POINTER(ctypes.c_float) * 4)(*[_fp(x) for x in b])
+        check(lib().rt_dqn_trainer_gradients(self._h, Wp, bp))
+        return W, b
+
 
 class NeuralQ:
     """NeuralQPathtracer (GPU/deep_learning/neural_q_pathtracer.cu:226-600) on the device:
