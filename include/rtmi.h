@@ -242,14 +242,17 @@ int rt_dqn_create(rt_ctx* ctx, const float* nn_vertices, int n_in, const int32_t
                   rt_dqn** out);
 int rt_dqn_destroy(rt_dqn* dqn);
 /* Kernel of the forward pass (same Q bit for bit; A/B measurement):
- * RT_DQN_MLP_AUTO (default) and RT_DQN_MLP_STREAM: the weight-streaming kernel (64 rays per
- * workgroup, weight fragments from L2); RT_DQN_MLP_STATIONARY: the weight-stationary one
+ * RT_DQN_MLP_AUTO (default) and RT_DQN_MLP_STREAM: the weight-streaming kernel (rt_dqn_mlp_rows
+ * rays per workgroup, weight fragments from L2); RT_DQN_MLP_STATIONARY: the weight-stationary one
  * (weights resident in registers, one workgroup per CU) for the reference's 200-300-200
  * shape, the streaming one otherwise. */
 #define RT_DQN_MLP_AUTO 0
 #define RT_DQN_MLP_STREAM 1
 #define RT_DQN_MLP_STATIONARY 2
 int rt_dqn_set_mlp(rt_dqn* dqn, int mode);
+/* Rays per workgroup of the weight-streaming forward kernel in this build (16 per M-tile):
+ * the ray counts at which a launch takes one more workgroup, for tests and benchmarks. */
+int rt_dqn_mlp_rows(void);
 /* DQNetwork::network_inference on n ray positions (host arrays): q = n x 144. */
 int rt_dqn_forward(rt_ctx* ctx, const rt_dqn* dqn, const float* loc /* n x 3 */, int n, float* q);
 /* Same on device buffers, asynchronous on `stream`. */

@@ -262,6 +262,8 @@ int rt_dqn_set_mlp(rt_dqn* dqn, int mode) {
     return RT_OK;
 }
 
+int rt_dqn_mlp_rows(void) { return rt::dqn_mlp_tile_rows(); }
+
 int rt_dqn_forward(rt_ctx* ctx, const rt_dqn* dqn, const float* loc, int n, float* q) {
     if (!ctx || !dqn || (n > 0 && (!loc || !q))) return err(RT_E_INVALID, "NULL argument");
     if (n < 0) return err(RT_E_INVALID, "n < 0");

@@ -5,6 +5,8 @@
   write_dynet(path, params)   the same format out (rt_dynet_write), e.g. DqnTrainer.params()
   synthetic_weights(...)  seeded He-normal weights for scenes whose trained model the
                           reference does not ship (archway: 918 inputs)
+  exact_weights / selection_weights / grid_points   networks and rays on which the bf16
+                          forward is exact, so the device's Q can be pinned bit for bit
   Dqn(ctx, nn_vertices, weights)   device network (rt_dqn_create)
   forward / sample / render / render_tiles_device
   DqnTrainer(ctx, nn_vertices, weights)   Neural-Q training (rt_dqn_trainer_*): TD targets,
@@ -98,6 +100,93 @@ def glorot_weights(n_in: int, seed: int = 1984, hidden=HIDDEN, n_out: int = ACTI
         W.append(rng.uniform(-sw, sw, (dims[i + 1], dims[i])).astype(np.float32))
         sb = np.sqrt(6.0 / dims[i + 1])
         b.append(rng.uniform(-sb, sb, dims[i + 1]).astype(np.float32))
+    return W, b
+
+
+# ---- networks on which the bf16 forward is exact (tests/test_dqn_forward_exact.py) ----
+# Integer weights and biases with every coordinate on the grid of eighths: every product and
+# partial sum of every layer is a multiple of EXACT_GRID, bf16 rounding keeps it one, and
+# while sum |w a| + |b| <= 2^24 * EXACT_GRID the fp32 accumulation is exact in any order, so
+# the device's Q equals the fp64-accumulating restatement's bit for bit.
+EXACT_GRID = 0.125
+EXACT_HALF = 32            # grid points per axis on each side of 0: coordinates in [-4, 4]
+EXACT_FILLS = ("dense", "sparse")
+
+
+def mlp_rows() -> int:
+    """rays per workgroup of the weight-streaming forward kernel in this build (rt_dqn_mlp_rows)"""
+    return int(lib().rt_dqn_mlp_rows())
+
+
+def grid_points(n: int, seed: int = 1984) -> np.ndarray:
+    """n points of the 65^3 grid of eighths in [-4, 4]^3 in a seeded order, distinct while
+    n <= 65^3 (the order wraps after that); the first m rows of grid_points(n) are
+    grid_points(m)."""
+    side = 2 * EXACT_HALF + 1
+    idx = np.resize(np.random.default_rng(seed).permutation(side ** 3), n)
+    ijk = np.stack([idx // (side * side), (idx // side) % side, idx % side], axis=1)
+    return ((ijk - EXACT_HALF) * EXACT_GRID).astype(np.float32)
+
+
+def exact_weights(n_in: int, hidden=HIDDEN, fill: str = "dense", seed: int = 1984,
+                  n_out: int = ACTIONS) -> Tuple[list, list, np.ndarray]:
+    """(W, b, nn_vertices) of an integer network: layer 0 from {-1, 0, 1} with 8 non-zeros per
+    row; layers 1-3 from {-1, +1} with every entry non-zero (`dense`), or 12 non-zeros per
+    row from {-2, -1, 1, 2} (`sparse`); biases non-zero integers in [-3, 3]; nn_vertices on the grid
+    of eighths in [-4, 4].  A row of a hidden layer with no positive weight is negated, so a
+    narrow layer (one feature) still passes its input on."""
+    if fill not in EXACT_FILLS:
+        raise ValueError(f"fill must be one of {EXACT_FILLS}, got {fill!r}")
+    rng = np.random.default_rng(seed)
+    dims = [n_in, *hidden, n_out]
+    verts = (rng.integers(-EXACT_HALF, EXACT_HALF + 1, n_in) * EXACT_GRID).astype(np.float32)
+
+    def rows(n_rows, n_cols, nnz, values):
+        w = np.zeros((n_rows, n_cols), np.float32)
+        for o in range(n_rows):
+            cols = rng.permutation(n_cols)[:nnz]
+            w[o, cols] = rng.choice(values, cols.size)
+        return w
+
+    W = [rows(dims[1], n_in, 8, (-1.0, 1.0))]
+    for l in range(1, 4):
+        if fill == "dense":
+            w = rng.choice(np.array((-1.0, 1.0), np.float32), (dims[l + 1], dims[l]))
+        else:
+            w = rows(dims[l + 1], dims[l], 12, (-2.0, -1.0, 1.0, 2.0))
+        if l < 3:
+            w[(w <= 0).all(axis=1)] *= -1.0
+        W.append(np.ascontiguousarray(w, np.float32))
+    b = [rng.choice(np.array((-3, -2, -1, 1, 2, 3), np.float32), dims[l + 1]) for l in range(4)]
+    return W, b, verts
+
+
+def selection_weights(W0: np.ndarray, b0: np.ndarray, sel: Sequence[int], hidden=HIDDEN,
+                      n_out: int = ACTIONS) -> Tuple[list, list]:
+    """(W, b) with the given layer 0 and 0/1 selection matrices with zero bias behind it, so
+    that Q[a] = h1[sel[a]] exactly (a one-term sum; re-rounding a bf16 value changes nothing):
+    the folded layer 0 alone, on any input.  hidden[0] is W0's height; with hidden[1] and
+    hidden[2] at least that, layers 1-2 pass h1 on and layer 3 selects; otherwise layer 1
+    selects (hidden[1], hidden[2] >= n_out) and layers 2-3 pass the selection on."""
+    W0 = np.ascontiguousarray(W0, np.float32)
+    sel = np.asarray(sel, np.int64)
+    h1 = W0.shape[0]
+    if hidden[0] != h1 or sel.shape != (n_out,) or sel.min() < 0 or sel.max() >= h1:
+        raise ValueError("selection_weights: hidden[0] must be W0's height and sel index it")
+    dims = [W0.shape[1], *hidden, n_out]
+    W = [W0] + [np.zeros((dims[l + 1], dims[l]), np.float32) for l in range(1, 4)]
+    a = np.arange(n_out)
+    if hidden[1] >= h1 and hidden[2] >= h1:
+        W[1][np.arange(h1), np.arange(h1)] = 1.0
+        W[2][np.arange(h1), np.arange(h1)] = 1.0
+        W[3][a, sel] = 1.0
+    elif hidden[1] >= n_out and hidden[2] >= n_out:
+        W[1][a, sel] = 1.0
+        W[2][a, a] = 1.0
+        W[3][a, a] = 1.0
+    else:
+        raise ValueError(f"selection_weights: hidden {tuple(hidden)} too narrow")
+    b = [np.ascontiguousarray(b0, np.float32).ravel()] + [np.zeros(dims[l + 1], np.float32) for l in range(1, 4)]
     return W, b
 
 

@@ -7,7 +7,8 @@ Parity levels:
     layers 1-3, vs the oracle's forward with the same arithmetic (same fold, same
     operand and activation rounding, exact accumulation): max |dq| <= 2e-2 * max|q|,
     mean <= 2e-3 * mean|q|; vs the fp32 forward (the reference's DyNet arithmetic):
-    mean <= 1e-2 * mean|q|
+    mean <= 1e-2 * mean|q|; bit for bit on networks where fp32 accumulation is exact, at
+    every hidden-width class and ray-count edge, both kernels (test_dqn_forward_exact.py)
   * render: statistical (a Q perturbation can flip one sampled cell and change a path):
     MAPE(gpu, oracle) must not exceed the oracle's own seed-to-seed MAPE.
 """
@@ -122,6 +123,25 @@ def test_forward_matches_oracle(rtmi_mod, oracle_mod, gpu_ctx, kind):
     g = rtmi_mod.obj_geometry(os.path.join(MODELS, f"{kind}.obj"), kind)
     W, b = trained(rtmi_mod) if kind == "door_room" else rtmi_mod.dqn.synthetic_weights(g.nn_vertices.size)
     pts, _ = room_points(g, 777, 3)  # not a multiple of the 64-row tile
+    with rtmi_mod.dqn.Dqn(gpu_ctx, g.nn_vertices, W, b) as net:
+        q = net.forward(pts)
+    qe = oracle_mod.dqn_forward(W, b, g.nn_vertices, pts, bf16=True)
+    qf = oracle_mod.dqn_forward(W, b, g.nn_vertices, pts, bf16=False)
+    err = np.abs(q - qe)
+    assert err.max() <= 2e-2 * np.abs(qe).max() + 1e-6, err.max()
+    assert err.mean() <= 2e-3 * np.abs(qe).mean() + 1e-7, err.mean()
+    assert np.abs(q - qf).mean() <= 1e-2 * np.abs(qf).mean()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hidden", [(96, 160, 96), (33, 31, 65), (224, 320, 224)], ids=lambda h: "-".join(map(str, h)))
+def test_forward_matches_oracle_other_widths(rtmi_mod, oracle_mod, gpu_ctx, hidden):
+    """test_forward_matches_oracle's rule, tolerances unchanged, on ordinary floats at widths
+    other than the reference's: the generic K loop of k_dqn_mlp (odd step counts, ragged
+    widths) and the reference-shape body with no zero padding in K."""
+    g = door(rtmi_mod)
+    W, b = rtmi_mod.dqn.synthetic_weights(g.nn_vertices.size, hidden=hidden)
+    pts, _ = room_points(g, 777, 3)
     with rtmi_mod.dqn.Dqn(gpu_ctx, g.nn_vertices, W, b) as net:
         q = net.forward(pts)
     qe = oracle_mod.dqn_forward(W, b, g.nn_vertices, pts, bf16=True)
@@ -267,6 +287,28 @@ def test_config4_bit_exact_downstream_of_forward(rtmi_mod, oracle_mod, gpu_ctx):
         ref, rc, calls = oracle_mod.render_dqn_wave(g, oracle_mod.camera(rtmi_mod.CAMERAS["archway"]),
                                                     oracle_mod.params_from(p), net.forward, rect)
     assert len(calls) > 20
+    assert casts == rc, (casts, rc)
+    assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), \
+        int((img.view(np.uint32) != ref.view(np.uint32)).sum())
+
+
+@pytest.mark.gpu
+def test_dqn_render_bit_exact_downstream_of_forward_generic_network(rtmi_mod, oracle_mod, gpu_ctx):
+    """The renderer's bf16 action-major Q on a network that takes the generic body of
+    k_dqn_mlp (hidden 96-160-96: k_dqn_mlp<.., QB> with the K loop, which runs only inside a
+    render): the door room at 128x128, a 32x32 window, 2 spp, GPU preset, bit for bit in image
+    and ray casts against the restatement's wavefront render fed by the device forward, as
+    test_config4_bit_exact_downstream_of_forward does for the reference shape."""
+    g = door(rtmi_mod)
+    W, b = rtmi_mod.dqn.synthetic_weights(g.nn_vertices.size, hidden=(96, 160, 96))
+    p = rtmi_mod.default_params(rtmi_mod.RT_PRESET_GPU, width=128, height=128, spp=2)
+    rect = (48, 48, 32, 32)
+    cam = rtmi_mod.camera(rtmi_mod.CAMERAS["door_room"])
+    with rtmi_mod.Scene(gpu_ctx, g) as sc, rtmi_mod.dqn.Dqn(gpu_ctx, g.nn_vertices, W, b) as net:
+        img, casts = rtmi_mod.dqn.render(gpu_ctx, sc, net, cam, p, rect)
+        ref, rc, calls = oracle_mod.render_dqn_wave(g, oracle_mod.camera(rtmi_mod.CAMERAS["door_room"]),
+                                                    oracle_mod.params_from(p), net.forward, rect)
+    assert len(calls) > 10 and img.mean() > 0
     assert casts == rc, (casts, rc)
     assert np.array_equal(img.view(np.uint32), ref.view(np.uint32)), \
         int((img.view(np.uint32) != ref.view(np.uint32)).sum())
