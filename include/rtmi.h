@@ -162,6 +162,30 @@ int rt_intersect_device(rt_ctx* ctx, const rt_scene* scene, const float* d_orig,
 int rt_intersect_method(rt_ctx* ctx, const rt_scene* scene, const float* orig, const float* dir, int n,
                         float t_scale, int hit_rule, int method, float* out_t, int32_t* out_hit,
                         int32_t* out_cand);
+/* Diagnostic: rt_intersect by the candidate route of the render kernels -- the exact test of a
+ * ray's candidate triangles only, in index order, the rest shared by the ray's wave -- with the
+ * candidates chosen by `source`:
+ *   RT_CAND_TABLE  surf[n]: ray r is taken as a bounce ray leaving surface surf[r]; its
+ *                  candidates come from the scene's bounce-ray candidate table for hit_rule
+ *                  (built on first use and kept, as a render builds it).  out_masks (optional):
+ *                  the masks the device lookup gave, words = ceil(n_tri / 64) per ray, bit
+ *                  i % 64 of word i / 64 = triangle i.  The hits are rt_intersect's as long as
+ *                  the table is sound for the rays.
+ *   RT_CAND_GIVEN  masks_in[n][words]: the caller's candidates (the GPU preset's camera rays
+ *                  take their tile's cull masks this way).  The hit is that of the scan
+ *                  restricted to the ray's mask; a ray with an empty mask hits nothing.
+ * pair_cap: the length of the wave's shared pair list, one the render kernels are built with:
+ * RT_CAND_CAP_TABLE (scenes of at most 64 triangles) or RT_CAND_CAP_SHARED; anything else is
+ * RT_E_INVALID.  RT_E_UNSUPPORTED: a scene of more than 256 triangles or on the BVH path, or
+ * (RT_CAND_TABLE) no table for the scene at this hit_rule and t_scale (the CPU rule's serves
+ * t_scale >= 256).  Never falls back to another method.  Replaces no reference interface. */
+#define RT_CAND_TABLE 0
+#define RT_CAND_GIVEN 1
+#define RT_CAND_CAP_TABLE 96
+#define RT_CAND_CAP_SHARED 256
+int rt_intersect_cand(rt_ctx* ctx, const rt_scene* scene, const float* orig, const float* dir, int n, float t_scale,
+                      int hit_rule, int source, const int32_t* surf, const uint64_t* masks_in, int pair_cap,
+                      float* out_t, int32_t* out_hit, uint64_t* out_masks);
 
 /* ---- acceleration structure for large scenes ----
  * The reference scans every triangle per ray (CPU/rays/ray.cpp:14-28, GPU/rays/ray.cu:

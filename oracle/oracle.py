@@ -124,6 +124,25 @@ def intersect(tri, n_surf, n_light, light_group, orig, direction, t_scale, hit_r
     return out_t, out_h
 
 
+def intersect_masked(tri, n_surf, n_light, light_group, orig, direction, masks, t_scale, hit_rule):
+    """intersect() restricted to each ray's candidates, masks (n_rays, ceil(n_tri / 64)) uint64:
+    the mask's triangles in index order through the rule's own window (orc_intersect_masked)."""
+    t_all = np.ascontiguousarray(tri, np.float32)
+    g = np.ascontiguousarray(light_group, np.int32)
+    o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    m = np.ascontiguousarray(masks, np.uint64).reshape(n, (n_surf + n_light + 63) // 64)
+    out_t = np.zeros(n, np.float32)
+    out_h = np.zeros(n, np.int32)
+    L = lib()
+    L.orc_intersect_masked.argtypes = [_FP, ctypes.c_int, ctypes.c_int, _IP, _FP, _FP, ctypes.c_void_p,
+                                       ctypes.c_int, ctypes.c_float, ctypes.c_int, _FP, _IP]
+    L.orc_intersect_masked(_f(t_all), n_surf, n_light, _i(g), _f(o), _f(d), m.ctypes.data_as(ctypes.c_void_p), n,
+                           t_scale, hit_rule, _f(out_t), _i(out_h))
+    return out_t, out_h
+
+
 def pass_masks(tri, orig, direction, t_scale, hit_rule):
     """[n_rays][ceil(n_tri / 64)] uint64: bit i = triangle i passes the exact test (no
     closest-hit window) -- what a candidate filter must keep (orc_pass_masks)."""

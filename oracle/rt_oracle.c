@@ -302,7 +302,9 @@ typedef struct {
     int tri;       /* unified triangle index, -1 none */
 } hit_t;
 
-static hit_t closest_hit(const orc_scene *sc, v3 o, v3 d, float t_scale, int hit_rule) {
+/* mask (NULL: every triangle): only the triangles whose bit is set are tested, in index order */
+static hit_t closest_hit_masked(const orc_scene *sc, v3 o, v3 d, float t_scale, int hit_rule,
+                                const uint64_t *mask) {
     hit_t h;
     h.tri = -1;
     h.t = (hit_rule == 0) ? FLT_MAX : 999999.0f;
@@ -310,6 +312,7 @@ static hit_t closest_hit(const orc_scene *sc, v3 o, v3 d, float t_scale, int hit
     v3 nD = mk(-D.x, -D.y, -D.z);
     int n = sc->n_surf + sc->n_light;
     for (int i = 0; i < n; i++) {
+        if (mask && !((mask[i / 64] >> (i % 64)) & 1u)) continue;
         v3 v0 = vtx(sc->tri, i, 0), v1 = vtx(sc->tri, i, 1), v2 = vtx(sc->tri, i, 2);
         v3 e1 = mk(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z);
         v3 e2 = mk(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z);
@@ -336,6 +339,10 @@ static hit_t closest_hit(const orc_scene *sc, v3 o, v3 d, float t_scale, int hit
         }
     }
     return h;
+}
+
+static hit_t closest_hit(const orc_scene *sc, v3 o, v3 d, float t_scale, int hit_rule) {
+    return closest_hit_masked(sc, o, d, t_scale, hit_rule, NULL);
 }
 
 static int32_t pack_hit(const orc_scene *sc, int tri, int hit_rule) {
@@ -366,6 +373,28 @@ ORC_API void orc_intersect(const float *tri, int n_surf, int n_light, const int3
         v3 o = mk(orig[r * 3], orig[r * 3 + 1], orig[r * 3 + 2]);
         v3 d = mk(dir[r * 3], dir[r * 3 + 1], dir[r * 3 + 2]);
         hit_t h = closest_hit(&sc, o, d, t_scale, hit_rule);
+        out_t[r] = h.tri >= 0 ? h.t : INFINITY;
+        out_hit[r] = pack_hit(&sc, h.tri, hit_rule);
+    }
+    free(sc.normal);
+}
+
+/* orc_intersect restricted to each ray's candidates: bit i % 64 of masks[r * words + i / 64]
+ * (words = ceil((n_surf + n_light) / 64)) = triangle i is tested for ray r.  The triangles
+ * of the mask in index order through the rule's own window -- rule 0's t < best + 1e-5, which
+ * depends on that order, rule 1's t < best from 999999 -- so the expected (t, hit) of the
+ * kernels' candidate route for any mask, one that omits the scan's hit included. */
+ORC_API void orc_intersect_masked(const float *tri, int n_surf, int n_light, const int32_t *light_group,
+                                  const float *orig, const float *dir, const uint64_t *masks, int n,
+                                  float t_scale, int hit_rule, float *out_t, int32_t *out_hit) {
+    orc_scene sc;
+    scene_init(&sc, tri, NULL, n_surf, NULL, light_group, n_light);
+    const int words = (n_surf + n_light + 63) / 64;
+    #pragma omp parallel for schedule(static)
+    for (int r = 0; r < n; r++) {
+        v3 o = mk(orig[r * 3], orig[r * 3 + 1], orig[r * 3 + 2]);
+        v3 d = mk(dir[r * 3], dir[r * 3 + 1], dir[r * 3 + 2]);
+        hit_t h = closest_hit_masked(&sc, o, d, t_scale, hit_rule, masks + (size_t)r * words);
         out_t[r] = h.tri >= 0 ? h.t : INFINITY;
         out_hit[r] = pack_hit(&sc, h.tri, hit_rule);
     }

@@ -1107,6 +1107,72 @@ int rt_intersect_method(rt_ctx* ctx, const rt_scene* scene, const float* orig, c
     return RT_OK;
 }
 
+int rt_intersect_cand(rt_ctx* ctx, const rt_scene* scene, const float* orig, const float* dir, int n, float t_scale,
+                      int hit_rule, int source, const int32_t* surf, const uint64_t* masks_in, int pair_cap,
+                      float* out_t, int32_t* out_hit, uint64_t* out_masks) {
+    if (!ctx || !scene) return fail(RT_E_INVALID, "ctx/scene is NULL");
+    if (n < 0) return fail(RT_E_INVALID, "n < 0");
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit_rule");
+    if (source != RT_CAND_TABLE && source != RT_CAND_GIVEN) return fail(RT_E_INVALID, "bad source %d", source);
+    const int n_tri = scene->dev.n_tri;
+    if (n_tri > 64 * rt::kCtabMaxWords || scene_uses_bvh(scene))
+        return fail(RT_E_UNSUPPORTED, "the candidate route serves scan scenes of at most %d triangles",
+                    64 * rt::kCtabMaxWords);
+    if (!rt::cand_pair_cap_served(n_tri, pair_cap))
+        return fail(RT_E_INVALID, "no render kernel uses pair cap %d with %d triangles", pair_cap, n_tri);
+    if (source == RT_CAND_GIVEN && out_masks) return fail(RT_E_INVALID, "out_masks needs RT_CAND_TABLE");
+    if (n == 0) return RT_OK;
+    if (!orig || !dir || !out_t || !out_hit) return fail(RT_E_INVALID, "NULL buffer");
+    if (source == RT_CAND_TABLE ? !surf : !masks_in) return fail(RT_E_INVALID, "the source's per-ray input is NULL");
+    const int words = (n_tri + 63) / 64;
+    if (source == RT_CAND_GIVEN) {  // a bit past the last triangle would index past the scene's records
+        const uint64_t live = (n_tri % 64) ? ((1ull << (n_tri % 64)) - 1ull) : ~0ull;
+        for (size_t r = 0; r < (size_t)n; ++r)
+            if (masks_in[r * words + (words - 1)] & ~live)
+                return fail(RT_E_INVALID, "ray %zu: a candidate bit past triangle %d", r, n_tri - 1);
+    }
+    int rc = set_device(ctx);
+    if (rc != RT_OK) return rc;
+    if (source == RT_CAND_TABLE) {
+        if (hit_rule == RT_HIT_RULE_CPU && !(t_scale >= rt::kCtabTsMin))
+            return fail(RT_E_UNSUPPORTED, "the CPU rule's table serves t_scale >= %g", (double)rt::kCtabTsMin);
+        rc = rt::scene_ensure_ctab(scene, hit_rule, t_scale, /*wanted=*/true);
+        if (rc != RT_OK) return rc;
+        const rt::CtabDev& T = scene->dev.ctab[hit_rule];
+        if (T.masks == nullptr || T.words != words || !(t_scale >= T.ts_min))
+            return fail(RT_E_UNSUPPORTED, "no candidate table for this scene / hit rule / t_scale");
+    }
+    float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
+    int32_t *d_h = nullptr, *d_s = nullptr;
+    unsigned long long *d_mi = nullptr, *d_mo = nullptr;
+    const size_t b3 = sizeof(float) * 3 * (size_t)n, bm = sizeof(uint64_t) * (size_t)n * (size_t)words;
+    hipError_t e = hipMalloc(&d_o, b3);
+    if (e == hipSuccess) e = hipMalloc(&d_d, b3);
+    if (e == hipSuccess) e = hipMalloc(&d_t, sizeof(float) * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc(&d_h, sizeof(int32_t) * (size_t)n);
+    if (e == hipSuccess && source == RT_CAND_TABLE) e = hipMalloc(&d_s, sizeof(int32_t) * (size_t)n);
+    if (e == hipSuccess && source == RT_CAND_GIVEN) e = hipMalloc(&d_mi, bm);
+    if (e == hipSuccess && out_masks) e = hipMalloc(&d_mo, bm);
+    if (e == hipSuccess) e = hipMemcpy(d_o, orig, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_d, dir, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess && d_s) e = hipMemcpy(d_s, surf, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess && d_mi) e = hipMemcpy(d_mi, masks_in, bm, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = rt::launch_intersect_cand(scene->dev, d_o, d_d, n, t_scale, hit_rule, d_s, d_mi, pair_cap, d_t, d_h, d_mo, 0);
+    if (e == hipSuccess) e = hipMemcpy(out_t, d_t, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_hit, d_h, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && d_mo) e = hipMemcpy(out_masks, d_mo, bm, hipMemcpyDeviceToHost);
+    (void)hipFree(d_o);
+    (void)hipFree(d_d);
+    (void)hipFree(d_t);
+    (void)hipFree(d_h);
+    if (d_s) (void)hipFree(d_s);
+    if (d_mi) (void)hipFree(d_mi);
+    if (d_mo) (void)hipFree(d_mo);
+    if (e != hipSuccess) return fail(RT_E_HIP, "rt_intersect_cand: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
 int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt_params* params,
               int x0, int y0, int w, int h, float* out_rgb, uint64_t* out_ray_casts) {
     if (!ctx || !scene || !cam || !out_rgb) return fail(RT_E_INVALID, "NULL argument");

@@ -466,6 +466,12 @@ hipError_t launch_intersect_bvh(const DeviceScene& s, const float* orig, const f
 // the matrix-core filter (closest_hit_mf) on caller rays; cand: optional candidates per ray
 hipError_t launch_intersect_mf(const DeviceScene& s, const float* orig, const float* dir, int n, float t_scale,
                                int hit_rule, float* out_t, int32_t* out_hit, int32_t* cand, hipStream_t stream);
+// the candidate route (closest_hit_ctab with surf, closest_hit_cand on masks_in) on caller rays, in the
+// render kernels' instantiations; hipErrorInvalidValue: no such instantiation, or no table for t_scale
+hipError_t launch_intersect_cand(const DeviceScene& s, const float* orig, const float* dir, int n, float t_scale,
+                                 int hit_rule, const int32_t* surf, const unsigned long long* masks_in, int pair_cap,
+                                 float* out_t, int32_t* out_hit, unsigned long long* out_masks, hipStream_t stream);
+bool cand_pair_cap_served(int n_tri, int pair_cap);  // a render kernel instantiates (mask words of n_tri, pair_cap)
 
 // exhaustive rcp_rn == 1.0f/x check over all 2^32 floats (4096 x 256 threads x 4096)
 hipError_t launch_selftest(int which, unsigned long long* mism, unsigned* first, hipStream_t stream);

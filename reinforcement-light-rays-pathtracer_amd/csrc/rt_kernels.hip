@@ -72,6 +72,52 @@ __global__ __launch_bounds__(256) void k_intersect_mf(const DeviceScene s, const
     if (cand != nullptr) cand[r] = nc;
 }
 
+// The candidate route on caller rays (rt_intersect_cand): every lane of a wave takes part,
+// lanes past n hold no candidates (F = 0).  surf != nullptr: the candidates from the scene's
+// table as a bounce ray leaving surf[r] gets them (closest_hit_ctab; out_masks, optional:
+// what the lookup gave, `words` per ray); else the caller's masks_in (closest_hit_cand, as
+// k_render_pq<.., CT> feeds it the rectangle cull's masks).  Each wave's LDS block is exactly
+// mf_wave_floats(CAP, RULE) floats and the four are adjacent, as in the render kernels of
+// the same instantiation: a write past a block lands in the next wave's rays.
+template <int RULE, int NW, int CAP>
+__global__ __launch_bounds__(256) void k_intersect_cand(const DeviceScene s, const int32_t* __restrict__ code,
+                                                        const float* __restrict__ orig,
+                                                        const float* __restrict__ dir, int n, float t_scale,
+                                                        const int32_t* __restrict__ surf,
+                                                        const unsigned long long* __restrict__ masks_in, int words,
+                                                        float* __restrict__ out_t, int32_t* __restrict__ out_hit,
+                                                        unsigned long long* __restrict__ out_masks) {
+    constexpr int wf = mf_wave_floats(CAP, RULE);
+    static_assert(wf % 2 == 0, "the blocks' 64-bit keys and masks stay aligned");
+    __shared__ __attribute__((aligned(16))) float wls[4 * wf];
+    float* wl = wls + (threadIdx.x >> 6) * wf;
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = r < n;
+    const f3 o = in ? make3(orig[3 * r + 0], orig[3 * r + 1], orig[3 * r + 2]) : make3(0.0f, 0.0f, 0.0f);
+    const f3 d = in ? make3(dir[3 * r + 0], dir[3 * r + 1], dir[3 * r + 2]) : make3(0.0f, 0.0f, 1.0f);
+    Hit h;
+    if (surf != nullptr) {  // (wave-uniform)
+        const CtabDev& T = s.ctab[RULE];
+        const int sf = in ? surf[r] : -1;
+        if (in && out_masks != nullptr) {
+            uint64_t F[NW];
+            ctab_candidates<NW>(T, s.n_tri, s.n_surf, sf, o, d, F);
+#pragma unroll
+            for (int k = 0; k < NW; ++k)
+                if (k < words) out_masks[(size_t)r * words + k] = F[k];
+        }
+        h = closest_hit_ctab<RULE, NW, CAP>(s, T, sf, o, d, t_scale, in, wl);
+    } else {
+        uint64_t F[NW];
+#pragma unroll
+        for (int k = 0; k < NW; ++k) F[k] = (in && k < words) ? masks_in[(size_t)r * words + k] : 0ull;
+        h = closest_hit_cand<RULE, NW, CAP>(s, F, o, d, t_scale, wl);
+    }
+    if (!in) return;
+    out_t[r] = (h.tri >= 0) ? h.t : __builtin_inff();
+    out_hit[r] = (h.tri >= 0) ? code[h.tri] : -1;
+}
+
 // The exact BVH path on caller rays (large scenes).
 template <int RULE>
 __global__ __launch_bounds__(256) void k_intersect_bvh(const DeviceScene s, const int32_t* __restrict__ code,
@@ -1264,6 +1310,48 @@ hipError_t launch_intersect_mf(const DeviceScene& s, const float* orig, const fl
     else
         hipLaunchKernelGGL(k_intersect_mf<1>, grid, block, 0, stream, s, s.code_gpu, orig, dir, n, t_scale, out_t,
                            out_hit, cand);
+    return hipGetLastError();
+}
+
+// The instantiations of the candidate route the render kernels use: one mask word (scenes of
+// at most 64 triangles) with either pair cap, four words with kMfPairCap.  surf: the table
+// route (s.ctab[hit_rule] must serve t_scale), else masks_in.
+bool cand_pair_cap_served(int n_tri, int pair_cap) {
+    return n_tri > 0 && n_tri <= 256 && (pair_cap == kMfPairCap || (pair_cap == kCtPairCap && n_tri <= 64));
+}
+hipError_t launch_intersect_cand(const DeviceScene& s, const float* orig, const float* dir, int n, float t_scale,
+                                 int hit_rule, const int32_t* surf, const unsigned long long* masks_in, int pair_cap,
+                                 float* out_t, int32_t* out_hit, unsigned long long* out_masks, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    const int words = (s.n_tri + 63) / 64;
+    const int nw = s.n_tri <= 64 ? 1 : 4;
+    if (s.n_tri <= 0 || words > nw || (surf == nullptr) == (masks_in == nullptr)) return hipErrorInvalidValue;
+    if (!cand_pair_cap_served(s.n_tri, pair_cap)) return hipErrorInvalidValue;
+    if (surf != nullptr && (s.ctab[hit_rule].masks == nullptr || s.ctab[hit_rule].words != words ||
+                            s.ctab[hit_rule].bins != kCtabBins || s.ctab[hit_rule].graze_n != kCtabGraze ||
+                            !(t_scale >= s.ctab[hit_rule].ts_min)))
+        return hipErrorInvalidValue;
+    const dim3 block(256), grid((unsigned)((n + 255) / 256));
+    const int32_t* code = hit_rule == 0 ? s.code_cpu : s.code_gpu;
+#define RT_LAUNCH_CAND(RULE, NW, CAP)                                                                            \
+    hipLaunchKernelGGL((k_intersect_cand<RULE, NW, CAP>), grid, block, 0, stream, s, code, orig, dir, n, t_scale, \
+                       surf, masks_in, words, out_t, out_hit, out_masks)
+    if (hit_rule == 0) {
+        if (nw == 4)
+            RT_LAUNCH_CAND(0, 4, kMfPairCap);
+        else if (pair_cap == kMfPairCap)
+            RT_LAUNCH_CAND(0, 1, kMfPairCap);
+        else
+            RT_LAUNCH_CAND(0, 1, kCtPairCap);
+    } else {
+        if (nw == 4)
+            RT_LAUNCH_CAND(1, 4, kMfPairCap);
+        else if (pair_cap == kMfPairCap)
+            RT_LAUNCH_CAND(1, 1, kMfPairCap);
+        else
+            RT_LAUNCH_CAND(1, 1, kCtPairCap);
+    }
+#undef RT_LAUNCH_CAND
     return hipGetLastError();
 }
 

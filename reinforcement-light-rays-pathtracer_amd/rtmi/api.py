@@ -235,6 +235,43 @@ def intersect_method(ctx: Context, scene: Scene, orig: np.ndarray, direction: np
     return (t, h, c) if count else (t, h)
 
 
+CAND_TABLE, CAND_GIVEN = 0, 1
+CAND_CAP_TABLE, CAND_CAP_SHARED = 96, 256
+
+
+def intersect_cand(ctx: Context, scene: Scene, orig: np.ndarray, direction: np.ndarray, t_scale: float,
+                   hit_rule: int, surf: Optional[np.ndarray] = None, masks: Optional[np.ndarray] = None,
+                   pair_cap: int = CAND_CAP_SHARED, guard: int = 0):
+    """rt_intersect_cand.  With `surf` (CAND_TABLE): the rays as bounce rays leaving those
+    surfaces, candidates from the scene's table -> (t, hit, masks the device lookup gave).
+    With `masks` (CAND_GIVEN, (n, words) uint64): the exact phase on those candidates ->
+    (t, hit).  guard > 0: the outputs carry that many extra elements after the n results,
+    filled with a pattern the call must leave alone (0xA5 bytes)."""
+    if (surf is None) == (masks is None):
+        raise ValueError("give surf (the table route) or masks (given candidates)")
+    o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    words = (scene.geom.n_tri + 63) // 64
+    u64 = ctypes.POINTER(ctypes.c_uint64)
+    t = np.full(n + guard, 0xA5A5A5A5, np.uint32).view(np.float32)
+    h = np.full(n + guard, 0xA5A5A5A5, np.uint32).view(np.int32)
+    if surf is not None:
+        s = np.ascontiguousarray(surf, np.int32).ravel()
+        if s.shape[0] != n:
+            raise ValueError("surf: one entry per ray")
+        m = np.full((n + guard, words), 0xA5A5A5A5A5A5A5A5, np.uint64)
+        check(lib().rt_intersect_cand(ctx.handle, scene.handle, _fp(o), _fp(d), n, float(t_scale), hit_rule,
+                                      CAND_TABLE, _ip(s), None, pair_cap, _fp(t), _ip(h), m.ctypes.data_as(u64)))
+        return (t, h, m) if guard else (t[:n], h[:n], m[:n])
+    mi = np.ascontiguousarray(masks, np.uint64).reshape(n, -1)
+    if mi.shape[1] != words:
+        raise ValueError(f"masks: {words} words per ray")
+    check(lib().rt_intersect_cand(ctx.handle, scene.handle, _fp(o), _fp(d), n, float(t_scale), hit_rule,
+                                  CAND_GIVEN, None, mi.ctypes.data_as(u64), pair_cap, _fp(t), _ip(h), None))
+    return (t, h) if guard else (t[:n], h[:n])
+
+
 def intersect_device(ctx: Context, scene: Scene, orig_ptr: int, dir_ptr: int, n: int,
                      t_scale: float, hit_rule: int, t_ptr: int, hit_ptr: int, stream: int = 0):
     check(lib().rt_intersect_device(ctx.handle, scene.handle, ctypes.c_void_p(orig_ptr),
