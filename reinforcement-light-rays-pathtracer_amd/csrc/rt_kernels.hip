@@ -697,13 +697,139 @@ __global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
     }
 }
 
+#ifndef RT_PS_POOL
+// The table-route kernel defers the retraces of the light pre-test to one pooled trip of the
+// workgroup (ps_pool) instead of keeping each in its lane for the wave's next trip (0: A/B builds)
+#define RT_PS_POOL 1
+#endif
+#ifndef RT_PS_FOLD_LDS
+#define RT_PS_FOLD_LDS 1  // 0: ps_finish folds a pixel's chunk sums with shuffles on all lanes (A/B builds)
+#endif
+#ifndef RT_PS_POOL_SPAN
+// entries of the pooled trip a wave takes per step.  Cornell workgroups defer 10-35 samples, so
+// at 64 the first wave serves them all in one step; a build with a small span (4) puts the same
+// frames through every wave and through several steps (test builds)
+#define RT_PS_POOL_SPAN 64
+#endif
+// whether k_render_ps<.., MF, CT> runs the pooled trip: its two barriers are compiled in or not
+// with this constant alone, never chosen at run time
+__host__ __device__ constexpr bool ps_pooled(int mf, bool ct) {
+    return RT_PS_POOL && RT_PS_STEAL && RT_PS_LIGHT_SPLIT && ct && mf == 1;
+}
+// a deferred sample's slot code: the surface to shade (the terminal ray's origin) and the
+// path's first surface -- the table route has at most 64 triangles, so 6 bits each
+__device__ __forceinline__ int ps_defer_code(int hit_tri, int f_tri0) { return (1 << 12) | (f_tri0 << 6) | hit_tri; }
+
+// the next direction from the surface hit (pos, hit_tri) at bounce depth dep of sample cur of
+// pixel lpix: cos theta and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the
+// path's Philox draw
+template <int SAMPLER>
+__device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4* __restrict__ shade, uint32_t lpix,
+                                             int cur, int dep, const f3& pos, int hit_tri, float* cos_out, f3* o_out,
+                                             f3* d_out) {
+    const float4 N = shade[hit_tri * kShadeF4 + 0];
+    const float4 T = shade[hit_tri * kShadeF4 + 1];
+    const float4 B = shade[hit_tri * kShadeF4 + 2];
+    float r1, r2;
+    draw2(lpix, (uint32_t)cur, 1u + (uint32_t)dep, a.seed_lo, a.seed_hi, &r1, &r2);
+    float cos_theta, sin_theta;
+    if (SAMPLER == 0) {
+        cos_theta = r1;
+        sin_theta = sqrtf(1.0f - r1 * r1);
+    } else {
+        cos_theta = sqrtf(r1);
+        sin_theta = sqrtf(1.0f - r1);
+    }
+    float sphi, cphi;
+    sincos_turn(r2, &sphi, &cphi);
+    const float sx = sin_theta * cphi, sz = sin_theta * sphi;
+    const f3 sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x,
+                        (sx * B.y + cos_theta * N.y) + sz * T.y,
+                        (sx * B.z + cos_theta * N.z) + sz * T.z);
+    *cos_out = cos_theta;
+    *o_out = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
+    *d_out = normalize(sd);
+}
+// folds the light L back through the bounce at surface tri whose direction had cos theta = c
+template <int SAMPLER>
+__device__ __forceinline__ void ps_fold(const float4* __restrict__ shade, f3& L, int tri, float cosv) {
+    const float4 c = shade[tri * kShadeF4 + (SAMPLER == 0 ? 3 : 4)];
+    if (SAMPLER == 0) {
+        L.x = div_rho((L.x * c.x) * cosv);
+        L.y = div_rho((L.y * c.y) * cosv);
+        L.z = div_rho((L.z * c.z) * cosv);
+    } else {
+        L = make3(L.x * c.x, L.y * c.y, L.z * c.z);
+    }
+}
+
+// the end of k_render_ps for one wave with at least one pixel: every lane sums its own slots
+// in sample order onto acc (RT_PS_STEAL: ended samples hold their value in fields 0..2), the
+// chunk sums of a pixel fold in chunk order and the pixel is stored
+__device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc& blk, int chunk, int lane, int lx,
+                                          int ly, bool valid, f3 acc) {
+#if RT_PS_STEAL
+    extern __shared__ float s_ps[];
+    const int pc = a.per_chunk;
+    const float* const slots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc) + lane;
+    for (int kk = 0; kk < pc; ++kk) {
+        const float* sl = slots + kk * kPsFields * 64;
+        acc.x = acc.x + sl[0 * 64];
+        acc.y = acc.y + sl[1 * 64];
+        acc.z = acc.z + sl[2 * 64];
+    }
+#endif
+    // fold the chunk sums of a pixel in chunk order: ((P0 + P1) + P2) + ...
+    const int base = lane & ~(a.split - 1);
+#if RT_PS_FOLD_LDS
+    // From four chunks on, through LDS: the lanes park their sums in the wave's slot region
+    // (row c of slot 0, position lane: the lane's own, already summed above) and the pixel's
+    // lanes of chunk 0, 1 and 2 each walk one channel in chunk order -- the same additions on
+    // the same operands as the shuffle fold below, which keeps all 64 lanes busy for
+    // split - 1 dependent rounds of three cross-lane reads each.
+    if (a.split >= 4) {
+        extern __shared__ float s_ps[];
+        float* const parkf = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(a.per_chunk);
+        parkf[0 * 64 + lane] = acc.x;
+        parkf[1 * 64 + lane] = acc.y;
+        parkf[2 * 64 + lane] = acc.z;
+        wave_lds_sync();
+        if (valid && chunk < 3) {
+            const float* src = parkf + chunk * 64 + base;
+            float t = src[0];
+            for (int kk = 1; kk < a.split; ++kk) t = t + src[kk];
+            float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
+            dst[chunk] = t / (float)a.spp;
+        }
+        return;
+    }
+#endif
+    f3 tot = acc;
+    for (int kk = 1; kk < a.split; ++kk) {
+        const float vx = __shfl(acc.x, base + kk, 64);
+        const float vy = __shfl(acc.y, base + kk, 64);
+        const float vz = __shfl(acc.z, base + kk, 64);
+        tot.x = tot.x + vx;
+        tot.y = tot.y + vy;
+        tot.z = tot.z + vz;
+    }
+    if (valid && chunk == 0) {
+        const float fs = (float)a.spp;
+        float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
+        store_rgb(dst, tot.x / fs, tot.y / fs, tot.z / fs);
+    }
+}
+
 // the work of k_render_ps for one wave with at least one pixel; returns the lane's casts.
 // CT: the bounce casts from the scene's candidate table (the launcher checked it serves this
-// launch) -- the matrix-core path is not compiled in, so the kernel's registers allow more waves
+// launch) -- the matrix-core path is not compiled in, so the kernel's registers allow more waves.
+// With the pooled trip (ps_pooled) the wave stops after its bounce loop: *n_deferred is the
+// number of samples it left for ps_pool (listed at the front of its queue), and the kernel runs
+// ps_finish after the pool; otherwise the wave finishes here.
 template <int SAMPLER, int RULE, int MF, bool CT = false>
 __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceScene& ms, float* wl,
                                             const BlockDesc& blk, int q, int chunk, int lane, int lx, int ly, int px,
-                                            int py, bool valid) {
+                                            int py, bool valid, int* n_deferred) {
     extern __shared__ float s_ps[];
     const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
     const float4* __restrict__ shade = ms.shade;  // (RT_PS_SCENE_LDS: the workgroup's LDS copy)
@@ -729,7 +855,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // ---- phase P: primary rays of the lane's samples ----
     unsigned n_casts = 0;
 #if RT_PROF
-    uint64_t pt[6] = {0, 0, 0, 0, 0, 0};  // P, shade, filter masks, exact, post, loops
+    // P, shade, filter masks, exact, post, loops, light pre-test passes, loops with < 16 live lanes
+    uint64_t pt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t0 = __builtin_amdgcn_s_memtime();
 #endif
     const float nts = a.t_scale;
@@ -868,10 +995,29 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
         q_total += __builtin_popcountll(m);
     }
     int q_next = 0;       // wave-uniform: next queue entry
-    float* own = slots;   // slot of the live path's sample (any lane's)
+    int own_e = lane;     // queue entry (k << 6 | lane) of the live path's sample (any lane's)
     uint32_t lpix = pix;  // its pixel (RNG key)
     bool live = false;
+    // the slot of the live path's sample
+    auto own_slot = [&]() -> float* { return wslots + (own_e >> 6) * kPsFields * 64 + (own_e & 63); };
+    // Deferred samples (ps_pooled): a lane whose light pre-test passed has re-parked its sample
+    // (`deferred`, set in the loop below) and lists the slot's entry at the front of the wave's
+    // queue, for ps_pool.  The front is dead: every deferred sample was claimed before, so
+    // n_def <= q_next and no unclaimed entry is overwritten.
+    int n_def = 0;        // wave-uniform
+    bool deferred = false;
     auto claim = [&]() {  // wave-level: lanes without a path take the next queued samples
+        if constexpr (ps_pooled(MF, CT)) {
+            const uint64_t dm = __ballot(deferred);
+            if (dm != 0ull) {
+                if (deferred)
+                    queue[n_def + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32),
+                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u))] =
+                        (uint16_t)own_e;
+                n_def += __builtin_popcountll(dm);
+                deferred = false;
+            }
+        }
         const uint64_t need = __ballot(!live);
         if (need == 0ull || q_next >= q_total) return;
         const int j = q_next + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
@@ -879,7 +1025,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
         if (!live && j < q_total) {
             const uint32_t e = queue[j];
             const int ol = (int)(e & 63u), kk = (int)(e >> 6);
-            own = wslots + kk * kPsFields * 64 + ol;
+            own_e = (int)e;
+            const float* own = wslots + kk * kPsFields * 64 + ol;
             pos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
             hit_tri = code_at(kk, ol);
             depth = 0;
@@ -925,32 +1072,11 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // the next direction from the surface hit (pos, hit_tri) at bounce depth dep: cos theta
     // and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the path's Philox draw
     auto shade_hit = [&](int dep, float* cos_out, f3* o_out, f3* d_out) {
-        const float4 N = shade[hit_tri * kShadeF4 + 0];
-        const float4 T = shade[hit_tri * kShadeF4 + 1];
-        const float4 B = shade[hit_tri * kShadeF4 + 2];
-        float r1, r2;
 #if RT_PS_STEAL
-        draw2(lpix, (uint32_t)cur, 1u + (uint32_t)dep, a.seed_lo, a.seed_hi, &r1, &r2);
+        ps_shade_hit<SAMPLER>(a, shade, lpix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
 #else
-        draw2(pix, (uint32_t)cur, 1u + (uint32_t)dep, a.seed_lo, a.seed_hi, &r1, &r2);
+        ps_shade_hit<SAMPLER>(a, shade, pix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
 #endif
-        float cos_theta, sin_theta;
-        if (SAMPLER == 0) {
-            cos_theta = r1;
-            sin_theta = sqrtf(1.0f - r1 * r1);
-        } else {
-            cos_theta = sqrtf(r1);
-            sin_theta = sqrtf(1.0f - r1);
-        }
-        float sphi, cphi;
-        sincos_turn(r2, &sphi, &cphi);
-        const float sx = sin_theta * cphi, sz = sin_theta * sphi;
-        const f3 sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x,
-                            (sx * B.y + cos_theta * N.y) + sz * T.y,
-                            (sx * B.z + cos_theta * N.z) + sz * T.z);
-        *cos_out = cos_theta;
-        *o_out = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
-        *d_out = normalize(sd);
     };
     // Light pre-test (RT_PS_LIGHT_SPLIT).  The terminal cast of a path (the one at depth
     // max_bounces) adds light only if its closest hit is a light triangle; a surface or a miss
@@ -962,8 +1088,19 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // percent of rays) -> the path stays live and the next trip traces the same ray (same
     // Philox draw) in full.  Terminal casts thus stop taking slots of the matrix-core trips:
     // the image and the ray casts are k_render's bit for bit.
+    // With the pooled trip (ps_pooled, max_bounces <= 2) a pass does not stay in its lane: those
+    // retraces arrive after the wave's queue has drained, so most waves ran one more trip with a
+    // handful of live lanes at the cost of a full one.  The lane re-parks the sample in its
+    // slot (the hit point to shade, and ps_defer_code as its code) and is free for new work;
+    // ps_pool traces the workgroup's deferred samples together once its four waves are done.
+    // The terminal ray and its fold need (pos, hit_tri, f_tri0) and draws keyed by the slot alone,
+    // so nothing else is kept; at greater depths the path stays in its lane as before.
     const bool split = RT_PS_LIGHT_SPLIT && use_mf && a.max_bounces >= 1 &&
                        (a.scene.n_tri - n_surf) <= kPsSplitLights;
+    const bool pool = ps_pooled(MF, CT) && a.max_bounces <= 2;
+#if RT_PROF
+    unsigned n_pass = 0;  // the lane's light pre-test passes
+#endif
     // the pre-test of the terminal ray from (pos, hit_tri) at depth dep = max_bounces - 1
     auto light_pass = [&](int dep) -> bool {
         float c;
@@ -984,6 +1121,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
 #if RT_PROF
         const uint64_t ta = __builtin_amdgcn_s_memtime();
         pt[5] += 1;
+        pt[7] += __builtin_popcountll(__ballot(live)) < 16 ? 1 : 0;
 #endif
         int s_tri = 0;
         float s_cos = 0.0f;
@@ -1031,39 +1169,38 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
             const float4 e = shade[h.tri * kShadeF4 + 3];
             L = make3(e.x, e.y, e.z);
             // fold back through the surface bounces: depth 2 (this shading), then depth 1
-            if (depth >= 2) {
-                const float4 c = shade[s_tri * kShadeF4 + (SAMPLER == 0 ? 3 : 4)];
-                if (SAMPLER == 0) {
-                    L.x = div_rho((L.x * c.x) * s_cos);
-                    L.y = div_rho((L.y * c.y) * s_cos);
-                    L.z = div_rho((L.z * c.z) * s_cos);
-                } else {
-                    L = make3(L.x * c.x, L.y * c.y, L.z * c.z);
-                }
-            }
-            {
-                const float4 c = shade[f_tri0 * kShadeF4 + (SAMPLER == 0 ? 3 : 4)];
-                if (SAMPLER == 0) {
-                    L.x = div_rho((L.x * c.x) * f_cos0);
-                    L.y = div_rho((L.y * c.y) * f_cos0);
-                    L.z = div_rho((L.z * c.z) * f_cos0);
-                } else {
-                    L = make3(L.x * c.x, L.y * c.y, L.z * c.z);
-                }
-            }
+            if (depth >= 2) ps_fold<SAMPLER>(shade, L, s_tri, s_cos);
+            ps_fold<SAMPLER>(shade, L, f_tri0, f_cos0);
         } else if (depth == a.max_bounces) {
             // bounces == MAX_RAY_BOUNCES -> vec3(0)
         } else {
             terminal = false;  // shade the hit on the next trip
             pos = make3(o.x + h.t * (d.x * a.t_scale), o.y + h.t * (d.y * a.t_scale), o.z + h.t * (d.z * a.t_scale));
             hit_tri = h.tri;
-            if (split && depth + 1 == a.max_bounces && !light_pass(depth)) {
-                ++n_casts;  // the terminal cast: no light triangle can be its hit
-                terminal = true;
+            if (split && depth + 1 == a.max_bounces) {
+                if (!light_pass(depth)) {
+                    ++n_casts;  // the terminal cast: no light triangle can be its hit
+                    terminal = true;
+                } else {
+#if RT_PROF
+                    ++n_pass;
+#endif
+#if RT_PS_STEAL
+                    if (pool) {
+                        // the retrace waits for ps_pool: the hit to shade goes back into the slot
+                        // in place of a value (below), and the next claim() lists the slot
+                        L = pos;
+                        set_code_at(own_e >> 6, own_e & 63, ps_defer_code(hit_tri, f_tri0));
+                        deferred = true;
+                        terminal = true;
+                    }
+#endif
+                }
             }
         }
         if (terminal) {
 #if RT_PS_STEAL
+            float* own = own_slot();
             own[0 * 64] = L.x;
             own[1 * 64] = L.y;
             own[2 * 64] = L.z;
@@ -1076,38 +1213,116 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
 #endif
         }
     }
-#if RT_PS_STEAL
-    // the lane's own samples in order: ended ones hold their value in fields 0..2
-    for (int kk = 0; kk < pc; ++kk) {
-        const float* sl = slots + kk * kPsFields * 64;
-        acc.x = acc.x + sl[0 * 64];
-        acc.y = acc.y + sl[1 * 64];
-        acc.z = acc.z + sl[2 * 64];
-    }
-#endif
-
 #if RT_PROF
     pt[4] = __builtin_amdgcn_s_memtime() - t_s;  // the whole bounce phase
+    pt[6] = wave_sum(n_pass);
     if (a.prof != nullptr && lane == 0) {
-        for (int i = 0; i < 6; ++i) atomicAdd(a.prof + i, (unsigned long long)pt[i]);
+        for (int i = 0; i < 8; ++i) atomicAdd(a.prof + i, (unsigned long long)pt[i]);
     }
 #endif
-    // fold the chunk sums of a pixel in chunk order: ((P0 + P1) + P2) + ...
-    const int base = lane & ~(a.split - 1);
-    f3 tot = acc;
-    for (int kk = 1; kk < a.split; ++kk) {
-        const float vx = __shfl(acc.x, base + kk, 64);
-        const float vy = __shfl(acc.y, base + kk, 64);
-        const float vz = __shfl(acc.z, base + kk, 64);
-        tot.x = tot.x + vx;
-        tot.y = tot.y + vy;
-        tot.z = tot.z + vz;
+#if RT_PS_STEAL
+    *n_deferred = n_def;
+#else
+    *n_deferred = 0;
+#endif
+    // (with the pooled trip the kernel finishes the wave after ps_pool; acc is still 0 there)
+    if constexpr (!ps_pooled(MF, CT)) ps_finish(a, blk, chunk, lane, lx, ly, valid, acc);
+    return n_casts;
+}
+
+// The pooled trip of k_render_ps (ps_pooled): the terminal casts that the four waves of the
+// workgroup deferred (counts[w] entries at the front of wave w's queue), traced together.
+// Every wave of the workgroup calls this between the kernel's two pool barriers, also a wave
+// without pixels.  Wave w takes entries [64 w, 64 w + 64) of the concatenated list, and again in
+// steps of 256 while entries remain (64: RT_PS_POOL_SPAN).  A lane shades its entry's parked
+// hit at depth max_bounces - 1 with the owner's keys (pixel and sample from the owner's wave,
+// slot and lane, as claim() derives them), traces the ray in full and folds a light hit back as
+// the bounce loop does -- the same functions on the same operands, so the same bits -- then
+// writes the sample's value (0 for a surface or a miss) into the owner's slot.  Returns the
+// lane's casts.
+template <int SAMPLER, int RULE>
+__device__ __forceinline__ unsigned ps_pool(const RenderLaunch& a, const DeviceScene& ms, float* wl,
+                                            const BlockDesc& blk, int q0, int lane, const unsigned* counts) {
+    extern __shared__ float s_ps[];
+    const float4* __restrict__ shade = ms.shade;
+    const int pc = a.per_chunk;
+    const int c0 = (int)counts[0], c1 = (int)counts[1], c2 = (int)counts[2];
+    const int total = ((c0 + c1) + c2) + (int)counts[3];
+    const int dep = a.max_bounces - 1;
+    unsigned n_casts = 0;
+#if RT_PROF
+    uint64_t trips = 0, sparse = 0;
+    const uint64_t t0 = __builtin_amdgcn_s_memtime();
+#endif
+    constexpr int span = RT_PS_POOL_SPAN;
+    static_assert(span >= 1 && span <= 64, "a wave takes at most one entry per lane");
+    for (int base = (int)(threadIdx.x >> 6) * span; base < total; base += 4 * span) {  // wave-uniform bounds
+        const bool has = lane < span && base + lane < total;
+        int j = base + lane, ow = 0;  // owner wave and position in its list
+        if (j >= c0) { j -= c0; ow = 1; }
+        if (ow == 1 && j >= c1) { j -= c1; ow = 2; }
+        if (ow == 2 && j >= c2) { j -= c2; ow = 3; }
+        float* own = s_ps;
+        int hit_tri = 0, f_tri0 = 0, cur = 0;
+        uint32_t lpix = 0;
+        float s_cos = 0.0f;
+        f3 o = make3(0.0f, 0.0f, 0.0f), d = make3(0.0f, 0.0f, 1.0f);
+        if (has) {
+            float* const ws = s_ps + (size_t)ow * ps_wave_floats(pc);
+            const uint16_t* oqueue =
+                reinterpret_cast<const uint16_t*>(ws + pc * kPsFields * 64 + (RT_PS_CODE16 ? pc * 32 : 0));
+            const uint32_t e = oqueue[j];
+            const int ol = (int)(e & 63u), kk = (int)(e >> 6);
+            own = ws + kk * kPsFields * 64 + ol;
+#if RT_PS_CODE16
+            const int code = (int)reinterpret_cast<const int16_t*>(ws + pc * kPsFields * 64)[kk * 64 + ol];
+#else
+            const int code = __float_as_int(own[3 * 64]);
+#endif
+            hit_tri = code & 63;
+            f_tri0 = (code >> 6) & 63;
+            const int ot = ow * 64 + ol;  // the owner's threadIdx.x
+            const int oq = q0 + (ot >> a.split_log2);
+            lpix = (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
+            cur = (ot & (a.split - 1)) * pc + kk;
+            const f3 pos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
+            ps_shade_hit<SAMPLER>(a, shade, lpix, cur, dep, pos, hit_tri, &s_cos, &o, &d);
+        }
+#if RT_PROF
+        trips += 1;
+        sparse += __builtin_popcountll(__ballot(has)) < 16 ? 1 : 0;
+#endif
+        // wave-level: a lane without an entry casts a finite ray with no candidates
+        const Hit h = closest_hit_ctab<RULE, 1, kCtPairCap>(ms, ms.ctab[RULE], hit_tri, o, d, a.t_scale, has, wl);
+        if (has) {
+            ++n_casts;
+            f3 L = make3(0.0f, 0.0f, 0.0f);
+            if (h.tri >= a.scene.n_surf) {
+                const float4 e = shade[h.tri * kShadeF4 + 3];
+                L = make3(e.x, e.y, e.z);
+                if (dep >= 1) ps_fold<SAMPLER>(shade, L, hit_tri, s_cos);
+                // cos theta of the path's first bounce: the draw its shading at depth 0 used
+                float f_cos0 = s_cos;
+                if (SAMPLER == 0 && dep >= 1) {
+                    float r1, r2;
+                    draw2(lpix, (uint32_t)cur, 1u, a.seed_lo, a.seed_hi, &r1, &r2);
+                    f_cos0 = r1;
+                }
+                ps_fold<SAMPLER>(shade, L, f_tri0, f_cos0);
+            }
+            own[0 * 64] = L.x;
+            own[1 * 64] = L.y;
+            own[2 * 64] = L.z;
+        }
     }
-    if (valid && chunk == 0) {
-        const float fs = (float)a.spp;
-        float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
-        store_rgb(dst, tot.x / fs, tot.y / fs, tot.z / fs);
+#if RT_PROF
+    if (a.prof != nullptr && lane == 0) {
+        atomicAdd(a.prof + 4, (unsigned long long)(__builtin_amdgcn_s_memtime() - t0));
+        atomicAdd(a.prof + 5, (unsigned long long)trips);
+        atomicAdd(a.prof + 7, (unsigned long long)sparse);
+        if (threadIdx.x == 0) atomicMax(a.prof + 8, (unsigned long long)total);
     }
+#endif
     return n_casts;
 }
 
@@ -1203,8 +1418,23 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
 #endif
         if (RT_PS_SCENE_LDS || (RT_MF_LDS && !CT) || ((RT_PS_CT_TRI_LDS || RT_PS_CT_DICT_LDS) && CT)) __syncthreads();
     }
-    const unsigned n_casts =
-        (vmask == 0ull) ? 0u : ps_body<SAMPLER, RULE, MF, CT>(a, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
+    int n_def = 0;  // the wave's samples left for the pooled trip
+    unsigned n_casts = 0;
+    if (vmask != 0ull)
+        n_casts = ps_body<SAMPLER, RULE, MF, CT>(a, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid, &n_def);
+    if constexpr (ps_pooled(MF, CT)) {
+        // The pooled trip.  Its two barriers stand here, at the kernel's top level: outside every
+        // loop and under no condition but the template's constant, so all four waves reach both
+        // -- a wave without pixels too (it skipped ps_body above, publishes 0 and serves the
+        // pool like the others), and also a launch that defers nothing (max_bounces > 2).
+        // wg_casts carries the waves' deferred counts first; the second barrier frees it for
+        // the casts below and makes the pool's values visible to the slots' owners.
+        if (lane == 0) wg_casts[threadIdx.x >> 6] = (unsigned)n_def;
+        __syncthreads();
+        n_casts += ps_pool<SAMPLER, RULE>(a, ms, wl, blk, q - ((int)threadIdx.x >> lg), lane, wg_casts);
+        __syncthreads();
+        if (vmask != 0ull) ps_finish(a, blk, chunk, lane, lx, ly, valid, make3(0.0f, 0.0f, 0.0f));
+    }
     if (a.casts != nullptr) {
         const unsigned total = wave_sum(n_casts);
         if (lane == 0) wg_casts[threadIdx.x >> 6] = total;
