@@ -492,6 +492,38 @@ int rt_render_sarsa_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* s
 int rt_sarsa_td_device(rt_sarsa* sarsa, void** d_sum, void** d_count, int64_t* n_entries);
 int rt_sarsa_apply(rt_sarsa* sarsa, void* stream);
 
+/* Radiance-map views: the reference GPU engine's PATH_TRACING_METHOD 2 (GPU/main.cu:414-495,
+ * GPU/path_tracing/voronoi_trace.cu, RadianceMap::set_voronoi_colours / get_voronoi_colour,
+ * radiance_map.cu:205-225): every camera hit drawn in the colour of its nearest radiance volume.
+ *
+ * rt_sarsa_voronoi_palette: set_voronoi_colour's random colours (host only).  Volume v gets
+ *   u(w0), u(w1), u(w2), u = (x >> 8) 2^-24, of the Philox4x32-10 block with key (seed lo, seed hi)
+ *   and counter (v, 0, 0, 0x566F726F): word 3 is 0 in every render draw, so the stream is apart
+ *   from them (the reference draws three rand() / RAND_MAX per volume).
+ * rt_sarsa_set_view_colours: the map's per-volume colour table (rgb: n_volumes x 3, host; NULL =
+ *   the palette of the map's own seed, which a map that never had it called draws with).
+ * rt_render_volume_view: per sample s in [first_sample, first_sample + spp) of every pixel, the
+ *   camera ray rt_render_sarsa casts for sample index s (jitter: event 0 of counter
+ *   (y W + x, s, 0, 0)), its closest hit under params->hit_rule and t_scale, the hit point
+ *   o + t (d t_scale), its nearest volume by the map's current search mode, and that volume's
+ *   colour; (1, 1, 1) for a light or a miss (voronoi_trace.cu:31-37).  The pixel is the sum of
+ *   its spp_split chunk sums in order, divided by spp.  max_bounces, sampler and env_light are
+ *   ignored.  out_rgb: W x H x 3.  out_tri, out_vol, out_pos (W x H [x 3], each may be NULL)
+ *   describe sample first_sample: the triangle (-1 miss, >= n_surf a light), the volume (-1
+ *   unless a surface was hit) and the hit point (zeros unless a surface was hit).  The map is
+ *   read only, in every TD mode (only rt_sarsa_search_stats' kd_fallbacks may grow).
+ * rt_render_volume_view_tiles_device: the same view over a tile list into device memory,
+ *   stream-ordered; tiles and output layout as rt_render_sarsa_tiles_device. */
+int rt_sarsa_voronoi_palette(uint64_t seed, int32_t n_volumes, float* rgb /* n_volumes x 3 */);
+int rt_sarsa_set_view_colours(rt_sarsa* sarsa, const float* rgb);
+int rt_render_volume_view(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa, const rt_camera* cam,
+                          const rt_params* params, uint32_t first_sample, float* out_rgb, int32_t* out_tri,
+                          int32_t* out_vol, float* out_pos);
+int rt_render_volume_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa,
+                                       const rt_camera* cam, const rt_params* params, uint32_t first_sample,
+                                       const int32_t* tiles, int n_tiles, int tile_size, float* d_out,
+                                       void* stream);
+
 /* Device self-tests of numeric building blocks (no reference counterpart): every
  * bit-exact claim against oracle/ rests on them.  result[0] = mismatches, result[1] = the
  * lowest mismatching input bits (0xffffffff: none).
@@ -552,7 +584,9 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 #define RT_KT_DQN_MLP 4       /* k_dqn_mlp: the Q-network forward (config 4) */
 #define RT_KT_DQN_BOUNCE 5    /* k_dqn_bounce: Q.cos sampling + trace */
 #define RT_KT_DQN_CAMERA 6    /* k_dqn_camera */
-#define RT_KT_COUNT 7
+#define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view) */
+#define RT_KT_SARSA_NEAREST 8 /* k_sarsa_nearest: rt_sarsa_nearest's queries (without its copies) */
+#define RT_KT_COUNT 9
 int rt_ktime_enable(int on);
 int rt_ktime_read(int kernel, double* total_ms, int64_t* launches);
 const char* rt_ktime_name(int kernel);

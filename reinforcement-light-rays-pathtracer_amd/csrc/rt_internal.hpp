@@ -22,7 +22,9 @@ enum KtimeKernel {
     KT_DQN_MLP = 4,
     KT_DQN_BOUNCE = 5,
     KT_DQN_CAMERA = 6,
-    KT_COUNT = 7
+    KT_SARSA_VIEW = 7,  // k_sarsa_view (the radiance-map view)
+    KT_SARSA_NEAREST = 8,  // k_sarsa_nearest (rt_sarsa_nearest's queries)
+    KT_COUNT = 9
 };
 struct KernelTimer {
     int kernel = -1;  // -1: not timing
@@ -456,6 +458,10 @@ bool sarsa_ctab_compiled();  // rt_sarsa.hip was built with RT_SARSA_CTAB=1 (the
 hipError_t launch_sarsa_rebuild(const SarsaMap& m, hipStream_t stream);  // CDF + argmax from Q
 hipError_t launch_sarsa_nearest(const SarsaMap& m, const float* pos, const float* nrm, int n, int32_t* out,
                                 hipStream_t stream);
+// the radiance-map view (k_sarsa_view): r.sample_base = the first sample index, colours [n_vol] rgb (w unused);
+// out_tri / out_vol / out_pos: optional per-pixel AOVs of that first sample, in r.out's pixel layout
+hipError_t launch_sarsa_view(const RenderLaunch& r, const SarsaMap& m, const float4* colours, int32_t* out_tri,
+                             int32_t* out_vol, float* out_pos, hipStream_t stream);
 
 hipError_t launch_intersect(const DeviceScene& s, const float* orig, const float* dir, int n,
                             float t_scale, int hit_rule, int use_filter, float* out_t,

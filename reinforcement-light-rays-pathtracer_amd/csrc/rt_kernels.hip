@@ -155,50 +155,6 @@ __global__ __launch_bounds__(256) void k_intersect_bvh(const DeviceScene s, cons
 // (closest_hit_mf, wave-level: lanes without a live sample take part with no
 // candidates), as the bounce casts of k_render_ps; the launcher picks it when the camera
 // lies inside the image's origin bound (else every camera ray would keep every triangle).
-// the bits of 64-triangle group g that are triangles of an n-triangle scene
-__device__ __forceinline__ uint64_t tri_mask(int n, int g) {
-    const int k = n - 64 * g;
-    return k >= 64 ? ~0ull : (k <= 0 ? 0ull : ((1ull << k) - 1ull));
-}
-
-// The candidate triangles of the wave's camera rays: bit i of cm[i / 64] = triangle i may
-// be the hit of a camera ray through one of the wave's pixels (the pixel rectangle's cull,
-// rect_cull in rt_cull.hpp; wave-uniform).  k_render_ps phase P, k_render<MF> camera rays.
-template <int RULE>
-__device__ __forceinline__ void wave_candidates(const RenderLaunch& a, bool valid, int px, int py, int lane,
-                                                uint64_t* cm) {
-    int x0 = valid ? px : 0x7fffffff, x1 = valid ? px : -1;
-    int y0 = valid ? py : 0x7fffffff, y1 = valid ? py : -1;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        x0 = min(x0, __shfl_xor(x0, off, 64));
-        x1 = max(x1, __shfl_xor(x1, off, 64));
-        y0 = min(y0, __shfl_xor(y0, off, 64));
-        y1 = max(y1, __shfl_xor(y1, off, 64));
-    }
-    const CamRect c = make_cam_rect(a.cam_x, a.cam_y, a.cam_z, a.cos_y, a.sin_y, a.width, a.height, a.t_scale,
-                                    __builtin_amdgcn_readfirstlane(x0), __builtin_amdgcn_readfirstlane(x1),
-                                    __builtin_amdgcn_readfirstlane(y0), __builtin_amdgcn_readfirstlane(y1));
-    const int n_tri = a.scene.n_tri;
-#pragma unroll
-    for (int g = 0; g < kRenderCullWords; ++g) {
-        if (g * 64 >= n_tri) {  // (wave-uniform) no triangle in this word
-            cm[g] = 0ull;
-            continue;
-        }
-        const int i = g * 64 + lane;
-        const bool in_range = i < n_tri;
-#ifdef RT_TIMING_NO_CULL
-        const bool keep = in_range;
-#else
-        // every lane tests a real record (triangle 0 past the end), the range masks after
-        const bool cull = rect_cull<RULE>(a.scene.filt + (size_t)(in_range ? i : 0) * kFiltF4, c);
-        const bool keep = in_range && !cull;
-#endif
-        cm[g] = __ballot(keep) & tri_mask(n_tri, g);
-    }
-}
-
 template <int PRESET, int SAMPLER, int RULE, bool STEAL, bool BVH, int MF = 0>
 #ifndef RT_MIN_WAVES
 #define RT_MIN_WAVES 1

@@ -1108,11 +1108,156 @@ __global__ __launch_bounds__(256) void k_sarsa_nearest(const SarsaMap m, const f
     if (in) out[i] = v;
 }
 
+// closest_hit's answer from the wave's camera-ray candidates (wave_candidates: the triangles
+// the cull of the wave's pixel rectangle keeps; cm is wave-uniform): the exact test on the
+// kept triangles in index order, their records by scalar loads.  No wave-level operation:
+// lanes without a ray skip it.
+template <int RULE>
+__device__ __forceinline__ Hit view_hit_culled(const DeviceScene& sc, const uint64_t* cm, f3 o, f3 d, float t_scale) {
+    cfloat4* __restrict__ tri = as_const(sc.isect);
+    const float nDx = -(d.x * t_scale);
+    const float nDy = -(d.y * t_scale);
+    const float nDz = -(d.z * t_scale);
+    Hit h;
+    h.t = (RULE == 0) ? FLT_MAX : 999999.0f;
+    h.tri = -1;
+#pragma unroll
+    for (int g = 0; g < kRenderCullWords; ++g) {
+        uint64_t w = cm[g];
+        while (w != 0ull) {
+            const int i = 64 * g + __builtin_ctzll(w);
+            w &= w - 1ull;
+            exact_one_c<RULE>(tri, i, o, nDx, nDy, nDz, h);
+        }
+    }
+    return h;
+}
+
+// The radiance-map view (the reference's PATH_TRACING_METHOD 2: GPU/path_tracing/
+// voronoi_trace.cu:6-41, RadianceMap::get_voronoi_colour, radiance_map.cu:218-225): per
+// sample the camera ray of k_sarsa_render (sample index a.sample_base + s), its closest hit,
+// the nearest volume of a surface hit as the render searches it, and that volume's entry of
+// the colour table; (1, 1, 1) for a light or a miss.  One lane per (pixel, chunk) in
+// k_sarsa_render's layout -- a wave covers 16 x 4 pixels at split 1 -- and its chunk fold.
+// Every lane of a wave that has a pixel runs all per_chunk trips: a lane outside the image
+// or the tile casts nothing and searches nothing, but stays for the cull's ballots, the
+// shared k-d walks (sarsa_resolve_walks) and the fold's shuffles.  Reads the map only
+// (grid_fallbacks counts its undecided queries as in the render).
+// cull: the camera rays take the cull of the wave's pixel rectangle (launch_sarsa_view).
+// out_tri / out_vol / out_pos (each may be null): triangle (-1: miss), volume (-1: no
+// surface) and hit point (zeros: no surface) of sample a.sample_base, by output pixel.
+template <int RULE>
+__global__ __launch_bounds__(256) void k_sarsa_view(const RenderLaunch a, const SarsaMap m,
+                                                    const float4* __restrict__ colours, int cull,
+                                                    int32_t* __restrict__ out_tri, int32_t* __restrict__ out_vol,
+                                                    float* __restrict__ out_pos) {
+    __shared__ int kd_stack[kKdStack * 256];
+    const int lg = a.split_log2;
+    const BlockDesc blk = a.blocks[blockIdx.x >> lg];
+    const int part = blockIdx.x & (a.split - 1);
+    const int q = (part << (8 - lg)) + ((int)threadIdx.x >> lg);
+    const int chunk = threadIdx.x & (a.split - 1);
+    const int lane = threadIdx.x & 63;
+    const int lx = q & 15, ly = q >> 4;
+    const int px = blk.px0 + lx, py = blk.py0 + ly;
+    const bool valid = (px < a.clip_x1) && (py < a.clip_y1);
+    if (__ballot(valid) == 0ull) return;  // (whole waves outside the image)
+    const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
+    const float4* __restrict__ shade = a.scene.shade;
+    const int n_surf = a.scene.n_surf;
+    int* const st = kd_stack_of(kd_stack);
+    int* const blk_ws = kd_stack + ((int)threadIdx.x >> 6) * (kKdStack * 64);
+    const f3 o = make3(a.cam_x, a.cam_y, a.cam_z);
+    uint64_t cm[kRenderCullWords] = {0ull, 0ull, 0ull, 0ull};
+    if (cull) wave_candidates<RULE>(a, valid, px, py, lane, cm);
+    f3 acc = make3(0.f, 0.f, 0.f);
+    for (int k = 0; k < a.per_chunk; ++k) {
+        const int s = chunk * a.per_chunk + k;
+        Hit h;
+        h.t = 0.0f;
+        h.tri = -1;
+        f3 d = make3(0.f, 0.f, 1.f);
+        if (valid) {
+            float r1, r2;
+            draw2(pix, a.sample_base + (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
+            camera_ray<1>(a, px, py, r1, r2, &d);
+            h = cull ? view_hit_culled<RULE>(a.scene, cm, o, d, a.t_scale)
+                     : closest_hit<RULE>(a.scene.isect, a.scene.n_tri, o, d, a.t_scale);
+        }
+        const bool is_surf = valid && (h.tri >= 0) && (h.tri < n_surf);
+        f3 pos = o;
+        f3 nrm = make3(0.f, 0.f, 0.f);
+        if (is_surf) {
+            const float Dx = d.x * a.t_scale, Dy = d.y * a.t_scale, Dz = d.z * a.t_scale;
+            pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
+            const float4 N4 = shade[h.tri * kShadeF4 + 0];
+            nrm = make3(N4.x, N4.y, N4.z);
+        }
+        int rv = -1;
+        if (is_surf) rv = m.use_grid ? sarsa_nearest_grid_tri(m, h.tri, pos, nrm) : kNeedWalk;
+        if (m.use_grid)  // the whole wave, with or without a query
+            sarsa_resolve_walks(m, pos, nrm, &rv, blk_ws, st, lane);
+        else if (rv == kNeedWalk)
+            rv = sarsa_nearest(m, pos, nrm, st);
+        float4 c = make_float4(1.f, 1.f, 1.f, 0.f);
+        if (rv >= 0) c = colours[rv];
+        acc.x = acc.x + c.x;
+        acc.y = acc.y + c.y;
+        acc.z = acc.z + c.z;
+        if (k == 0 && chunk == 0 && valid) {
+            const size_t op = (size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx);
+            if (out_tri != nullptr) out_tri[op] = h.tri;
+            if (out_vol != nullptr) out_vol[op] = rv;
+            if (out_pos != nullptr) {
+                out_pos[3 * op + 0] = is_surf ? pos.x : 0.0f;
+                out_pos[3 * op + 1] = is_surf ? pos.y : 0.0f;
+                out_pos[3 * op + 2] = is_surf ? pos.z : 0.0f;
+            }
+        }
+    }
+    const int base = lane & ~(a.split - 1);
+    f3 tot = acc;
+    for (int k = 1; k < a.split; ++k) {
+        const float vx = __shfl(acc.x, base + k, 64);
+        const float vy = __shfl(acc.y, base + k, 64);
+        const float vz = __shfl(acc.z, base + k, 64);
+        tot.x = tot.x + vx;
+        tot.y = tot.y + vy;
+        tot.z = tot.z + vz;
+    }
+    if (valid && chunk == 0) {
+        const float fs = (float)a.spp;
+        float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
+        store_rgb(dst, tot.x / fs, tot.y / fs, tot.z / fs);
+    }
+}
+
 }  // namespace
+
+// the camera rays take the rectangle cull where k_render_ps takes it (filter records valid
+// for this camera and t_scale, at most 256 triangles) and the GPU preset's ray is the cull's
+// camera model: pitch 0 (camera_ray's second rotation is then the identity, exactly)
+hipError_t launch_sarsa_view(const RenderLaunch& a, const SarsaMap& m, const float4* colours, int32_t* out_tri,
+                             int32_t* out_vol, float* out_pos, hipStream_t stream) {
+    if (a.n_blocks <= 0) return hipSuccess;
+    if (colours == nullptr || a.out == nullptr) return hipErrorInvalidValue;
+    if (a.split < 1 || a.split > 64 || (1 << a.split_log2) != a.split || a.per_chunk * a.split != a.spp)
+        return hipErrorInvalidValue;
+    const int cull = (a.use_filter && a.scene.filt != nullptr && a.scene.n_tri <= 64 * kRenderCullWords &&
+                      a.cos_x == 1.0f && a.sin_x == 0.0f) ? 1 : 0;
+    const dim3 grid((unsigned)(a.n_blocks * a.split));
+    KernelTimer kt(KT_SARSA_VIEW, stream);
+    if (a.hit_rule == 0)
+        hipLaunchKernelGGL((k_sarsa_view<0>), grid, dim3(256), 0, stream, a, m, colours, cull, out_tri, out_vol, out_pos);
+    else
+        hipLaunchKernelGGL((k_sarsa_view<1>), grid, dim3(256), 0, stream, a, m, colours, cull, out_tri, out_vol, out_pos);
+    return hipGetLastError();
+}
 
 hipError_t launch_sarsa_nearest(const SarsaMap& m, const float* pos, const float* nrm, int n, int32_t* out,
                                 hipStream_t stream) {
     if (n <= 0) return hipSuccess;
+    KernelTimer kt(KT_SARSA_NEAREST, stream);
     hipLaunchKernelGGL(k_sarsa_nearest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m, pos, nrm, n, out);
     return hipGetLastError();
 }

@@ -368,6 +368,8 @@ struct rt_sarsa {
     // the camera rays' rectangle masks of its table route (four 16x4 rectangles per block)
     unsigned long long* d_cull = nullptr;
     size_t cull_cap = 0;
+    // the views' per-volume colour table, rgb in a float4 (rt_sarsa_set_view_colours; in allocs)
+    float4* d_view = nullptr;
     ~rt_sarsa() {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
@@ -397,10 +399,11 @@ float initial_irradiance(const float* cc, const float* q, float lum) {
     return irr;
 }
 
-int check_sarsa_params(const rt_params* p) {
+// view: rt_render_volume_view's parameters (it casts camera rays only: max_bounces is ignored)
+int check_sarsa_params(const rt_params* p, bool view = false) {
     if (!p) return err(RT_E_INVALID, "params is NULL");
     if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return err(RT_E_INVALID, "bad image size / spp");
-    if (p->max_bounces < 1) return err(RT_E_INVALID, "max_bounces must be >= 1");
+    if (!view && p->max_bounces < 1) return err(RT_E_INVALID, "max_bounces must be >= 1");
     if (p->preset != RT_PRESET_GPU)
         return err(RT_E_UNSUPPORTED, "the SARSA renderer implements the GPU-engine preset");
     if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU) return err(RT_E_INVALID, "bad hit_rule");
@@ -469,6 +472,51 @@ int render_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, cons
     }
     if (apply) RT_HIPE(rt::launch_sarsa_apply(sa->m, stream));
     sa->frames += 1;
+    return RT_OK;
+}
+
+constexpr uint32_t kPaletteWord = 0x566F726Fu;  // RNG counter word 3 of the view palette (0 in every render draw)
+
+// RadianceMap::set_voronoi_colours (radiance_map.cu:205-216): three uniforms per volume
+void voronoi_palette(uint64_t seed, int n, float* rgb, int stride) {
+    for (int v = 0; v < n; ++v) {
+        uint32_t r[4];
+        rt::philox4x32_10((uint32_t)v, 0u, 0u, kPaletteWord, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+        for (int c = 0; c < 3; ++c) rgb[(size_t)stride * v + c] = rt::u01(r[c]);
+    }
+}
+
+// the map's colour table on the device: rgb (n x 3, host) or, NULL, the palette of its seed.
+// The caller has set the device; no view may be in flight on the table (callers synchronise).
+int upload_view_colours(rt_sarsa* sa, const float* rgb) {
+    std::vector<float> tab((size_t)sa->n_vol * 4, 0.f);
+    if (rgb) {
+        for (int v = 0; v < sa->n_vol; ++v) memcpy(&tab[(size_t)4 * v], rgb + (size_t)3 * v, sizeof(float) * 3);
+    } else {
+        voronoi_palette(sa->seed, sa->n_vol, tab.data(), 4);
+    }
+    if (!sa->d_view) RT_HIPE(sa->alloc(&sa->d_view, (size_t)sa->n_vol));
+    RT_HIPE(hipMemcpy(sa->d_view, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// one view launch (rt_render_volume_view*): the map's frame counter and learning state stay
+int view_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const rt_params* p, uint32_t first_sample,
+               const rt::BlockDesc* d_blocks, int n_blocks, int out_pitch, float* d_out, int32_t* d_tri,
+               int32_t* d_vol, float* d_pos, hipStream_t stream) {
+    if (!sa->d_view) {  // never set: the palette of the map's seed
+        const int rc = upload_view_colours(sa, nullptr);
+        if (rc != RT_OK) return rc;
+    }
+    rt::RenderLaunch a = rt::render_launch(scene, cam, p);
+    a.blocks = d_blocks;
+    a.n_blocks = n_blocks;
+    a.clip_x1 = p->width;
+    a.clip_y1 = p->height;
+    a.out_pitch = out_pitch;
+    a.out = d_out;
+    a.sample_base = first_sample;
+    RT_HIPE(rt::launch_sarsa_view(a, sa->m, sa->d_view, d_tri, d_vol, d_pos, stream));
     return RT_OK;
 }
 
@@ -1048,6 +1096,83 @@ int rt_sarsa_apply(rt_sarsa* sa, void* stream) {
     RT_HIPE(hipSetDevice(sa->device));
     RT_HIPE(rt::launch_sarsa_apply(sa->m, (hipStream_t)stream));
     return RT_OK;
+}
+
+int rt_sarsa_voronoi_palette(uint64_t seed, int32_t n_volumes, float* rgb) {
+    if (n_volumes < 0) return err(RT_E_INVALID, "n_volumes < 0");
+    if (n_volumes > 0 && !rgb) return err(RT_E_INVALID, "rgb is NULL");
+    voronoi_palette(seed, n_volumes, rgb, 3);
+    return RT_OK;
+}
+
+int rt_sarsa_set_view_colours(rt_sarsa* sa, const float* rgb) {
+    if (!sa) return err(RT_E_INVALID, "NULL argument");
+    RT_HIPE(hipSetDevice(sa->device));
+    RT_HIPE(hipDeviceSynchronize());  // a view in flight still reads the table
+    return upload_view_colours(sa, rgb);
+}
+
+int rt_render_volume_view(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,
+                          const rt_params* params, uint32_t first_sample, float* out_rgb, int32_t* out_tri,
+                          int32_t* out_vol, float* out_pos) {
+    if (!ctx || !scene || !sa || !cam || !out_rgb) return err(RT_E_INVALID, "NULL argument");
+    int rc = check_sarsa_params(params, true);
+    if (rc != RT_OK) return rc;
+    if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
+    RT_HIPE(hipSetDevice(sa->device));
+    const int W = params->width, H = params->height;
+    std::vector<rt::BlockDesc> blocks;
+    for (int by = 0; by < H; by += 16)
+        for (int bx = 0; bx < W; bx += 16) blocks.push_back({bx, by, bx, by});
+    rt::BlockDesc* d_blocks = nullptr;
+    float *d_out = nullptr, *d_pos = nullptr;
+    int32_t *d_tri = nullptr, *d_vol = nullptr;
+    const size_t np = (size_t)W * H;
+    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
+    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
+    if (e == hipSuccess && out_tri) e = hipMalloc(&d_tri, sizeof(int32_t) * np);
+    if (e == hipSuccess && out_vol) e = hipMalloc(&d_vol, sizeof(int32_t) * np);
+    if (e == hipSuccess && out_pos) e = hipMalloc(&d_pos, sizeof(float) * 3 * np);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
+    rc = RT_OK;
+    if (e == hipSuccess)
+        rc = view_frame(sa, scene, cam, params, first_sample, d_blocks, (int)blocks.size(), W, d_out, d_tri, d_vol,
+                        d_pos, 0);
+    if (rc == RT_OK && e == hipSuccess) e = hipDeviceSynchronize();
+    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_tri)
+        e = hipMemcpy(out_tri, d_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_vol)
+        e = hipMemcpy(out_vol, d_vol, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_pos)
+        e = hipMemcpy(out_pos, d_pos, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
+    (void)hipFree(d_blocks);
+    (void)hipFree(d_out);
+    (void)hipFree(d_tri);
+    (void)hipFree(d_vol);
+    (void)hipFree(d_pos);
+    if (rc != RT_OK) return rc;
+    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_volume_view: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_render_volume_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,
+                                       const rt_params* params, uint32_t first_sample, const int32_t* tiles,
+                                       int n_tiles, int tile_size, float* d_out, void* stream) {
+    if (!ctx || !scene || !sa || !cam) return err(RT_E_INVALID, "NULL argument");
+    int rc = check_sarsa_params(params, true);
+    if (rc != RT_OK) return rc;
+    if (n_tiles < 0 || (n_tiles > 0 && (!tiles || !d_out))) return err(RT_E_INVALID, "bad tiles/out");
+    if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
+    RT_HIPE(hipSetDevice(sa->device));
+    if (n_tiles == 0) return RT_OK;
+    const rt::BlockDesc* d_blocks = nullptr;
+    int n_blocks = 0;
+    rc = rt::ctx_blocks(ctx, tiles, n_tiles, tile_size, params->width, params->height, &d_blocks, &n_blocks);
+    if (rc != RT_OK) return rc;
+    return view_frame(sa, scene, cam, params, first_sample, d_blocks, n_blocks, tile_size, d_out, nullptr, nullptr,
+                      nullptr, (hipStream_t)stream);
 }
 
 }  // extern "C"

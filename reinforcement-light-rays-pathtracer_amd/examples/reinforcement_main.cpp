@@ -8,6 +8,9 @@
 //   ./build/reinforcement_demo dqn <scene.obj> <kind> <model> [frames] [spp] [out.bmp]
 //   ./build/reinforcement_demo neuralq <scene.obj> <kind> <model> [frames] [spp] [out.bmp]
 //     (trains from <model>; writes nn_training_stats.txt and trained.model)
+//   ./build/reinforcement_demo voronoi <scene.obj> <kind> [frames] [out.bmp] [width height]
+//     (GPU/main.cu:414-495, PATH_TRACING_METHOD 2: the radiance volumes' Voronoi view, one
+//      sample per frame; the last frame is saved)
 //   (kind: 1 door_room, 2 archway, 3 complex_light_room; scene "cornell" = the Cornell box)
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +22,7 @@
 #include "../host/reinforcement_path_tracing.h"
 #include "../host/scene.h"
 #include "../host/sdl_screen.h"
+#include "../host/voronoi_trace.h"
 
 using namespace rtmi;
 
@@ -33,7 +37,7 @@ static vec4 camera_for(int kind) {  // GPU/main.cu:100-104
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s sarsa|dqn <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
+        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
         return 2;
     }
     const bool nq = strcmp(argv[1], "neuralq") == 0;
@@ -41,16 +45,23 @@ int main(int argc, char** argv) {
     const int kind = atoi(argv[3]);
     int a = 4;
     const char* model = dqn ? (argc > a ? argv[a++] : "") : "";
+    const bool voronoi = strcmp(argv[1], "voronoi") == 0;
     const int frames = argc > a ? atoi(argv[a++]) : 4;
-    const int spp = argc > a ? atoi(argv[a++]) : 32;
+    const int spp = (!voronoi && argc > a) ? atoi(argv[a++]) : 32;
     const char* out = argc > a ? argv[a++] : "render.bmp";
+    const int width = (voronoi && argc > a + 1) ? atoi(argv[a]) : 512;
+    const int height = (voronoi && argc > a + 1) ? atoi(argv[a + 1]) : 512;
+    if (width <= 0 || height <= 0) {
+        fprintf(stderr, "bad screen size %d x %d\n", width, height);
+        return 2;
+    }
     Scene scene;
     if (strcmp(argv[2], "cornell") == 0) scene.load_cornell_box_scene();
     else if (!scene.load_custom_scene_kind(argv[2], kind)) {
         fprintf(stderr, "cannot load %s\n", argv[2]);
         return 1;
     }
-    SDLScreen screen(512, 512, false);
+    SDLScreen screen(width, height, false);
     Camera camera(camera_for(kind));
     try {
         DeviceScene ds(scene);
@@ -61,6 +72,15 @@ int main(int argc, char** argv) {
                 printf("frame %d: %llu ray casts, epsilon %.3f\n", f, (unsigned long long)casts, pt.epsilon());
             }
             pt.save_model("trained.model");
+        } else if (voronoi) {
+            // GPU/main.cu:429-490: the radiance map, its Voronoi colours, then the render loop
+            RadianceMap map(ds);
+            printf("radiance volumes: %d (KD array %d)\n", map.radiance_volumes_count, map.radiance_array_size);
+            map.set_voronoi_colours();
+            for (int f = 0; f < frames; ++f) {
+                draw_voronoi_trace(screen, map, camera, scene, (uint32_t)f);
+                printf("frame %d: voronoi view\n", f);
+            }
         } else if (dqn) {
             PretrainedPathtracer pt(ds, model);
             for (int f = 0; f < frames; ++f) {

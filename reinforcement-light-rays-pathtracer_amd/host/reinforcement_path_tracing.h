@@ -101,6 +101,9 @@ class RadianceMap {
     // paths in flight of the in-frame rule (its races depend on it; the reference's GTX 1070 Ti
     // held about 4,864: the setting its training logs are matched at); 0: the whole device
     void set_in_frame_lanes(int lanes) { detail::check(rt_sarsa_set_inframe_lanes(map_, lanes)); }
+    // RadianceMap::set_voronoi_colours (radiance_map.cu:205-216): a random colour per volume for
+    // draw_voronoi_trace (voronoi_trace.h), from the map's seed
+    void set_voronoi_colours() { detail::check(rt_sarsa_set_view_colours(map_, nullptr)); }
     // GPU/main.cu:321-339 after a frame: the average path length as the reference computes it
     // (int(sum over pixels of int(path lengths / spp)) / pixels)) and the zero-contribution
     // paths; append_training_stats writes its "avg 0 zero" line.

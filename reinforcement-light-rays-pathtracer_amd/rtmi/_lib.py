@@ -39,7 +39,9 @@ RT_KT_SARSA_APPLY = 3
 RT_KT_DQN_MLP = 4
 RT_KT_DQN_BOUNCE = 5
 RT_KT_DQN_CAMERA = 6
-RT_KT_COUNT = 7
+RT_KT_SARSA_VIEW = 7
+RT_KT_SARSA_NEAREST = 8
+RT_KT_COUNT = 9
 
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -63,6 +65,8 @@ EXPORTS = (
     "rt_dqn_td_targets_device",
     "rt_scene_set_accel", "rt_scene_accel_info", "rt_scene_ctab_info", "rt_bvh_check",
     "rt_ktime_enable", "rt_ktime_read", "rt_ktime_name",
+    "rt_sarsa_voronoi_palette", "rt_sarsa_set_view_colours", "rt_render_volume_view",
+    "rt_render_volume_view_tiles_device",
 )
 
 
@@ -184,6 +188,12 @@ def _declare(lib):
                                              _IP, i, i, _P, _P, i, _P]),
         "rt_sarsa_td_device": (i, [_P, ctypes.POINTER(_P), ctypes.POINTER(_P), ctypes.POINTER(ctypes.c_int64)]),
         "rt_sarsa_apply": (i, [_P, _P]),
+        "rt_sarsa_voronoi_palette": (i, [ctypes.c_uint64, ctypes.c_int32, _FP]),
+        "rt_sarsa_set_view_colours": (i, [_P, _FP]),
+        "rt_render_volume_view": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                      ctypes.c_uint32, _FP, _IP, _IP, _FP]),
+        "rt_render_volume_view_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                                   ctypes.c_uint32, _IP, i, i, _P, _P]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),

@@ -11,6 +11,10 @@
   .set_sampling(SAMPLE_MAX)       sample_max_direction_from_radiance_distribution
   .set_td_mode(TD_INFRAME)        the reference's racy in-frame TD update (one GPU)
   .frame_stats() / .append_stats_line(path)   sarsa_training_stats.txt (GPU/main.cu:321-339)
+  .view(cam, params, first_sample, aov) / .view_tiles_device(...)   the Voronoi view (GPU/main.cu
+                                  method 2): each camera hit in its nearest volume's colour
+  .set_view_colours(rgb)          the view's per-volume colours; voronoi_palette(seed, n) the default,
+                                  irradiance_colours / visits_colours / max_q_colours from read()
 """
 from __future__ import annotations
 
@@ -168,6 +172,46 @@ class RadianceMap:
                                                  ctypes.c_void_p(out_ptr), ctypes.c_void_p(casts_ptr),
                                                  int(bool(apply)), ctypes.c_void_p(stream)))
 
+    def set_view_colours(self, rgb=None) -> None:
+        """The views' per-volume colour table, n_volumes x 3 (rt_sarsa_set_view_colours); None:
+        the random palette of the map's seed (RadianceMap::set_voronoi_colours), which is also
+        what a map that never had this called draws with."""
+        if rgb is None:
+            check(lib().rt_sarsa_set_view_colours(self._h, None))
+            return
+        t = np.ascontiguousarray(rgb, np.float32)
+        if t.shape != (self.n_volumes, 3):
+            raise ValueError(f"colour table must be ({self.n_volumes}, 3), got {t.shape}")
+        check(lib().rt_sarsa_set_view_colours(self._h, _fp(t)))
+
+    def view(self, cam, params, first_sample: int = 0, aov: bool = False):
+        """Every camera hit in the colour of its nearest volume (the reference's Voronoi view,
+        GPU/path_tracing/voronoi_trace.cu; rt_render_volume_view): samples first_sample ..
+        first_sample + spp - 1 of rt_render_sarsa's camera rays.  The map is left as it is.
+        Returns rgb (H, W, 3); with aov, (rgb, tri, vol, pos) where tri (-1 miss, >= n_surf
+        light), vol (-1 unless a surface was hit) and pos (H, W, 3) describe sample first_sample."""
+        h, w = params.height, params.width
+        out = np.zeros((h, w, 3), np.float32)
+        if not aov:
+            check(lib().rt_render_volume_view(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
+                                              ctypes.byref(params), first_sample, _fp(out), None, None, None))
+            return out
+        tri = np.zeros((h, w), np.int32)
+        vol = np.zeros((h, w), np.int32)
+        pos = np.zeros((h, w, 3), np.float32)
+        check(lib().rt_render_volume_view(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
+                                          ctypes.byref(params), first_sample, _fp(out), _ip(tri), _ip(vol), _fp(pos)))
+        return out, tri, vol, pos
+
+    def view_tiles_device(self, cam, params, tiles: np.ndarray, tile_size: int, out_ptr: int, stream: int,
+                          first_sample: int = 0) -> None:
+        """The view over a tile list into device memory, stream-ordered; tiles and output
+        layout as render_tiles_device (rt_render_volume_view_tiles_device)."""
+        t = np.ascontiguousarray(tiles, np.int32).reshape(-1, 2)
+        check(lib().rt_render_volume_view_tiles_device(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
+                                                       ctypes.byref(params), first_sample, _ip(t), t.shape[0],
+                                                       tile_size, ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream)))
+
     def td_device(self):
         """Device pointers of the frame's TD sums (int64, fixed point 2^-32) and counts (uint32)."""
         s, c, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(0)
@@ -187,6 +231,44 @@ class RadianceMap:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def voronoi_palette(seed: int, n: int) -> np.ndarray:
+    """The random per-volume colours of seed `seed`, (n, 3) in [0, 1) (rt_sarsa_voronoi_palette;
+    RadianceMap::set_voronoi_colours)."""
+    out = np.zeros((max(n, 0), 3), np.float32)
+    check(lib().rt_sarsa_voronoi_palette(seed, n, _fp(out)))  # (n < 0: refused there)
+    return out
+
+
+# ---- colour tables for RadianceMap.set_view_colours from RadianceMap.read() ----
+
+def irradiance_colours(irradiance: np.ndarray) -> np.ndarray:
+    """The irradiance estimate accumulators as grey, scaled to the largest one."""
+    a = np.maximum(np.asarray(irradiance, np.float32), 0)
+    top = float(a.max()) if a.size else 0.0
+    g = a / np.float32(top) if top > 0 else np.zeros_like(a)
+    return np.repeat(g[:, None], 3, axis=1).astype(np.float32)
+
+
+def visits_colours(visits: np.ndarray) -> np.ndarray:
+    """Each volume's visits summed over its sectors, as grey on a log scale."""
+    tot = np.asarray(visits, np.uint64).reshape(-1, SECTORS).sum(axis=1).astype(np.float64)
+    top = float(tot.max()) if tot.size else 0.0
+    g = np.log1p(tot) / np.log1p(top) if top > 0 else np.zeros_like(tot)
+    return np.repeat(g[:, None], 3, axis=1).astype(np.float32)
+
+
+def max_q_colours(q: np.ndarray) -> np.ndarray:
+    """The first sector of largest Q (the max-direction sampler's sector) as a colour: sector
+    12 x + y -> hue x / 12 at full saturation, value (y + 1) / 12."""
+    k = np.argmax(np.asarray(q, np.float32).reshape(-1, SECTORS), axis=1)  # the first maximum
+    hue = (k // 12).astype(np.float32) / np.float32(12)
+    val = ((k % 12) + 1).astype(np.float32) / np.float32(12)
+    h6 = hue * np.float32(6)
+    # HSV -> RGB at saturation 1: channel c = value * clip(|((h6 + shift_c) mod 6) - 3| - 1, 0, 1)
+    rgb = [np.clip(np.abs(np.mod(h6 + np.float32(s), 6) - 3) - 1, 0, 1) * val for s in (0, 4, 2)]
+    return np.stack(rgb, axis=1).astype(np.float32)
 
 
 def stats_line(path_floor_sum: int, zero_paths: int, pixels: int) -> str:
