@@ -672,6 +672,16 @@ __global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
 __host__ __device__ constexpr bool ps_pooled(int mf, bool ct) {
     return RT_PS_POOL && RT_PS_STEAL && RT_PS_LIGHT_SPLIT && ct && mf == 1;
 }
+#ifndef RT_PS_PIPE
+// With the pooled trip, the light pre-test of a lane's sample runs one trip later, between the
+// issue of the next sample's table lookup and its first use (0: on the spot, A/B builds)
+#define RT_PS_PIPE 1
+#endif
+#ifndef RT_PS_EARLY
+// the pipelined loop loads the claimed sample's patch frame (the table lookup's first link)
+// with its shading frame, ahead of the Philox block (0: where the lookup starts, A/B builds)
+#define RT_PS_EARLY 1
+#endif
 // a deferred sample's slot code: the surface to shade (the terminal ray's origin) and the
 // path's first surface -- the table route has at most 64 triangles, so 6 bits each
 __device__ __forceinline__ int ps_defer_code(int hit_tri, int f_tri0) { return (1 << 12) | (f_tri0 << 6) | hit_tri; }
@@ -679,13 +689,12 @@ __device__ __forceinline__ int ps_defer_code(int hit_tri, int f_tri0) { return (
 // the next direction from the surface hit (pos, hit_tri) at bounce depth dep of sample cur of
 // pixel lpix: cos theta and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the
 // path's Philox draw
+// (ps_shade_dir: with the surface's shading frame N, T, B in hand -- a caller that loads the
+// records ahead of time, the pipelined loop)
 template <int SAMPLER>
-__device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4* __restrict__ shade, uint32_t lpix,
-                                             int cur, int dep, const f3& pos, int hit_tri, float* cos_out, f3* o_out,
+__device__ __forceinline__ void ps_shade_dir(const RenderLaunch& a, const float4& N, const float4& T, const float4& B,
+                                             uint32_t lpix, int cur, int dep, const f3& pos, float* cos_out, f3* o_out,
                                              f3* d_out) {
-    const float4 N = shade[hit_tri * kShadeF4 + 0];
-    const float4 T = shade[hit_tri * kShadeF4 + 1];
-    const float4 B = shade[hit_tri * kShadeF4 + 2];
     float r1, r2;
     draw2(lpix, (uint32_t)cur, 1u + (uint32_t)dep, a.seed_lo, a.seed_hi, &r1, &r2);
     float cos_theta, sin_theta;
@@ -705,6 +714,18 @@ __device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4
     *cos_out = cos_theta;
     *o_out = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
     *d_out = normalize(sd);
+}
+// v.xyz stay in their registers from here on: whatever load produced them is waited for at this
+// point, and no later use waits again (an empty statement for the compiler's scheduling only)
+__device__ __forceinline__ void ps_pin(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); }
+template <int SAMPLER>
+__device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4* __restrict__ shade, uint32_t lpix,
+                                             int cur, int dep, const f3& pos, int hit_tri, float* cos_out, f3* o_out,
+                                             f3* d_out) {
+    const float4 N = shade[hit_tri * kShadeF4 + 0];
+    const float4 T = shade[hit_tri * kShadeF4 + 1];
+    const float4 B = shade[hit_tri * kShadeF4 + 2];
+    ps_shade_dir<SAMPLER>(a, N, T, B, lpix, cur, dep, pos, cos_out, o_out, d_out);
 }
 // folds the light L back through the bounce at surface tri whose direction had cos theta = c
 template <int SAMPLER>
@@ -962,17 +983,20 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // n_def <= q_next and no unclaimed entry is overwritten.
     int n_def = 0;        // wave-uniform
     bool deferred = false;
+    auto list_deferred = [&](bool def, int e) {  // wave-level: the lanes with def list their entry e
+        const uint64_t dm = __ballot(def);
+        if (dm != 0ull) {
+            if (def)
+                queue[n_def + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u))] =
+                    (uint16_t)e;
+            n_def += __builtin_popcountll(dm);
+        }
+    };
     auto claim = [&]() {  // wave-level: lanes without a path take the next queued samples
         if constexpr (ps_pooled(MF, CT)) {
-            const uint64_t dm = __ballot(deferred);
-            if (dm != 0ull) {
-                if (deferred)
-                    queue[n_def + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32),
-                                                                 __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u))] =
-                        (uint16_t)own_e;
-                n_def += __builtin_popcountll(dm);
-                deferred = false;
-            }
+            list_deferred(deferred, own_e);
+            deferred = false;
         }
         const uint64_t need = __ballot(!live);
         if (need == 0ull || q_next >= q_total) return;
@@ -1068,7 +1092,161 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
             pass |= exact_tv<RULE>(ms.isect, j, lo, nDx, nDy, nDz) != __builtin_inff();
         return pass;
     };
-    for (;;) {
+#if RT_PROF
+    uint64_t t_pre = 0;  // wave cycles inside the light pre-test
+#endif
+    bool piped = false;  // the pipelined loop has done the bounces: the loop after it does not run
+#if RT_PS_PIPE
+    // The pipelined loop (pooled trip with the pre-test on: every live lane ends its path in
+    // the trip that claimed it, so every trip starts with all lanes free and the paths at depth
+    // 0).  The cast's table lookup opens with two dependent global loads that nothing in the
+    // lane's own chain covers, and the pre-test that follows a surface hit shares no data with
+    // the lane's next sample.  So a sample whose cast hit a surface does not run its pre-test on
+    // the spot: the lane keeps it as pending (the hit point, and the slot's entry packed with
+    // the two triangles) and goes free.  Next trip: claim, shade the new sample, issue its lookup
+    // (closest_hit_ctab_begin), then run the pending sample's pre-test -- its keys re-derived
+    // from the entry as claim() derives them -- store its value or its deferral and list the
+    // deferrals (their samples were claimed a trip ago: n_def <= q_next holds), and only then
+    // use the lookup's words (closest_hit_ctab_finish).  Loads return in the order of their
+    // issue, so a wait inside the pre-test for its surface's shading frame would wait for the
+    // lookup's words as well: the frame is loaded where the sample becomes pending, ahead of the
+    // next trip's loads, and pinned in registers (ps_pin) at the top of that trip, on every
+    // path.  (Pinned later, after the new sample's shading on one path and where a lane has no
+    // new sample on the other, the compiler still waits inside the pre-test.)  Every sample runs
+    // the same float operations on the same operands as in the loop below, and the casts are
+    // counted at the same events: the image and the ray casts are unchanged.  When the queue has
+    // drained, the pre-tests still pending run after the loop.  Nothing but the pending sample
+    // and wave-uniform counters is carried from trip to trip.
+    if constexpr (ps_pooled(MF, CT)) piped = pool && split;
+    if constexpr (ps_pooled(MF, CT)) {
+        if (piped) {
+            const CtabDev& tab = ms.ctab[RULE];
+            bool pend = false;
+            f3 p_pos = make3(0.0f, 0.0f, 0.0f);
+            int p_pack = 0;  // the entry << 12 | f_tri0 << 6 | hit_tri
+            float4 pN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pT = pN, pB = pN;  // its surface's shading frame
+            // the pending samples' pre-tests and the listing of those that pass (wave-level)
+            auto pretest_pending = [&]() {
+#if RT_PROF
+                const uint64_t tp = __builtin_amdgcn_s_memtime();
+#endif
+                const int e = p_pack >> 12, ol = e & 63, kk = e >> 6;
+                bool pass = false;
+                if (pend) {
+                    const int oq = q - (lane >> a.split_log2) + (ol >> a.split_log2);
+                    const uint32_t ppix =
+                        (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
+                    const int pcur = (ol & (a.split - 1)) * pc + kk;
+                    float c;
+                    f3 lo, ld;
+                    ps_shade_dir<SAMPLER>(a, pN, pT, pB, ppix, pcur, a.max_bounces - 1, p_pos, &c, &lo, &ld);
+                    const float nDx = -(ld.x * a.t_scale), nDy = -(ld.y * a.t_scale), nDz = -(ld.z * a.t_scale);
+                    for (int j = n_surf; j < a.scene.n_tri; ++j)
+                        pass |= exact_tv<RULE>(ms.isect, j, lo, nDx, nDy, nDz) != __builtin_inff();
+                    f3 v = make3(0.0f, 0.0f, 0.0f);
+                    if (pass) {
+                        // the retrace waits for ps_pool: the hit to shade goes back into the slot
+                        v = p_pos;
+                        set_code_at(kk, ol, (1 << 12) | (p_pack & 4095));  // ps_defer_code(hit_tri, f_tri0)
+#if RT_PROF
+                        ++n_pass;
+#endif
+                    } else {
+                        ++n_casts;  // the terminal cast: no light triangle can be its hit
+                    }
+                    float* own = wslots + kk * kPsFields * 64 + ol;
+                    own[0 * 64] = v.x;
+                    own[1 * 64] = v.y;
+                    own[2 * 64] = v.z;
+                    pend = false;
+                }
+                list_deferred(pass, e);
+#if RT_PROF
+                t_pre += __builtin_amdgcn_s_memtime() - tp;
+#endif
+            };
+            while (q_next < q_total) {
+#if RT_PROF
+                const uint64_t ta = __builtin_amdgcn_s_memtime();
+                pt[5] += 1;
+                pt[7] += q_total - q_next < 16 ? 1 : 0;
+#endif
+                ps_pin(pN);
+                ps_pin(pT);
+                ps_pin(pB);
+                // claim(): every lane is free, lane l takes entry q_next + l
+                const int qj = q_next + lane;
+                const bool has = qj < q_total;
+                q_next = min(q_total, q_next + 64);
+                int s_tri = 0, s_e = 0;
+                float s_cos = 0.0f;
+                f3 so = cam, sd = make3(0.0f, 0.0f, 1.0f);  // (a lane without a sample: a finite ray, no candidates)
+                CtabLook<1> look = ctab_no_look<1>();
+                if (has) {
+                    s_e = (int)queue[qj];
+                    const int ol = s_e & 63, kk = s_e >> 6;
+                    const float* own = wslots + kk * kPsFields * 64 + ol;
+                    const f3 spos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
+                    s_tri = code_at(kk, ol);
+                    // the new sample's loads: its shading frame (and, RT_PS_EARLY, its patch frame, the
+                    // lookup's first link) ahead of the Philox block
+                    const float4 N = shade[s_tri * kShadeF4 + 0];
+                    const float4 T = shade[s_tri * kShadeF4 + 1];
+                    const float4 B = shade[s_tri * kShadeF4 + 2];
+#if RT_PS_EARLY
+                    const CtabFrame R = ctab_frame(tab, s_tri);
+#endif
+                    const int oq = q - (lane >> a.split_log2) + (ol >> a.split_log2);  // the owner's pixel
+                    const uint32_t spix =
+                        (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
+                    const int scur = (ol & (a.split - 1)) * pc + kk;
+                    ps_shade_dir<SAMPLER>(a, N, T, B, spix, scur, 0, spos, &s_cos, &so, &sd);
+#if RT_PS_EARLY
+                    look = closest_hit_ctab_begin<1>(tab, R, so, sd, true);
+#else
+                    look = closest_hit_ctab_begin<1>(ms, tab, s_tri, so, sd, true);
+#endif
+                }
+#if RT_PROF
+                const uint64_t tb = __builtin_amdgcn_s_memtime();
+                const uint64_t tp0 = t_pre;
+#endif
+                if (__ballot(pend) != 0ull) pretest_pending();
+                const Hit h = closest_hit_ctab_finish<RULE, 1, kCtPairCap>(ms, tab, s_tri, look, so, sd, a.t_scale, has,
+                                                                           wl);
+#if RT_PROF
+                pt[1] += tb - ta;  // (with the claim and the lookup's begin half)
+                pt[3] += (__builtin_amdgcn_s_memtime() - tb) - (t_pre - tp0);
+#endif
+                if (!has) continue;
+                ++n_casts;
+                if (h.tri >= 0 && h.tri < n_surf && 1 < a.max_bounces) {
+                    // a surface with one bounce left: pending
+                    p_pos = make3(so.x + h.t * (sd.x * a.t_scale), so.y + h.t * (sd.y * a.t_scale),
+                                  so.z + h.t * (sd.z * a.t_scale));
+                    p_pack = (s_e << 12) | (s_tri << 6) | h.tri;
+                    pN = shade[h.tri * kShadeF4 + 0];
+                    pT = shade[h.tri * kShadeF4 + 1];
+                    pB = shade[h.tri * kShadeF4 + 2];
+                    pend = true;
+                    continue;
+                }
+                f3 L = make3(0.0f, 0.0f, 0.0f);  // a miss, or a surface at max_bounces
+                if (h.tri >= n_surf) {
+                    const float4 e = shade[h.tri * kShadeF4 + 3];
+                    L = make3(e.x, e.y, e.z);
+                    ps_fold<SAMPLER>(shade, L, s_tri, s_cos);  // (depth 1: the path's first bounce)
+                }
+                float* own = wslots + (s_e >> 6) * kPsFields * 64 + (s_e & 63);
+                own[0 * 64] = L.x;
+                own[1 * 64] = L.y;
+                own[2 * 64] = L.z;
+            }
+            if (__ballot(pend) != 0ull) pretest_pending();
+        }
+    }
+#endif
+    for (; !piped;) {
 #if RT_PS_STEAL
         claim();
 #endif
@@ -1134,7 +1312,14 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
             pos = make3(o.x + h.t * (d.x * a.t_scale), o.y + h.t * (d.y * a.t_scale), o.z + h.t * (d.z * a.t_scale));
             hit_tri = h.tri;
             if (split && depth + 1 == a.max_bounces) {
+#if RT_PROF
+                const uint64_t tp = __builtin_amdgcn_s_memtime();
+                const bool lp = light_pass(depth);
+                t_pre += __builtin_amdgcn_s_memtime() - tp;
+                if (!lp) {
+#else
                 if (!light_pass(depth)) {
+#endif
                     ++n_casts;  // the terminal cast: no light triangle can be its hit
                     terminal = true;
                 } else {
@@ -1174,6 +1359,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     pt[6] = wave_sum(n_pass);
     if (a.prof != nullptr && lane == 0) {
         for (int i = 0; i < 8; ++i) atomicAdd(a.prof + i, (unsigned long long)pt[i]);
+        atomicAdd(a.prof + 9, (unsigned long long)t_pre);
     }
 #endif
 #if RT_PS_STEAL

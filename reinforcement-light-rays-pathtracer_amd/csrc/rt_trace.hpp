@@ -840,15 +840,40 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
 // every triangle where the table does not apply (origin off the surface's plane or grid, a
 // direction off its hemisphere, non-unit or non-finite).  F: NW >= T.words mask words (the
 // rest 0).  rt_ctab.cpp ctab_lookup is the same lookup on the host.
+//
+// The lookup in two halves, for a caller with independent work to put between them
+// (k_render_ps's pipelined bounce loop): ctab_begin runs the address arithmetic and issues the
+// loads of the entry's mask words -- the end of a chain of two dependent global loads (the
+// surface's patch frame, then the entry) -- and ctab_finish, the first use of those words,
+// folds them into F.  ctab_candidates is the two back to back.
 template <int NW>
-__device__ __forceinline__ void ctab_candidates(const CtabDev& T, int n_tri, int n_surf, int surf, f3 o, f3 d,
-                                                uint64_t (&F)[NW]) {
-    const int W = T.words;
+struct CtabLook {
+    uint64_t m[NW];  // the entry's mask words as loaded (0 where the table does not apply)
+    int gi;          // the direction's grazing bin
+    bool in, cp;     // the table applies; the coplanar triangles join
+};
+struct CtabFrame {  // a surface's patch frame (CtabDev::tri), the first link of the chain
+    float4 R0, R1, R2, R3;
+};
+__device__ __forceinline__ CtabFrame ctab_frame(const CtabDev& T, int surf) {
+    return CtabFrame{T.tri[surf * 4 + 0], T.tri[surf * 4 + 1], T.tri[surf * 4 + 2], T.tri[surf * 4 + 3]};
+}
+template <int NW>
+__device__ __forceinline__ CtabLook<NW> ctab_no_look() {
+    CtabLook<NW> L;
 #pragma unroll
-    for (int w = 0; w < NW; ++w) F[w] = (w < W) ? ((n_tri - 64 * w >= 64) ? ~0ull : ((1ull << (n_tri - 64 * w)) - 1ull)) : 0ull;
-    if (surf < 0 || surf >= n_surf) return;
-    const float4 R0 = T.tri[surf * 4 + 0], R1 = T.tri[surf * 4 + 1];
-    const float4 R2 = T.tri[surf * 4 + 2], R3 = T.tri[surf * 4 + 3];
+    for (int k = 0; k < NW; ++k) L.m[k] = 0ull;
+    L.gi = 0;
+    L.in = false;
+    L.cp = false;
+    return L;
+}
+// (with the frame of the surface, 0 <= surf < n_surf, in hand)
+template <int NW>
+__device__ __forceinline__ CtabLook<NW> ctab_begin(const CtabDev& T, const CtabFrame& R, f3 o, f3 d) {
+    CtabLook<NW> L = ctab_no_look<NW>();
+    const int W = T.words;
+    const float4 R0 = R.R0, R1 = R.R1, R2 = R.R2, R3 = R.R3;
     const float bx = o.x - R0.x, by = o.y - R0.y, bz = o.z - R0.z;
     const float w = (bx * R3.x + by * R3.y) + bz * R3.z;
     const float pu = ((bx * R1.x + by * R1.y) + bz * R1.z) * R0.w;
@@ -858,7 +883,7 @@ __device__ __forceinline__ void ctab_candidates(const CtabDev& T, int n_tri, int
     const float cn = (d.x * R3.x + d.y * R3.y) + d.z * R3.z;  // R3: the surface's shading normal
     const bool in = (fabsf(w) <= T.h) & (pu >= 0.0f) & (pu < (float)nu) & (pv >= 0.0f) & (pv < (float)nv) &
                     (len2 >= 1.0f - 0x1p-20f) & (len2 <= 1.0f + 0x1p-20f) & (cn >= -kCtabHemi);
-    if (!in) return;
+    if (!in) return L;
     // cube-map face: the axis of the largest |d_i| (x before y before z on ties), u, v the next two
     const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
     const bool fx = (ax >= ay) & (ax >= az), fy = !fx & (ay >= az);
@@ -874,15 +899,32 @@ __device__ __forceinline__ void ctab_candidates(const CtabDev& T, int n_tri, int
     const int gv = min(kCtabGraze - 1, max(0, (int)(v1 * (0.5f * kCtabGraze))));
     const int patch = base + (int)pu * nv + (int)pv;
     const unsigned long long* mm = T.masks + ((size_t)patch * (6 * kCtabBins * kCtabBins) + (f * kCtabBins + iu) * kCtabBins + iv) * W;
-    const int gi = (f * kCtabGraze + gu) * kCtabGraze + gv;
+    L.gi = (f * kCtabGraze + gu) * kCtabGraze + gv;
     // the triangles coplanar with the surface join near its plane's great circle (rule 0) or always (rule 1)
-    const bool cp = fabsf(cn) < T.cop_th;
+    L.cp = fabsf(cn) < T.cop_th;
+    L.in = true;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) L.m[k] = (k < W) ? mm[k] : 0ull;
+    return L;
+}
+template <int NW>
+__device__ __forceinline__ CtabLook<NW> ctab_begin(const CtabDev& T, int n_surf, int surf, f3 o, f3 d) {
+    if (surf < 0 || surf >= n_surf) return ctab_no_look<NW>();
+    return ctab_begin<NW>(T, ctab_frame(T, surf), o, d);
+}
+template <int NW>
+__device__ __forceinline__ void ctab_finish(const CtabDev& T, int n_tri, int surf, const CtabLook<NW>& L,
+                                            uint64_t (&F)[NW]) {
+    const int W = T.words;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) F[w] = (w < W) ? ((n_tri - 64 * w >= 64) ? ~0ull : ((1ull << (n_tri - 64 * w)) - 1ull)) : 0ull;
+    if (!L.in) return;
+    const uint64_t (&m)[NW] = L.m;
+    const int gi = L.gi;
+    const bool cp = L.cp;
     if (T.gflag) {
         // the grazing fold (rt_ctab.cpp): the entry holds its bin's grazing mask unless bit 63 of
         // its last word asks for the lookup -- one dependent access for most rays, not three
-        uint64_t m[NW];
-#pragma unroll
-        for (int k = 0; k < NW; ++k) m[k] = (k < W) ? mm[k] : 0ull;
         uint64_t last = 0ull;
 #pragma unroll
         for (int k = 0; k < NW; ++k)
@@ -899,7 +941,13 @@ __device__ __forceinline__ void ctab_candidates(const CtabDev& T, int n_tri, int
     const unsigned long long* gg = T.gdict + (size_t)T.gid[gi] * W;
 #pragma unroll
     for (int k = 0; k < NW; ++k)
-        if (k < W) F[k] = mm[k] | gg[k] | (cp ? T.cop[surf * W + k] : 0ull);
+        if (k < W) F[k] = m[k] | gg[k] | (cp ? T.cop[surf * W + k] : 0ull);
+}
+template <int NW>
+__device__ __forceinline__ void ctab_candidates(const CtabDev& T, int n_tri, int n_surf, int surf, f3 o, f3 d,
+                                                uint64_t (&F)[NW]) {
+    const CtabLook<NW> L = ctab_begin<NW>(T, n_surf, surf, o, d);
+    ctab_finish<NW>(T, n_tri, surf, L, F);
 }
 
 #ifndef RT_CTAB_OWN
@@ -1056,6 +1104,34 @@ __device__ __forceinline__ Hit closest_hit_ctab(const DeviceScene& s, const Ctab
     uint64_t F[NW];
     if (active) {
         ctab_candidates<NW>(T, s.n_tri, s.n_surf, surf, o, d, F);
+    } else {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) F[k] = 0ull;
+    }
+    return closest_hit_cand<RULE, NW, CAP>(s, F, o, d, t_scale, wl);
+}
+// closest_hit_ctab in two halves (ctab_begin / ctab_finish): what the caller runs between them
+// covers the latency of the entry's loads.  Same hit as the unsplit cast.
+template <int NW>
+__device__ __forceinline__ CtabLook<NW> closest_hit_ctab_begin(const DeviceScene& s, const CtabDev& T, int surf, f3 o,
+                                                               f3 d, bool active) {
+    // (an inactive lane: surf -1 is off the table and loads nothing)
+    return ctab_begin<NW>(T, s.n_surf, active ? surf : -1, o, d);
+}
+// (an active lane's surface frame loaded by the caller, ctab_frame)
+template <int NW>
+__device__ __forceinline__ CtabLook<NW> closest_hit_ctab_begin(const CtabDev& T, const CtabFrame& R, f3 o, f3 d,
+                                                               bool active) {
+    if (!active) return ctab_no_look<NW>();
+    return ctab_begin<NW>(T, R, o, d);
+}
+template <int RULE, int NW, int CAP = kMfPairCap>
+__device__ __forceinline__ Hit closest_hit_ctab_finish(const DeviceScene& s, const CtabDev& T, int surf,
+                                                       const CtabLook<NW>& L, f3 o, f3 d, float t_scale, bool active,
+                                                       float* wl) {
+    uint64_t F[NW];
+    if (active) {
+        ctab_finish<NW>(T, s.n_tri, surf, L, F);
     } else {
 #pragma unroll
         for (int k = 0; k < NW; ++k) F[k] = 0ull;
