@@ -644,7 +644,7 @@ bool build_mf_image(const std::vector<float4>& isect, int n, double mf_bound, st
                 (*frag)[(gi * 64 + 48 + 4 * s) * 8 + 6] = (uint16_t)(rb & 0xffffu);
                 (*frag)[(gi * 64 + 48 + 4 * s) * 8 + 7] = (uint16_t)(rb >> 16);
             }
-            // and the group's largest threshold (lane 49: RT_MF_RHO_GROUP builds)
+            // and the group's largest threshold (lane 49: the one closest_hit_mf reads)
             float gmax = 0.0f;
             for (int s = 0; s < 4; ++s) gmax = std::max(gmax, (*rho)[gi * 4 + s]);
             uint32_t gb;

@@ -567,13 +567,6 @@ __global__ __launch_bounds__(256) void k_fold_chunks(const RenderLaunch a) {
     store_rgb(dst, tot.x / fs, tot.y / fs, tot.z / fs);
 }
 
-#ifndef RT_PQ_CTAB
-#define RT_PQ_CTAB 1  // 0: k_render_pq's casts always on the matrix-core filter (A/B)
-#endif
-#ifndef RT_RENDER_PQ
-#define RT_RENDER_PQ 1  // 0: the GPU preset's matrix-core renders keep the per-pixel k_render (A/B)
-#endif
-
 // k_render_ps: the CPU-engine preset (PRESET 0) in two phases per wave.
 //
 // Primary rays are a known family: the camera position and the pixel rectangle of the
@@ -594,29 +587,12 @@ __global__ __launch_bounds__(256) void k_fold_chunks(const RenderLaunch a) {
 //   continuing: the hit point x, y, z, triangle;  ended: L.x, L.y, L.z, -1.
 // (int16 codes: 13 KB of slots per 256-lane workgroup at 4 samples per lane instead of 16 KB --
 // with the table route's pair list that is 25.6 KB per workgroup, six per CU)
-#ifndef RT_PS_CODE16
-#define RT_PS_CODE16 1  // the slots' hit codes as int16 beside three float rows (0: a fourth float row)
-#endif
-constexpr int kPsFields = RT_PS_CODE16 ? 3 : 4;  // float rows per sample slot
-
-#ifndef RT_PS_PRIM_BATCH
-#define RT_PS_PRIM_BATCH 4  // samples per candidate pass of phase P (1: one sample at a time)
-#endif
-#ifndef RT_PS_STEAL
-#define RT_PS_STEAL 1  // 0: each lane bounces only its own samples (A/B builds)
-#endif
-#ifndef RT_PS_CTAB
-#define RT_PS_CTAB 1  // 0: k_render_ps's bounce casts on the matrix-core image even with a candidate table (A/B)
-#endif
-#ifndef RT_PS_LIGHT_SPLIT
-#define RT_PS_LIGHT_SPLIT 1  // 0: terminal casts always run the full closest hit (A/B builds)
-#endif
+constexpr int kPsFields = 3;     // float rows per sample slot
+constexpr int kPsPrimBatch = 4;  // samples per candidate pass of phase P
 constexpr int kPsSplitLights = 8;  // the light pre-test runs when the scene has at most this many light triangles
-// floats of LDS per wave: the sample slots, then (RT_PS_STEAL) the wave's queue of
-// continuing samples, one u16 (k << 6 | lane) per slot
-__host__ __device__ constexpr int ps_wave_floats(int pc) {
-    return pc * kPsFields * 64 + (RT_PS_CODE16 ? pc * 32 : 0) + (RT_PS_STEAL ? pc * 32 : 0);
-}
+// floats of LDS per wave: the sample slots' float rows, their int16 codes, then the wave's
+// queue of continuing samples, one u16 (k << 6 | lane) per slot
+__host__ __device__ constexpr int ps_wave_floats(int pc) { return pc * kPsFields * 64 + pc * 32 + pc * 32; }
 
 
 // Candidate masks of the primary-ray phase: wave w of workgroup b writes
@@ -653,14 +629,8 @@ __global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
     }
 }
 
-#ifndef RT_PS_POOL
 // The table-route kernel defers the retraces of the light pre-test to one pooled trip of the
-// workgroup (ps_pool) instead of keeping each in its lane for the wave's next trip (0: A/B builds)
-#define RT_PS_POOL 1
-#endif
-#ifndef RT_PS_FOLD_LDS
-#define RT_PS_FOLD_LDS 1  // 0: ps_finish folds a pixel's chunk sums with shuffles on all lanes (A/B builds)
-#endif
+// workgroup (ps_pool) instead of keeping each in its lane for the wave's next trip.
 #ifndef RT_PS_POOL_SPAN
 // entries of the pooled trip a wave takes per step.  Cornell workgroups defer 10-35 samples, so
 // at 64 the first wave serves them all in one step; a build with a small span (4) puts the same
@@ -669,19 +639,7 @@ __global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
 #endif
 // whether k_render_ps<.., MF, CT> runs the pooled trip: its two barriers are compiled in or not
 // with this constant alone, never chosen at run time
-__host__ __device__ constexpr bool ps_pooled(int mf, bool ct) {
-    return RT_PS_POOL && RT_PS_STEAL && RT_PS_LIGHT_SPLIT && ct && mf == 1;
-}
-#ifndef RT_PS_PIPE
-// With the pooled trip, the light pre-test of a lane's sample runs one trip later, between the
-// issue of the next sample's table lookup and its first use (0: on the spot, A/B builds)
-#define RT_PS_PIPE 1
-#endif
-#ifndef RT_PS_EARLY
-// the pipelined loop loads the claimed sample's patch frame (the table lookup's first link)
-// with its shading frame, ahead of the Philox block (0: where the lookup starts, A/B builds)
-#define RT_PS_EARLY 1
-#endif
+__host__ __device__ constexpr bool ps_pooled(int mf, bool ct) { return ct && mf == 1; }
 // a deferred sample's slot code: the surface to shade (the terminal ray's origin) and the
 // path's first surface -- the table route has at most 64 triangles, so 6 bits each
 __device__ __forceinline__ int ps_defer_code(int hit_tri, int f_tri0) { return (1 << 12) | (f_tri0 << 6) | hit_tri; }
@@ -740,12 +698,36 @@ __device__ __forceinline__ void ps_fold(const float4* __restrict__ shade, f3& L,
     }
 }
 
+// The keys of the sample behind queue entry e (k << 6 | lane) of a wave whose lane 0 holds
+// pixel wq0 of the block: its pixel (the RNG key) and its sample index
+struct PsKeys {
+    uint32_t pix;
+    int cur;
+};
+__device__ __forceinline__ PsKeys ps_owner_keys(const RenderLaunch& a, const BlockDesc& blk, int wq0, int e) {
+    const int ol = e & 63, kk = e >> 6;
+    const int oq = wq0 + (ol >> a.split_log2);  // the owner lane's pixel
+    PsKeys key;
+    key.pix = (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
+    key.cur = (ol & (a.split - 1)) * a.per_chunk + kk;
+    return key;
+}
+// the light pre-test of the ray (lo, ld): whether a light triangle passes the exact test without
+// its t window (ps_body says what follows from it)
+template <int RULE>
+__device__ __forceinline__ bool ps_light_pass(const RenderLaunch& a, const DeviceScene& ms, const f3& lo, const f3& ld) {
+    const float nDx = -(ld.x * a.t_scale), nDy = -(ld.y * a.t_scale), nDz = -(ld.z * a.t_scale);
+    bool pass = false;
+    for (int j = a.scene.n_surf; j < a.scene.n_tri; ++j)
+        pass |= exact_tv<RULE>(ms.isect, j, lo, nDx, nDy, nDz) != __builtin_inff();
+    return pass;
+}
+
 // the end of k_render_ps for one wave with at least one pixel: every lane sums its own slots
-// in sample order onto acc (RT_PS_STEAL: ended samples hold their value in fields 0..2), the
+// in sample order onto acc (ended samples hold their value in fields 0..2), the
 // chunk sums of a pixel fold in chunk order and the pixel is stored
 __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc& blk, int chunk, int lane, int lx,
                                           int ly, bool valid, f3 acc) {
-#if RT_PS_STEAL
     extern __shared__ float s_ps[];
     const int pc = a.per_chunk;
     const float* const slots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc) + lane;
@@ -755,17 +737,14 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
         acc.y = acc.y + sl[1 * 64];
         acc.z = acc.z + sl[2 * 64];
     }
-#endif
     // fold the chunk sums of a pixel in chunk order: ((P0 + P1) + P2) + ...
     const int base = lane & ~(a.split - 1);
-#if RT_PS_FOLD_LDS
     // From four chunks on, through LDS: the lanes park their sums in the wave's slot region
     // (row c of slot 0, position lane: the lane's own, already summed above) and the pixel's
     // lanes of chunk 0, 1 and 2 each walk one channel in chunk order -- the same additions on
     // the same operands as the shuffle fold below, which keeps all 64 lanes busy for
     // split - 1 dependent rounds of three cross-lane reads each.
     if (a.split >= 4) {
-        extern __shared__ float s_ps[];
         float* const parkf = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(a.per_chunk);
         parkf[0 * 64 + lane] = acc.x;
         parkf[1 * 64 + lane] = acc.y;
@@ -780,7 +759,6 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
         }
         return;
     }
-#endif
     f3 tot = acc;
     for (int kk = 1; kk < a.split; ++kk) {
         const float vx = __shfl(acc.x, base + kk, 64);
@@ -809,20 +787,15 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
                                             int py, bool valid, int* n_deferred) {
     extern __shared__ float s_ps[];
     const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
-    const float4* __restrict__ shade = ms.shade;  // (RT_PS_SCENE_LDS: the workgroup's LDS copy)
+    const float4* __restrict__ shade = ms.shade;  // (the workgroup's LDS copy, when the kernel staged one)
     const int n_surf = a.scene.n_surf;
     const int pc = a.per_chunk;
     float* const wslots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc);
     float* const slots = wslots + lane;
     // a slot's hit code: the triangle a continuing path's primary hit is on, or -1 (ended)
-#if RT_PS_CODE16
     int16_t* const wcodes = reinterpret_cast<int16_t*>(wslots + pc * kPsFields * 64);
     auto code_at = [&](int kk, int ln) -> int { return (int)wcodes[kk * 64 + ln]; };
     auto set_code_at = [&](int kk, int ln, int c) { wcodes[kk * 64 + ln] = (int16_t)c; };
-#else
-    auto code_at = [&](int kk, int ln) -> int { return __float_as_int(wslots[(kk * kPsFields + 3) * 64 + ln]); };
-    auto set_code_at = [&](int kk, int ln, int c) { wslots[(kk * kPsFields + 3) * 64 + ln] = __int_as_float(c); };
-#endif
     const f3 cam = make3(a.cam_x, a.cam_y, a.cam_z);
 
     // ---- candidate triangles of the wave's pixel rectangle (rect_cull, rt_cull.hpp) ----
@@ -863,14 +836,13 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
         sl[2 * 64] = v2;
         set_code_at(k, lane, code);
     };
-#if RT_PS_PRIM_BATCH > 1
     // The primary rays all start at the camera, so the cofactors of the exact test that
     // involve only b = cam - v0 and the edges (s3, s4, s6, det_t) are the same for every
     // sample of the wave: computed once per candidate for a batch of samples, each sample
-    // then runs the direction-dependent rest (exact_one_c's operations on the same
+    // then runs the direction-dependent rest (exact_one's operations on the same
     // operands in the same order: the same bits).  Samples of a batch fold the candidates
-    // in index order each, as before.
-    constexpr int PB = RT_PS_PRIM_BATCH;
+    // in index order each.
+    constexpr int PB = kPsPrimBatch;
     for (int k0 = 0; k0 < pc; k0 += PB) {
         f3 dd[PB];
         float nx[PB], ny[PB], nz[PB];
@@ -918,29 +890,6 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
         for (int j = 0; j < PB; ++j)
             if (k0 + j < pc) park(k0 + j, dd[j], hh[j]);
     }
-#else
-    for (int k = 0; k < pc; ++k) {
-        const int s = chunk * pc + k;
-        float r1, r2;
-        draw2(pix, (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
-        f3 d;
-        camera_ray<0>(a, px, py, r1, r2, &d);
-        const float nDx = -(d.x * nts), nDy = -(d.y * nts), nDz = -(d.z * nts);
-        Hit h;
-        h.t = (RULE == 0) ? FLT_MAX : 999999.0f;
-        h.tri = -1;
-#pragma unroll
-        for (int g = 0; g < kRenderCullWords; ++g) {
-            uint64_t m = cm[g];
-            while (m != 0ull) {
-                const int b = __builtin_ctzll(m);
-                m &= m - 1ull;
-                exact_one_c<RULE>(isect, g * 64 + b, cam, nDx, nDy, nDz, h);
-            }
-        }
-        park(k, d, h);
-    }
-#endif
 
     // ---- phase S: bounces ----
 #if RT_PROF
@@ -948,21 +897,19 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     pt[0] += t_s - t0;
 #endif
     f3 acc = make3(0.0f, 0.0f, 0.0f);
-    int k = 0;          // next slot
-    int cur = 0;        // sample of the live path
+    int cur = 0;       // sample of the live path
     int depth = 0;      // surface bounces of the live path so far
     f3 o = cam, d = make3(0.0f, 0.0f, 1.0f);
     f3 pos = cam;       // the live path's surface hit to shade next, and its triangle
     int hit_tri = 0;
     int f_tri0 = 0;
     float f_cos0 = 0.0f;
-#if RT_PS_STEAL
     // The wave's continuing samples form one queue (slot-major: k, then lane), so a lane
     // whose path ends takes the next queued sample of any lane of the wave instead of
     // only its own: the wave runs ceil(casts / 64) trips instead of its busiest lane's.
     // A finished sample's value goes back into its slot; every lane then sums its own
     // slots in sample order (the fixed-chunk sum: the image is unchanged).
-    uint16_t* const queue = reinterpret_cast<uint16_t*>(wslots + pc * kPsFields * 64 + (RT_PS_CODE16 ? pc * 32 : 0));
+    uint16_t* const queue = reinterpret_cast<uint16_t*>(wslots + pc * kPsFields * 64 + pc * 32);
     int q_total = 0;
     for (int kk = 0; kk < pc; ++kk) {
         const bool cont = valid && code_at(kk, lane) >= 0;
@@ -1010,40 +957,13 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
             pos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
             hit_tri = code_at(kk, ol);
             depth = 0;
-            const int oq = q - (lane >> a.split_log2) + (ol >> a.split_log2);  // the lane's pixel
-            lpix = (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
-            cur = (ol & (a.split - 1)) * pc + kk;
+            const PsKeys key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), (int)e);
+            lpix = key.pix;
+            cur = key.cur;
             live = true;
         }
         q_next = min(q_total, q_next + __builtin_popcountll(need));
     };
-#endif
-    // next continuing sample of the lane (adding the values of the ended ones in order)
-    auto fetch = [&]() -> bool {
-        while (k < pc) {
-            const float* sl = slots + k * kPsFields * 64;
-            const int code = code_at(k, lane);
-            if (code < 0) {
-                acc.x = acc.x + sl[0 * 64];
-                acc.y = acc.y + sl[1 * 64];
-                acc.z = acc.z + sl[2 * 64];
-                ++k;
-                continue;
-            }
-            pos = make3(sl[0 * 64], sl[1 * 64], sl[2 * 64]);
-            hit_tri = code;
-            depth = 0;
-            cur = chunk * pc + k;
-            ++k;
-            return true;
-        }
-        return false;
-    };
-#if RT_PS_STEAL
-    (void)fetch;
-#else
-    bool live = valid && fetch();
-#endif
     // the bounce casts on the matrix cores when the scene has the image (wave-uniform)
     const bool use_mf = MF > 0;  // the launcher: MF = 64-triangle blocks of the scene (image present), else 0
     // scenes of at most 64 triangles: the candidates from the scene's table (rt_ctab.cpp) instead
@@ -1052,13 +972,9 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // the next direction from the surface hit (pos, hit_tri) at bounce depth dep: cos theta
     // and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the path's Philox draw
     auto shade_hit = [&](int dep, float* cos_out, f3* o_out, f3* d_out) {
-#if RT_PS_STEAL
         ps_shade_hit<SAMPLER>(a, shade, lpix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
-#else
-        ps_shade_hit<SAMPLER>(a, shade, pix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
-#endif
     };
-    // Light pre-test (RT_PS_LIGHT_SPLIT).  The terminal cast of a path (the one at depth
+    // Light pre-test.  The terminal cast of a path (the one at depth
     // max_bounces) adds light only if its closest hit is a light triangle; a surface or a miss
     // there gives 0.  If no light triangle passes the exact test without its t window
     // (exact_tv: the full test's own operations), the closest hit cannot be a light, and the
@@ -1068,14 +984,15 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // percent of rays) -> the path stays live and the next trip traces the same ray (same
     // Philox draw) in full.  Terminal casts thus stop taking slots of the matrix-core trips:
     // the image and the ray casts are k_render's bit for bit.
-    // With the pooled trip (ps_pooled, max_bounces <= 2) a pass does not stay in its lane: those
-    // retraces arrive after the wave's queue has drained, so most waves ran one more trip with a
-    // handful of live lanes at the cost of a full one.  The lane re-parks the sample in its
-    // slot (the hit point to shade, and ps_defer_code as its code) and is free for new work;
-    // ps_pool traces the workgroup's deferred samples together once its four waves are done.
-    // The terminal ray and its fold need (pos, hit_tri, f_tri0) and draws keyed by the slot alone,
-    // so nothing else is kept; at greater depths the path stays in its lane as before.
-    const bool split = RT_PS_LIGHT_SPLIT && use_mf && a.max_bounces >= 1 &&
+    // With the pooled trip (ps_pooled) a pass does not stay in its lane: those retraces arrive
+    // after the wave's queue has drained, so most waves ran one more trip with a handful of live
+    // lanes at the cost of a full one.  The lane re-parks the sample in its slot (the hit point
+    // to shade, and ps_defer_code as its code) and is free for new work; ps_pool traces the
+    // workgroup's deferred samples together once its four waves are done.  The terminal ray and
+    // its fold need (pos, hit_tri, f_tri0) and draws keyed by the slot alone, so nothing else is
+    // kept.  (`pool` is always true in the pooled variant: launch_render refuses the CPU preset
+    // above two bounces.)
+    const bool split = use_mf && a.max_bounces >= 1 &&
                        (a.scene.n_tri - n_surf) <= kPsSplitLights;
     const bool pool = ps_pooled(MF, CT) && a.max_bounces <= 2;
 #if RT_PROF
@@ -1086,20 +1003,20 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
         float c;
         f3 lo, ld;
         shade_hit(dep, &c, &lo, &ld);
-        const float nDx = -(ld.x * a.t_scale), nDy = -(ld.y * a.t_scale), nDz = -(ld.z * a.t_scale);
-        bool pass = false;
-        for (int j = n_surf; j < a.scene.n_tri; ++j)
-            pass |= exact_tv<RULE>(ms.isect, j, lo, nDx, nDy, nDz) != __builtin_inff();
-        return pass;
+        return ps_light_pass<RULE>(a, ms, lo, ld);
     };
 #if RT_PROF
     uint64_t t_pre = 0;  // wave cycles inside the light pre-test
 #endif
     bool piped = false;  // the pipelined loop has done the bounces: the loop after it does not run
-#if RT_PS_PIPE
     // The pipelined loop (pooled trip with the pre-test on: every live lane ends its path in
     // the trip that claimed it, so every trip starts with all lanes free and the paths at depth
-    // 0).  The cast's table lookup opens with two dependent global loads that nothing in the
+    // 0).  Invariant: deferrals come only from this loop.  launch_render refuses the CPU preset
+    // above two bounces, so in the pooled variant `pool` is true, this loop runs whenever the
+    // pre-test is on, and the loop after it runs only with the pre-test off: its deferral
+    // branch, the `deferred` flag and its listing in claim() never execute.  (Deleting them was
+    // measured and cost 2.6 % of the bench frame through register allocation alone: DESIGN.md
+    // §7, round 9.)  The cast's table lookup opens with two dependent global loads that nothing in the
     // lane's own chain covers, and the pre-test that follows a surface hit shares no data with
     // the lane's next sample.  So a sample whose cast hit a surface does not run its pre-test on
     // the spot: the lane keeps it as pending (the hit point, and the slot's entry packed with
@@ -1133,16 +1050,11 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
                 const int e = p_pack >> 12, ol = e & 63, kk = e >> 6;
                 bool pass = false;
                 if (pend) {
-                    const int oq = q - (lane >> a.split_log2) + (ol >> a.split_log2);
-                    const uint32_t ppix =
-                        (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
-                    const int pcur = (ol & (a.split - 1)) * pc + kk;
+                    const PsKeys key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), e);
                     float c;
                     f3 lo, ld;
-                    ps_shade_dir<SAMPLER>(a, pN, pT, pB, ppix, pcur, a.max_bounces - 1, p_pos, &c, &lo, &ld);
-                    const float nDx = -(ld.x * a.t_scale), nDy = -(ld.y * a.t_scale), nDz = -(ld.z * a.t_scale);
-                    for (int j = n_surf; j < a.scene.n_tri; ++j)
-                        pass |= exact_tv<RULE>(ms.isect, j, lo, nDx, nDy, nDz) != __builtin_inff();
+                    ps_shade_dir<SAMPLER>(a, pN, pT, pB, key.pix, key.cur, a.max_bounces - 1, p_pos, &c, &lo, &ld);
+                    pass = ps_light_pass<RULE>(a, ms, lo, ld);
                     f3 v = make3(0.0f, 0.0f, 0.0f);
                     if (pass) {
                         // the retrace waits for ps_pool: the hit to shade goes back into the slot
@@ -1188,24 +1100,15 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
                     const float* own = wslots + kk * kPsFields * 64 + ol;
                     const f3 spos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
                     s_tri = code_at(kk, ol);
-                    // the new sample's loads: its shading frame (and, RT_PS_EARLY, its patch frame, the
-                    // lookup's first link) ahead of the Philox block
+                    // the new sample's loads: its shading frame and its patch frame (the lookup's
+                    // first link) ahead of the Philox block
                     const float4 N = shade[s_tri * kShadeF4 + 0];
                     const float4 T = shade[s_tri * kShadeF4 + 1];
                     const float4 B = shade[s_tri * kShadeF4 + 2];
-#if RT_PS_EARLY
                     const CtabFrame R = ctab_frame(tab, s_tri);
-#endif
-                    const int oq = q - (lane >> a.split_log2) + (ol >> a.split_log2);  // the owner's pixel
-                    const uint32_t spix =
-                        (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
-                    const int scur = (ol & (a.split - 1)) * pc + kk;
-                    ps_shade_dir<SAMPLER>(a, N, T, B, spix, scur, 0, spos, &s_cos, &so, &sd);
-#if RT_PS_EARLY
+                    const PsKeys key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), s_e);  // the owner's
+                    ps_shade_dir<SAMPLER>(a, N, T, B, key.pix, key.cur, 0, spos, &s_cos, &so, &sd);
                     look = closest_hit_ctab_begin<1>(tab, R, so, sd, true);
-#else
-                    look = closest_hit_ctab_begin<1>(ms, tab, s_tri, so, sd, true);
-#endif
                 }
 #if RT_PROF
                 const uint64_t tb = __builtin_amdgcn_s_memtime();
@@ -1245,11 +1148,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
             if (__ballot(pend) != 0ull) pretest_pending();
         }
     }
-#endif
     for (; !piped;) {
-#if RT_PS_STEAL
         claim();
-#endif
         if (__ballot(live) == 0ull) break;
         if (!use_mf && !live) continue;
 #if RT_PROF
@@ -1326,7 +1226,6 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
 #if RT_PROF
                     ++n_pass;
 #endif
-#if RT_PS_STEAL
                     if (pool) {
                         // the retrace waits for ps_pool: the hit to shade goes back into the slot
                         // in place of a value (below), and the next claim() lists the slot
@@ -1335,23 +1234,15 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
                         deferred = true;
                         terminal = true;
                     }
-#endif
                 }
             }
         }
         if (terminal) {
-#if RT_PS_STEAL
             float* own = own_slot();
             own[0 * 64] = L.x;
             own[1 * 64] = L.y;
             own[2 * 64] = L.z;
             live = false;
-#else
-            acc.x = acc.x + L.x;
-            acc.y = acc.y + L.y;
-            acc.z = acc.z + L.z;
-            live = fetch();
-#endif
         }
     }
 #if RT_PROF
@@ -1362,11 +1253,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
         atomicAdd(a.prof + 9, (unsigned long long)t_pre);
     }
 #endif
-#if RT_PS_STEAL
     *n_deferred = n_def;
-#else
-    *n_deferred = 0;
-#endif
     // (with the pooled trip the kernel finishes the wave after ps_pool; acc is still 0 there)
     if constexpr (!ps_pooled(MF, CT)) ps_finish(a, blk, chunk, lane, lx, ly, valid, acc);
     return n_casts;
@@ -1411,16 +1298,11 @@ __device__ __forceinline__ unsigned ps_pool(const RenderLaunch& a, const DeviceS
         f3 o = make3(0.0f, 0.0f, 0.0f), d = make3(0.0f, 0.0f, 1.0f);
         if (has) {
             float* const ws = s_ps + (size_t)ow * ps_wave_floats(pc);
-            const uint16_t* oqueue =
-                reinterpret_cast<const uint16_t*>(ws + pc * kPsFields * 64 + (RT_PS_CODE16 ? pc * 32 : 0));
+            const uint16_t* oqueue = reinterpret_cast<const uint16_t*>(ws + pc * kPsFields * 64 + pc * 32);
             const uint32_t e = oqueue[j];
             const int ol = (int)(e & 63u), kk = (int)(e >> 6);
             own = ws + kk * kPsFields * 64 + ol;
-#if RT_PS_CODE16
             const int code = (int)reinterpret_cast<const int16_t*>(ws + pc * kPsFields * 64)[kk * 64 + ol];
-#else
-            const int code = __float_as_int(own[3 * 64]);
-#endif
             hit_tri = code & 63;
             f_tri0 = (code >> 6) & 63;
             const int ot = ow * 64 + ol;  // the owner's threadIdx.x
@@ -1472,7 +1354,7 @@ __device__ __forceinline__ unsigned ps_pool(const RenderLaunch& a, const DeviceS
 #define RT_PS_MIN_WAVES 4  // the matrix-core filter's operands: ~99 VGPRs
 #endif
 #ifndef RT_PS_CT_WAVES
-// occupancy floor of the table-route variant: 6 (80 VGPRs, 7 spilled) -- with the int16 slot codes
+// occupancy floor of the table-route variant: 6 (80 VGPRs, 9 spilled) -- with the int16 slot codes
 // its workgroup takes 26.7 KB of LDS and six fit a CU (Cornell 512^2 x 256: 2.39 -> 2.24 ms,
 // profiles/r6v/; at the 28.7-KB layout LDS held it to five and 6 only added spills)
 #define RT_PS_CT_WAVES 6
@@ -1500,7 +1382,7 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
     // wave put 16 MB per launch of atomic write traffic on a 3 MB frame
     __shared__ unsigned wg_casts[4];
     // LDS after the sample slots (launch_render_t sizes it): the waves' exact-phase
-    // regions, then (RT_MF_LDS) the matrix-core filter's image
+    // regions, then the scene's hit-test records and, when not CT, its shading records
     DeviceScene ms = a.scene;
     float* wl = nullptr;
     if (MF > 0) {
@@ -1509,56 +1391,21 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
         // (the table route's wave blocks hold a shorter pair list: mf_wave_floats)
         constexpr int wf = CT ? mf_wave_floats(kCtPairCap, RULE) : kMfWaveFloats;
         wl = mf_base + (size_t)(threadIdx.x >> 6) * wf;
-        float* next = mf_base + 4 * wf;
-#if RT_PS_SCENE_LDS
         // hit-test and shading records of the scene (divergent per-lane reads: LDS latency
-        // instead of L1/L2)
-        {
-            const int n = a.scene.n_tri;
-            float4* li = reinterpret_cast<float4*>(next);
-            float4* ls = li + (size_t)n * kIsectF4;
-            for (int i = threadIdx.x; i < n * kIsectF4; i += 256) li[i] = a.scene.isect[i];
-            ms.isect = li;
-            constexpr bool shade_lds = RT_PS_SHADE_LDS && (!CT || RT_PS_CT_SHADE_LDS);
-            if (shade_lds) {
-                for (int i = threadIdx.x; i < n * kShadeF4; i += 256) ls[i] = a.scene.shade[i];
-                ms.shade = ls;
-            }
-            next = reinterpret_cast<float*>(ls + (shade_lds ? (size_t)n * kShadeF4 : 0));
-        }
-#endif
-#if RT_PS_CT_TRI_LDS
-        // the table's surface patch frames (the first link of every bounce cast's lookup chain:
-        // frame -> patch and bin -> mask words): from LDS instead of L1/L2
-        if constexpr (CT) {
-            float4* lt = reinterpret_cast<float4*>(next);
-            const int m = a.scene.n_surf * 4;
-            for (int i = threadIdx.x; i < m; i += 256) lt[i] = a.scene.ctab[RULE].tri[i];
-            ms.ctab[RULE].tri = lt;
-            next = reinterpret_cast<float*>(lt + m);
-        }
-#endif
-#if RT_PS_CT_DICT_LDS
-        // the grazing masks' dictionary (a few dozen words): the last link of the lookup chain in LDS
-        if constexpr (CT) {
-            const CtabDev& T = a.scene.ctab[RULE];
-            if (T.n_gdict <= kPsCtDictLds) {
-                unsigned long long* ld = reinterpret_cast<unsigned long long*>(next);
-                for (int i = threadIdx.x; i < T.n_gdict; i += 256) ld[i] = T.gdict[i];
-                ms.ctab[RULE].gdict = ld;
-            }
-            next += 2 * kPsCtDictLds;
-        }
-#endif
-#if RT_MF_LDS
+        // instead of L1/L2).  The table-route kernel reads its shading records from L1/L2: with
+        // the shorter pair list that kept the workgroup at 29.4 KB of LDS, five per CU (Cornell
+        // 512^2 x 256: 2.33 ms, in LDS 2.37-2.40; the 35.6-KB layout of round 5 held four per
+        // CU: 2.63 ms, profiles/r6f/ab.log)
+        const int n = a.scene.n_tri;
+        float4* li = reinterpret_cast<float4*>(mf_base + 4 * wf);
+        for (int i = threadIdx.x; i < n * kIsectF4; i += 256) li[i] = a.scene.isect[i];
+        ms.isect = li;
         if (!CT) {
-            const int ng = mf_groups(a.scene.n_tri);
-            uint4* lf = reinterpret_cast<uint4*>(next);
-            for (int i = threadIdx.x; i < ng * 64; i += 256) lf[i] = a.scene.mf_frag[i];
-            ms.mf_frag = lf;
+            float4* ls = li + (size_t)n * kIsectF4;
+            for (int i = threadIdx.x; i < n * kShadeF4; i += 256) ls[i] = a.scene.shade[i];
+            ms.shade = ls;
         }
-#endif
-        if (RT_PS_SCENE_LDS || (RT_MF_LDS && !CT) || ((RT_PS_CT_TRI_LDS || RT_PS_CT_DICT_LDS) && CT)) __syncthreads();
+        __syncthreads();
     }
     int n_def = 0;  // the wave's samples left for the pooled trip
     unsigned n_casts = 0;
@@ -1568,7 +1415,7 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
         // The pooled trip.  Its two barriers stand here, at the kernel's top level: outside every
         // loop and under no condition but the template's constant, so all four waves reach both
         // -- a wave without pixels too (it skipped ps_body above, publishes 0 and serves the
-        // pool like the others), and also a launch that defers nothing (max_bounces > 2).
+        // pool like the others), and also a launch that defers nothing (the light pre-test off).
         // wg_casts carries the waves' deferred counts first; the second barrier frees it for
         // the casts below and makes the pool's values visible to the slots' owners.
         if (lane == 0) wg_casts[threadIdx.x >> 6] = (unsigned)n_def;
@@ -1727,21 +1574,11 @@ hipError_t launch_intersect_cand(const DeviceScene& s, const float* orig, const 
     return hipGetLastError();
 }
 
-#ifndef RT_MF_RENDER
-#define RT_MF_RENDER 1  // 0: the GPU preset's casts on the fp32 filter (A/B builds)
-#endif
-#ifndef RT_CAM_CULL
-#define RT_CAM_CULL 1  // 0: a camera outside the image's bound keeps the fp32 filter (A/B builds)
-#endif
-#ifndef RT_STEAL_MAX_LDS
-#define RT_STEAL_MAX_LDS (64 * 1024)  // sample stealing when its LDS fits (0: never)
-#endif
-
 // Sample stealing pays where path lengths vary (GPU preset, up to 80 casts: Cornell
 // +24%, complex_light_room +32%); with the CPU preset's cap of 3 casts the lanes stay
 // in step and it costs 1%, so that preset keeps the fixed chunks.
-#ifndef RT_PS
-#define RT_PS 1  // 0: the CPU preset without the primary-ray phase (A/B builds)
+#ifndef RT_STEAL_MAX_LDS
+#define RT_STEAL_MAX_LDS (64 * 1024)  // sample stealing when its LDS fits (0: never)
 #endif
 #ifndef RT_PS_MAX_LDS
 #define RT_PS_MAX_LDS (40 * 1024)  // per workgroup: 8 samples per lane
@@ -1749,25 +1586,23 @@ hipError_t launch_intersect_cand(const DeviceScene& s, const float* orig, const 
 
 template <int PRESET, int SAMPLER, int RULE>
 static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
-    if (PRESET == 0 && RT_PS && a.use_filter && a.scene.n_tri <= 64 * kRenderCullWords &&
+    if (PRESET == 0 && a.use_filter && a.scene.n_tri <= 64 * kRenderCullWords &&
         a.scene.bvh_nodes == nullptr) {
         const size_t ps_lds = (size_t)4 * ps_wave_floats(a.per_chunk) * sizeof(float);
         if (ps_lds <= (size_t)RT_PS_MAX_LDS) {
             // the bounce casts from the scene's candidate table (rt_ctab.cpp) when it serves this
             // launch: one mask word, this build's bins, t_scale >= its ts_min
             const CtabDev& T = a.scene.ctab[RULE];
-            const bool ct = RT_PS_CTAB && RT_MF && a.scene.mf_frag != nullptr && a.scene.n_tri <= 64 &&
-                            T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze &&
-                            a.t_scale >= T.ts_min && T.words == 1;
+            const bool ct = a.scene.mf_frag != nullptr && a.scene.n_tri <= 64 && T.masks != nullptr &&
+                            T.bins == kCtabBins && T.graze_n == kCtabGraze && a.t_scale >= T.ts_min && T.words == 1;
+            // The kernel's dynamic LDS, in its order: ps_lds, the four waves' slots, codes and
+            // queue (ps_wave_floats); then, with the matrix-core image, the four waves' exact-phase
+            // blocks (the table route's hold the shorter pair list), the scene's isect records and,
+            // when not CT, its shading records
             size_t mf_lds = 0;
-            if (RT_MF && a.scene.mf_frag != nullptr) {
+            if (a.scene.mf_frag != nullptr) {
                 mf_lds = (size_t)4 * (ct ? mf_wave_floats(kCtPairCap, RULE) : kMfWaveFloats) * sizeof(float);
-                if (RT_PS_SCENE_LDS)
-                    mf_lds += (size_t)a.scene.n_tri *
-                              (kIsectF4 + (RT_PS_SHADE_LDS && (!ct || RT_PS_CT_SHADE_LDS) ? kShadeF4 : 0)) * sizeof(float4);
-                if (RT_MF_LDS && !ct) mf_lds += (size_t)mf_groups(a.scene.n_tri) * 64 * sizeof(uint4);
-                if (RT_PS_CT_TRI_LDS && ct) mf_lds += (size_t)a.scene.n_surf * 4 * sizeof(float4);
-                if (RT_PS_CT_DICT_LDS && ct) mf_lds += (size_t)kPsCtDictLds * sizeof(uint64_t);
+                mf_lds += (size_t)a.scene.n_tri * (kIsectF4 + (ct ? 0 : kShadeF4)) * sizeof(float4);
             }
             const dim3 grid((unsigned)(a.n_blocks * a.split));
             KernelTimer kt(KT_RENDER_PS, stream);
@@ -1789,13 +1624,13 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
     // the GPU preset's casts on the matrix-core filter: when the scene has the image and
     // the camera is inside its origin bound (camera rays then get real masks)
     const float cb = a.scene.mf_bound;
-    const bool mf_base = PRESET == 1 && RT_MF_RENDER && a.use_filter && a.scene.mf_frag != nullptr &&
+    const bool mf_base = PRESET == 1 && a.use_filter && a.scene.mf_frag != nullptr &&
                          a.scene.bvh_nodes == nullptr && a.t_scale > 0.0f && a.t_scale <= kFiltMaxTScale;
     const bool cam_in = fabsf(a.cam_x) <= cb && fabsf(a.cam_y) <= cb && fabsf(a.cam_z) <= cb;
     // a camera outside the bound: its rays take the wave's primary-ray cull (rt_cull.hpp),
     // which models the CPU preset's camera -- the GPU preset's is the same ray when the
     // pitch is 0 (camera_ray: the second rotation is the identity, exactly)
-    const bool cam_cull = !cam_in && RT_CAM_CULL && a.scene.n_tri <= 64 * kRenderCullWords &&
+    const bool cam_cull = !cam_in && a.scene.n_tri <= 64 * kRenderCullWords &&
                           a.cos_x == 1.0f && a.sin_x == 0.0f;
     const bool mf = mf_base && (cam_in || cam_cull);
     if (mf) {
@@ -1803,7 +1638,7 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
             RenderLaunch b = a;
             b.cam_cull = cam_in ? 0 : 1;
             const bool one = a.scene.n_tri <= 64;
-            if (RT_RENDER_PQ && cam_in && a.csum != nullptr && a.work != nullptr) {
+            if (cam_in && a.csum != nullptr && a.work != nullptr) {
                 (void)hipMemsetAsync(a.work, 0, sizeof(unsigned long long), stream);
                 // a persistent grid: as many workgroups as the device holds at 4 waves per SIMD
                 const unsigned wgs = (unsigned)min(a.n_blocks * a.split, RT_MF_RENDER_WAVES * device_cu_count());
@@ -1811,7 +1646,7 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
                 // t_scale, and the camera rays' rectangle cull -- CPU-preset camera geometry, i.e.
                 // pitch 0 (camera_ray: the second rotation is then the identity, exactly)
                 const CtabDev& T = a.scene.ctab[RULE];
-                const bool ct = RT_PQ_CTAB && a.cull != nullptr && a.cos_x == 1.0f && a.sin_x == 0.0f &&
+                const bool ct = a.cull != nullptr && a.cos_x == 1.0f && a.sin_x == 0.0f &&
                                 a.scene.n_tri <= 64 * kRenderCullWords && T.masks != nullptr && T.bins == kCtabBins &&
                                 T.graze_n == kCtabGraze && a.t_scale >= T.ts_min && T.words <= (one ? 1 : 4);
                 if (ct) {

@@ -105,11 +105,8 @@ RT_HD f3 cross(f3 x, f3 y) {
     return make3(x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y);
 }
 
-#ifndef RT_XOR3
-#define RT_XOR3 1
-#endif
 // a ^ b ^ c: one v_bitop3_b32 on gfx950 (the compiler emits two v_xor_b32 for it)
-#if defined(__HIP_DEVICE_COMPILE__) && RT_XOR3
+#if defined(__HIP_DEVICE_COMPILE__)
 #define RT_XOR3F(a, b, c) __builtin_amdgcn_bitop3_b32((a), (b), (c), 0x96)
 #else
 #define RT_XOR3F(a, b, c) ((a) ^ (b) ^ (c))

@@ -51,29 +51,10 @@ struct Hit {
 // RULE 0 = CPU triangle.cpp.o predicate (inv = 1/detA; accept t>=0, u>=0, v>=0,
 //          u+v<=1, t < best+1e-5, t > 1e-5; best starts at FLT_MAX)
 // RULE 1 = GPU/rays/ray.cu:63-64 (true divisions; t < best; best starts 999999)
-// Build-time knobs (A/B experiments; defaults are the shipped configuration):
-//   RT_HIT_MODE 0: exact; u/v behind a branch on the t test (skipped per wave)
-//               1: exact, branch-free
-//               2: conservative approximate rejection (v_rcp_f32) first; the
-//                  exact IEEE test runs only for lanes it cannot reject
-//   RT_UNROLL   unroll factor of the triangle loop
-#ifndef RT_HIT_MODE
-#define RT_HIT_MODE 2  // 7% faster than 0 on Cornell 512^2/256 spp, same image (profiles/r1_ab3.json)
-#endif
-#ifndef RT_UNROLL
-#define RT_UNROLL 1
-#endif
-//   RT_FAST_RCP 1: 1/detA by rcp_rn (v_rcp_f32 + Newton, exhaustively verified)
-#ifndef RT_FAST_RCP
-#define RT_FAST_RCP 1
-#endif
-#if RT_FAST_RCP
-#define RT_RCP(x) rcp_rn(x)
-#else
-#define RT_RCP(x) (1.0f / (x))
-#endif
-
-// rcp_rn / rcp_rn_from: rt_math.hpp
+// The scan rejects conservatively first (v_rcp_f32) and runs the exact IEEE test only for
+// lanes it cannot reject: 7% faster than the exact test behind a branch on the t test on
+// Cornell 512^2/256 spp, same image (profiles/r1_ab3.json).  1/detA is rcp_rn (v_rcp_f32 +
+// Newton, exhaustively verified; rcp_rn / rcp_rn_from: rt_math.hpp).
 
 // Exact hit test of one triangle (the reference's arithmetic, see above).
 template <int RULE>
@@ -94,7 +75,7 @@ template <int RULE>
 __device__ __forceinline__ void exact_test(float detA, float det_t, float det_u, float det_v, int i,
                                            Hit& h) {
     if (RULE == 0) {
-        const float inv = RT_RCP(detA);
+        const float inv = rcp_rn(detA);
         const float t = det_t * inv;
         const float u = det_u * inv;
         const float v = det_v * inv;
@@ -125,11 +106,9 @@ __device__ __forceinline__ Hit closest_hit(const float4* __restrict__ tri_g, int
     Hit h;
     h.t = (RULE == 0) ? FLT_MAX : 999999.0f;
     h.tri = -1;
-#if RT_HIT_MODE == 2
     // upper bound of the t window, widened by 2^-18 (RULE 0: best + eps)
     float hi = ((RULE == 0) ? (h.t + kEps) : h.t) * (1.0f + 0x1p-18f);
-#endif
-#pragma unroll RT_UNROLL
+#pragma unroll 1
     for (int i = 0; i < n_tri; ++i) {
         const float4 A = ldc(tri + i * kIsectF4 + 0);
         const float4 E1 = ldc(tri + i * kIsectF4 + 1);
@@ -143,33 +122,11 @@ __device__ __forceinline__ Hit closest_hit(const float4* __restrict__ tri_g, int
         const float s3 = by * E2.z - E2.y * bz;
         const float s4 = by * E1.z - E1.y * bz;
         const float det_t = (bx * A.w - E1.x * s3) + E2.x * s4;
-#if RT_HIT_MODE == 0
-        bool tpass;
-        float inv = 0.0f;
-        if (RULE == 0) {
-            inv = RT_RCP(detA);
-            const float t = det_t * inv;
-            tpass = (detA != 0.0f) && (t >= 0.0f) && (t < h.t + kEps) && (t > kEps);
-        } else {
-            const float t = det_t / detA;
-            tpass = (detA != 0.0f) && (t >= 0.0f) && (t < h.t);
-        }
-        if (tpass) {
-            // det_u = det(-D, b, e2), det_v = det(-D, e1, b)
-            const float s5 = nDy * bz - by * nDz;
-            const float s6 = E1.y * bz - by * E1.z;
-            const float det_u = (nDx * s3 - bx * s1) + E2.x * s5;
-            const float det_v = (nDx * s6 - E1.x * s5) + bx * s2;
-            exact_test<RULE>(detA, det_t, det_u, det_v, i, h);
-        }
-#else
+        // det_u = det(-D, b, e2), det_v = det(-D, e1, b)
         const float s5 = nDy * bz - by * nDz;
         const float s6 = E1.y * bz - by * E1.z;
         const float det_u = (nDx * s3 - bx * s1) + E2.x * s5;
         const float det_v = (nDx * s6 - E1.x * s5) + bx * s2;
-#if RT_HIT_MODE == 1
-        exact_test<RULE>(detA, det_t, det_u, det_v, i, h);
-#else
         // Conservative rejection: with |detA| in [2^-100, 2^100], v_rcp_f32 is
         // within 1 ulp, so ta/ua/va differ from the exact t/u/v by < 2^-21
         // relative.  A lane is rejected only if the exact test must fail:
@@ -186,18 +143,12 @@ __device__ __forceinline__ Hit closest_hit(const float4* __restrict__ tri_g, int
                                ((ta < lo) || (ta > hi) || (ua < -0x1p-90f) || (va < -0x1p-90f) ||
                                 ((ua + va) > 1.0f + 0x1p-18f));
         if (!sure_miss) {
-#if RT_FAST_RCP
             if (RULE == 0)
                 exact_test_inv<RULE>(detA, rcp_rn_from(detA, r), det_t, det_u, det_v, i, h);
             else
                 exact_test<RULE>(detA, det_t, det_u, det_v, i, h);
-#else
-            exact_test<RULE>(detA, det_t, det_u, det_v, i, h);
-#endif
             hi = ((RULE == 0) ? (h.t + kEps) : h.t) * (1.0f + 0x1p-18f);
         }
-#endif
-#endif
     }
     return h;
 }
@@ -485,7 +436,7 @@ __device__ __forceinline__ float exact_tv(const float4* __restrict__ tri, int i,
     const float det_v = (nDx * s6 - E1.x * s5) + bx * s2;
     float t, u, v;
     if (RULE == 0) {
-        const float inv = RT_RCP(detA);
+        const float inv = rcp_rn(detA);
         t = det_t * inv;
         u = det_u * inv;
         v = det_v * inv;
@@ -502,43 +453,26 @@ __device__ __forceinline__ float exact_tv(const float4* __restrict__ tri, int i,
 #ifndef RT_PROF
 #define RT_PROF 0  // 1: k_render_ps sums per-phase s_memtime cycles into RenderLaunch::prof
 #endif
-#ifndef RT_MF_PINGPONG
-#define RT_MF_PINGPONG 1  // 0: one operand set prefetched a group ahead (copied each group)
-#endif
-#ifndef RT_MF_RHO_GROUP
-#define RT_MF_RHO_GROUP 1  // one sign-test threshold per 4-triangle group, the largest (0: per slot, 2: 1/2; 1 measured fastest, profiles/r3i)
-#endif
-#ifndef RT_MF_FIRST_OWN
-// 1: with one 64-triangle block (NB == 1) each lane tests its first candidate itself, the
-// rest shared (Cornell 512^2 x 256: 3.92 vs 4.00 ms; on complex_light_room's four blocks it
-// measured 314 vs 310 ms, so wider scenes share every pair: profiles/r3q/)
-#define RT_MF_FIRST_OWN 1
-#endif
-#ifndef RT_MF_COOP
-#define RT_MF_COOP 1  // 0: each lane runs its own candidates' exact tests (A/B builds)
-#endif
 
 // LDS of one wave for the shared exact phase: rays [6][64] (o, -D), pairs [cap] u16
-// (lane << 6 | triangle of the block); the tests' t values stay in registers
+// (lane << 6 | triangle of the block), then the tests' t values [cap] (read back from LDS:
+// by cross-lane reads instead, Cornell 512^2 x 256 took 4.19 vs 3.96 ms)
 #ifndef RT_MF_PAIR_CAP
 #define RT_MF_PAIR_CAP 256
 #endif
-#ifndef RT_MF_TV_LDS
-#define RT_MF_TV_LDS 1  // 0: t values by cross-lane reads (Cornell 512^2 x 256: 4.19 vs 3.96 ms)
-#endif
 constexpr int kMfPairCap = RT_MF_PAIR_CAP;
-constexpr int kMfWaveFloats = 6 * 64 + kMfPairCap / 2 + (RT_MF_TV_LDS ? kMfPairCap : 0);
+constexpr int kMfWaveFloats = 6 * 64 + kMfPairCap / 2 + kMfPairCap;
 static_assert(kMfWaveFloats >= 11 * 64, "cand_exact_min's LDS (rays, first, mask, key) fits a wave's block");
 // The table-route kernel k_render_ps<.., CT> (RULE 0): about 3 candidates per ray of which the
 // lane tests its first RT_CTAB_OWN itself, so the shared phase lists a few dozen pairs per wave;
-// a smaller list block (with RT_PS_CT_SHADE_LDS) lets one more workgroup fit a CU's LDS
+// a smaller list block (with the shading records left in L1/L2) lets one more workgroup fit a
+// CU's LDS
 #ifndef RT_PS_CT_PAIR_CAP
 #define RT_PS_CT_PAIR_CAP 96  // (64 / 96 / 128 / 256: 2.37 / 2.33 / 2.34 / 2.63 ms with the shading records in L1/L2)
 #endif
 constexpr int kCtPairCap = RT_PS_CT_PAIR_CAP;
 __host__ __device__ constexpr int mf_wave_floats(int cap, int rule) {
-    return (rule == 1 && 6 * 64 + cap / 2 + (RT_MF_TV_LDS ? cap : 0) < 11 * 64) ? 11 * 64
-                                                                              : 6 * 64 + cap / 2 + (RT_MF_TV_LDS ? cap : 0);
+    return (rule == 1 && 6 * 64 + cap / 2 + cap < 11 * 64) ? 11 * 64 : 6 * 64 + cap / 2 + cap;
 }
 
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -563,9 +497,6 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
     if (total == 0) return;
     const float* ray = wl;  // (o, -D) of every lane: written by closest_hit_mf before its masks
     uint16_t* pr = reinterpret_cast<uint16_t*>(wl + 6 * 64);
-    // the lane's pairs not yet folded (lowest bit first) and the list position of the next
-    uint64_t R = F;
-    int pos = excl;
     for (int cb = 0; cb < total; cb += CAP) {
         {
             uint64_t G = F;
@@ -579,7 +510,6 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
         }
         wave_lds_sync();
         const int nb = min(CAP, total - cb);
-#if RT_MF_TV_LDS
         float* tv = wl + 6 * 64 + CAP / 2;
         for (int k = lane; k < nb; k += 64) {
             const uint32_t q = pr[k];
@@ -605,42 +535,6 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
                 ++p;
             }
         }
-        (void)R;
-        (void)pos;
-#else
-        for (int sb = 0; sb < nb; sb += 64) {
-            // 64 pairs at a time: lane k tests pair sb + k; each lane then takes its own pairs'
-            // results from the testing lanes' registers (ds_bpermute: no LDS array for them)
-            float tr = __builtin_inff();
-            const int k = sb + lane;
-            if (k < nb) {
-                const uint32_t q = pr[k];
-                const int rl = (int)(q >> 6);
-                const f3 ro = make3(ray[0 * 64 + rl], ray[1 * 64 + rl], ray[2 * 64 + rl]);
-                tr = exact_tv<RULE>(isect, tri0 + (int)(q & 63u), ro, ray[3 * 64 + rl], ray[4 * 64 + rl],
-                                    ray[5 * 64 + rl]);
-            }
-            // The fold, one pair per lane and step, with the whole wave active: a cross-lane
-            // read (ds_bpermute) from a lane that is switched off returns 0, not its value,
-            // so the read must not sit in a lane-divergent loop.  A lane's next pair is in
-            // this window iff pos < base + 64 (earlier windows consumed those before it).
-            const int base = cb + sb;
-            for (;;) {
-                const bool has = (R != 0ull) && (pos < base + 64);
-                if (__ballot(has) == 0ull) break;
-                const float t = __shfl(tr, has ? pos - base : 0, 64);
-                if (has) {
-                    const int b = __builtin_ctzll(R);
-                    R &= R - 1ull;
-                    ++pos;
-                    if ((RULE == 0) ? (t < h.t + kEps) : (t < h.t)) {
-                        h.t = t;
-                        h.tri = tri0 + b;
-                    }
-                }
-            }
-        }
-#endif
         wave_lds_sync();  // the pair list is read before the next window overwrites it
     }
 }
@@ -673,7 +567,6 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
     wl[4 * 64 + lane] = nDy;
     wl[5 * 64 + lane] = nDz;
     const uint4* __restrict__ frag = s.mf_frag;
-    [[maybe_unused]] const int slot = lane >> 4;  // the lane's slot of the MFMA output
     const mf_f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
 
     Hit h;
@@ -719,19 +612,10 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
                 // one 4-triangle group: 4 MFMAs (ray blocks 0..3), drop bits shifted in
                 auto group = [&](const mf_u32x4 af) {
                     // the slots' sign-test thresholds, stored in the fragment's unused K entries
-                    // (build_mf_image: lane 48 + 4 s, dword 3)
-#if RT_MF_RHO_GROUP == 2
-                    const float rho = 0.5f;  // the bound of every threshold (loosest)
-#elif RT_MF_RHO_GROUP == 1
-                    // the group's largest (one scalar per group: a looser test for its smaller triangles)
+                    // (build_mf_image: lane 48 + 4 s, dword 3): the group's largest, lane 49 (one scalar
+                    // per group, a looser test for its smaller triangles; measured faster than
+                    // per-slot thresholds and than the bound 1/2 for all, profiles/r3i)
                     const float rho = __int_as_float(__builtin_amdgcn_readlane((int)af[3], 49));
-#else
-                    const float t0 = __int_as_float(__builtin_amdgcn_readlane((int)af[3], 48));
-                    const float t1 = __int_as_float(__builtin_amdgcn_readlane((int)af[3], 52));
-                    const float t2 = __int_as_float(__builtin_amdgcn_readlane((int)af[3], 56));
-                    const float t3 = __int_as_float(__builtin_amdgcn_readlane((int)af[3], 60));
-                    const float rho = (slot & 2) ? ((slot & 1) ? t3 : t2) : ((slot & 1) ? t1 : t0);
-#endif
                     const mf_bf16x8 A = __builtin_bit_cast(mf_bf16x8, af);
                     const mf_f32x4 q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B0, zero, 0, 0, 0);
                     const mf_f32x4 q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B1, zero, 0, 0, 0);
@@ -742,7 +626,6 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
                     m2 = __builtin_amdgcn_alignbit(m2, mf_drop(q2, rho), 31);
                     m3 = __builtin_amdgcn_alignbit(m3, mf_drop(q3, rho), 31);
                 };
-#if RT_MF_PINGPONG
                 // two operand sets in flight: group g + 2's fragment is loaded right after
                 // group g's MFMAs have read theirs, a whole group of work before its use.
                 // The loads are inline asm with explicit waits: written as plain loads, the
@@ -766,15 +649,6 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
                     fb = mf_load(fr + n3 * 64);
                 }
                 mf_wait0(fa, fb);  // the last (unused) loads land before their registers are reused
-#else
-                uint4 afn = frag[gi0 * 64 + lane];
-                for (int g = 0; g < G; ++g) {
-                    const uint4 af = afn;
-                    if (g + 1 < G) afn = frag[(gi0 + g + 1) * 64 + lane];  // the next group's operand ahead
-                    const mf_u32x4 v = {af.x, af.y, af.z, af.w};
-                    group(v);
-                }
-#endif
                 // lane (slot s, ray q) holds m_c for ray 16 c + q; after the transpose lane
                 // (c, q) holds the masks of slots 0..3 of its own ray: bit j of slot s's mask
                 // is triangle s G + j of the round
@@ -805,10 +679,11 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
                 Fw = use_ovr ? ((active && g < 4) ? ovr[g < 4 ? g : 0] : 0ull) : Fw;
             }
             if (COUNT) *n_cand += __builtin_popcountll(Fw);
-#if RT_MF_COOP
-#if RT_MF_FIRST_OWN
-            // the lane's first candidate on its own lane (its own ray, no pair list: every live
-            // lane has one, usually its hit), then the rest (≈ 0.3 per ray) shared by the wave
+            // With one 64-triangle block the lane's first candidate on its own lane (its own ray,
+            // no pair list: every live lane has one, usually its hit), then the rest (≈ 0.3 per
+            // ray) shared by the wave (Cornell 512^2 x 256: 3.92 vs 4.00 ms; on
+            // complex_light_room's four blocks it measured 314 vs 310 ms, so wider scenes share
+            // every pair: profiles/r3q/)
             if (NB == 1 && Fw != 0ull) {
                 const int b = __builtin_ctzll(Fw);
                 const float t = exact_tv<RULE>(s.isect, tri0 + b, o, nDx, nDy, nDz);
@@ -818,16 +693,7 @@ __device__ __forceinline__ Hit closest_hit_mf(const DeviceScene& s, f3 o, f3 d, 
                 }
                 Fw &= Fw - 1ull;
             }
-#endif
             mf_exact_wave<RULE>(s.isect, tri0, Fw, o, nDx, nDy, nDz, wl, lane, h);
-#else
-            uint64_t G = Fw;
-            while (G != 0ull) {
-                const int b = __builtin_ctzll(G);
-                G &= G - 1ull;
-                exact_one<RULE>(s.isect, tri0 + b, o, nDx, nDy, nDz, h);
-            }
-#endif
         }
     }
     return h;
@@ -963,9 +829,7 @@ __device__ __forceinline__ bool ctab_usable(const CtabDev& T, float t_scale) {
 // hit.  The lane's first RT_CTAB_OWN candidates on its own lane, the rest shared by the wave
 // (mf_exact_wave, per 64-triangle block).  Wave-level like closest_hit_mf (a lane without a ray:
 // F = 0).  closest_hit_ctab: F from the table T for a bounce ray leaving surface `surf`.
-#ifndef RT_CAND_MIN
-#define RT_CAND_MIN 1  // 0: RULE 1's shared exact phase folds as RULE 0's (per-lane list walks)
-#endif
+// RULE 1's shared exact phase folds by minimum (cand_exact_min) instead of per-lane list walks.
 #ifndef RT_CAND_OWN_MIN
 #define RT_CAND_OWN_MIN 0  // RT_CTAB_OWN of the min-fold phase (complex_light_room 512^2 x 64: 0 / 1 -> 50.9 / 66.8 ms)
 #endif
@@ -1059,7 +923,7 @@ __device__ __forceinline__ Hit closest_hit_cand(const DeviceScene& s, uint64_t (
     Hit h;
     h.t = (RULE == 0) ? FLT_MAX : 999999.0f;
     h.tri = -1;
-    constexpr bool kMin = RULE == 1 && RT_CAND_MIN;
+    constexpr bool kMin = RULE == 1;
     // the lane's first candidates (in index order) on its own lane
 #pragma unroll
     for (int k = 0; k < (kMin ? RT_CAND_OWN_MIN : RT_CTAB_OWN); ++k) {
@@ -1112,13 +976,7 @@ __device__ __forceinline__ Hit closest_hit_ctab(const DeviceScene& s, const Ctab
 }
 // closest_hit_ctab in two halves (ctab_begin / ctab_finish): what the caller runs between them
 // covers the latency of the entry's loads.  Same hit as the unsplit cast.
-template <int NW>
-__device__ __forceinline__ CtabLook<NW> closest_hit_ctab_begin(const DeviceScene& s, const CtabDev& T, int surf, f3 o,
-                                                               f3 d, bool active) {
-    // (an inactive lane: surf -1 is off the table and loads nothing)
-    return ctab_begin<NW>(T, s.n_surf, active ? surf : -1, o, d);
-}
-// (an active lane's surface frame loaded by the caller, ctab_frame)
+// (an active lane's surface frame loaded by the caller, ctab_frame; an inactive lane loads nothing)
 template <int NW>
 __device__ __forceinline__ CtabLook<NW> closest_hit_ctab_begin(const CtabDev& T, const CtabFrame& R, f3 o, f3 d,
                                                                bool active) {
@@ -1139,41 +997,10 @@ __device__ __forceinline__ Hit closest_hit_ctab_finish(const DeviceScene& s, con
     return closest_hit_cand<RULE, NW, CAP>(s, F, o, d, t_scale, wl);
 }
 
-#ifndef RT_FILTER
-#define RT_FILTER 1  // 0: always the single-phase scan (A/B builds)
-#endif
-#ifndef RT_MF
-#define RT_MF 1  // 0: the bounce casts of k_render_ps on the fp32 filter (A/B builds)
-#endif
-#ifndef RT_PS_SCENE_LDS
-#define RT_PS_SCENE_LDS 1  // k_render_ps<MF>: the scene's isect/shade records in LDS (0: global)
-#endif
-#ifndef RT_PS_SHADE_LDS
-#define RT_PS_SHADE_LDS 1  // 0: with RT_PS_SCENE_LDS, only the isect records in LDS (shading from L1/L2)
-#endif
-#ifndef RT_PS_CT_DICT_LDS
-#define RT_PS_CT_DICT_LDS 0  // 1: the table route's grazing dictionary in LDS (when it has <= kPsCtDictLds words)
-#endif
-constexpr int kPsCtDictLds = 64;
-#ifndef RT_PS_CT_TRI_LDS
-#define RT_PS_CT_TRI_LDS 0  // 1: the table route's surface patch frames (CtabDev::tri) in LDS
-#endif
-#ifndef RT_PS_CT_SHADE_LDS
-// the table-route kernel's shading records: from L1/L2 (0) -- with the shorter pair list it keeps
-// the workgroup at 29.4 KB of LDS, five per CU (Cornell 512^2 x 256: 2.33 ms, in LDS 2.37-2.40;
-// the 35.6-KB layout of round 5 held four per CU: 2.63 ms, profiles/r6f/ab.log)
-#define RT_PS_CT_SHADE_LDS 0
-#endif
-#ifndef RT_MF_LDS
-#define RT_MF_LDS 0  // 1: k_render_ps reads the image from a workgroup copy in LDS (0: global)
-#endif
-
 template <int RULE>
 __device__ __forceinline__ Hit closest_hit_sel(const DeviceScene& s, int use_filter, f3 o, f3 d,
                                                float t_scale) {
-#if RT_FILTER
     if (use_filter) return closest_hit_filtered<RULE>(s.filt, s.isect, s.n_tri, o, d, t_scale);
-#endif
     return closest_hit<RULE>(s.isect, s.n_tri, o, d, t_scale);
 }
 

@@ -1,4 +1,4 @@
-"""k_render_ps's pipelined bounce loop (rt_kernels.hip: ps_body under RT_PS_PIPE): with the
+"""k_render_ps's pipelined bounce loop (rt_kernels.hip: the first loop of ps_body): with the
 pooled trip, a sample whose cast hit a surface with one bounce left is kept by its lane as
 pending, and its light pre-test runs in the lane's next trip, between the issue of the next
 sample's table lookup and the first use of the loaded words -- or, once the wave's queue has
@@ -8,7 +8,12 @@ The yardstick is test_ps_pool.py's: Cornell, CPU preset, t_scale 256, the table 
 the uint32 view of the image and the ray casts against the CPU restatement (oracle.render).
 The shapes are the smallest at which the new order can go wrong: one trip and then the drain;
 several trips with pending samples carried across claims; a wave whose queue is empty.
+
+The table route's other loop (ps_body's second) with bounces left runs when the pre-test is off:
+Cornell with its light quad cut into more triangles than the pre-test takes.
 """
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -82,6 +87,46 @@ def test_max_bounces(rtmi_mod, oracle_mod, gpu_ctx, cornell, max_bounces, spp, s
     """per_chunk 1 and 10.  At max_bounces 0 and 1 nothing is ever pending (0: the pre-test is
     off and the old loop runs; 1: a surface hit ends the path with 0 on the spot)."""
     _check(rtmi_mod, oracle_mod, gpu_ctx, cornell, width=32, height=16, spp=spp, spp_split=split,
+           max_bounces=max_bounces)
+
+
+def many_lights_geometry(g):
+    """g with its light quad (two triangles) cut into nine coplanar triangles that cover the same
+    quad, same emission and light group: each triangle into four at its edges' midpoints (the
+    orientation kept), the last of the eight halved once more."""
+    assert g.n_light == 2 and np.array_equal(g.emission[0], g.emission[1]) and g.light_group[0] == g.light_group[1]
+    half = np.float32(0.5)
+    parts = []
+    for t in g.light:
+        a, b, c = t[0:3], t[3:6], t[6:9]
+        ab, bc, ca = (a + b) * half, (b + c) * half, (c + a) * half
+        parts += [(a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca)]
+    p, q, r = parts.pop()
+    m = (p + q) * half
+    parts += [(p, m, r), (m, q, r)]
+    light = np.stack([np.concatenate(t) for t in parts]).astype(np.float32)
+    n = light.shape[0]
+    return dataclasses.replace(g, light=light, emission=np.repeat(g.emission[:1], n, axis=0),
+                               light_group=np.repeat(g.light_group[:1], n))
+
+
+@pytest.fixture(scope="module")
+def many_lights(rtmi_mod, gpu_ctx):
+    g = many_lights_geometry(rtmi_mod.cornell_geometry(rtmi_mod.RT_PRESET_CPU))
+    with rtmi_mod.Scene(gpu_ctx, g) as sc:
+        yield g, sc
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("max_bounces", [1, 2])
+@pytest.mark.parametrize("spp,split", [(4, 4), (40, 4)])
+def test_general_loop_on_table_route(rtmi_mod, oracle_mod, gpu_ctx, many_lights, max_bounces, spp, split):
+    """Nine light triangles: more than the light pre-test takes (kPsSplitLights 8), so the
+    table-route kernel runs its general loop with bounces left -- shading at depth 1, the folds
+    through both bounces, nothing deferred and an empty pooled trip.  per_chunk 1 and 10."""
+    g, _ = many_lights
+    assert g.n_light == 9 and g.n_tri <= 64
+    _check(rtmi_mod, oracle_mod, gpu_ctx, many_lights, width=32, height=16, spp=spp, spp_split=split,
            max_bounces=max_bounces)
 
 
