@@ -344,6 +344,76 @@ int rt_dqn_td_targets_device(rt_ctx* ctx, uint64_t seed, const float* d_next_q, 
                              const float* d_reward, const float* d_discount, const uint32_t* d_pix, int sample,
                              int bounce, int n, float* d_target, void* stream);
 
+/* ---- Q-network fit to a radiance map (the reference's NN_Q_Value_Trainer) ----
+ * The supervised stage between rt_sarsa_save_q and rt_render_dqn
+ * (NN_Q_Value_Trainer/Source/main.cu:118-294): the network is fitted to the rows
+ * "position -> all Q values" of a trained radiance map, squared distance over every output,
+ * Adam, batches of 128 rows, 100 epochs, an 80/20 train/test split with the test error per
+ * epoch.  It runs on an rt_dqn_trainer, so a fitted network can go on into rt_neuralq_create
+ * or, through rt_dqn_trainer_params, into rt_dqn_create / rt_dynet_write.  DyNet is not
+ * available: parity is against the fp64 restatement, unpinned against DyNet itself.
+ *
+ * rt_dqn_fit_order: the split and the shuffle (main.cu:126 std::random_shuffle, :147-156
+ *   rand() / RAND_MAX < 0.8), host only, with Philox in place of rand().  Row i draws the
+ *   Philox4x32-10 block of key (seed lo, seed hi) and counter (i, 0, 0, RT_DQN_FIT_TAG): word 3
+ *   is 0 in every render draw and 0x566F726F in the Voronoi palette, so the stream is apart
+ *   from both.  u = (w0 >> 8) 2^-24; the row trains if u < train_fraction (compared in float),
+ *   else it is a test row.  order: the training rows, then the test rows, each set ascending
+ *   in (w1, i) -- a random permutation, ties broken by the index.  train_fraction in (0, 1]
+ *   (the reference: 0.8); n >= 0. */
+#define RT_DQN_FIT_TAG 0x51466974u /* "QFit" */
+int rt_dqn_fit_order(uint64_t seed, int32_t n, float train_fraction, int32_t* order /* n */, int32_t* n_train);
+/* One update of main.cu:192-238 on n rows: forward on the positions (network input
+ * nn_vertices - loc, main.cu:25-36), loss = sum_b sum_a (target - q)^2
+ * (sum_batches(squared_distance)), backward, trainer.update().  The output gradient is
+ * q > 0 ? -2 (target - q) : 0 for every element: a dead output counts in the loss and passes
+ * no gradient, as in rt_dqn_train_step_device.  Device arrays: d_loc n x 3, d_target n x n_out
+ * (row-major; any 4-byte alignment: the result does not depend on it).  Otherwise as
+ * rt_dqn_train_step_device: asynchronous on `stream`, either out pointer synchronises, the loss
+ * and the gradient norm before clipping; the trainer's update count advances, so fit steps and
+ * Neural-Q steps on one trainer share Adam's time. */
+int rt_dqn_fit_step_device(rt_ctx* ctx, rt_dqn_trainer* trainer, const float* d_loc /* n x 3 */,
+                           const float* d_target /* n x n_out */, int n, float* loss_out, float* grad_norm_out,
+                           void* stream);
+/* The middle of that step alone, on the caller's device arrays (for measurement and checks):
+ * the loss sum (target - q)^2 over d_q and d_target (n x n_out each) and the output gradient
+ * into d_dq (n x n_out, every element written).  Nothing of the trainer but its reduction
+ * scratch is touched.  loss_out (host, optional) synchronises the stream. */
+int rt_dqn_fit_loss_device(rt_ctx* ctx, rt_dqn_trainer* trainer, const float* d_q, const float* d_target, int n,
+                           float* d_dq, float* loss_out, void* stream);
+/* The test loop of main.cu:241-277: sum_b ||target_b - Q(loc_b)||^2 with no update.  The
+ * forward runs in chunks of RT_DQN_FIT_ERROR_CHUNK rows, so the trainer's workspace does not
+ * grow with n.  Each difference is the fp32 target - q; its square and every sum are double,
+ * in an order that depends on n and n_out alone: bit-identical run to run.  Parameters,
+ * moments, gradients and the update count are untouched.  n = 0 gives 0.  error_out (host,
+ * required) synchronises the stream. */
+#define RT_DQN_FIT_ERROR_CHUNK 4096
+int rt_dqn_fit_error_device(rt_ctx* ctx, rt_dqn_trainer* trainer, const float* d_loc, const float* d_target,
+                            int n, double* error_out, void* stream);
+/* The data set of a fit: the reference's radiance_map_data (host arrays pos n x 3, q n x
+ * n_actions, e.g. rt_qtable_read's or rt_sarsa_volumes' + rt_sarsa_read's), uploaded once in
+ * the order of rt_dqn_fit_order(seed, n, train_fraction): every batch and the test set are
+ * contiguous device slices.  The trainer is borrowed (as rt_neuralq_create borrows it) and
+ * must outlive the fit.  RT_E_INVALID: n_actions differs from the trainer's output width,
+ * batch_size <= 0, n <= 0, a value that is not finite (an in-frame RT_SARSA_SAMPLE_MAX map can
+ * hold infinities), or a split that leaves no training row.  An empty test set is allowed
+ * (its error is 0). */
+typedef struct rt_dqn_fit rt_dqn_fit;
+int rt_dqn_fit_create(rt_ctx* ctx, rt_dqn_trainer* trainer, const float* pos, const float* q, int32_t n,
+                      int32_t n_actions, uint64_t seed, float train_fraction, int32_t batch_size,
+                      rt_dqn_fit** out);
+int rt_dqn_fit_destroy(rt_dqn_fit* fit);
+/* n_batches = ceil(n_train / batch_size); any pointer may be NULL */
+int rt_dqn_fit_info(const rt_dqn_fit* fit, int32_t* n_train, int32_t* n_test, int32_t* n_batches,
+                    int32_t* epochs_done);
+/* One pass of main.cu:186-284: rt_dqn_fit_step_device on the n_batches batches in order (the
+ * last one ragged), then rt_dqn_fit_error_device on the test rows under the updated
+ * parameters.  Nothing waits for the device between batches; the steps' float losses are
+ * added on the device in double, in batch order; the call synchronises once, at its end.
+ * loss_out / error_out (host, each may be NULL): the reference's printed "Loss:" and
+ * "Error:". */
+int rt_dqn_fit_epoch(rt_ctx* ctx, rt_dqn_fit* fit, double* loss_out, double* error_out, void* stream);
+
 /* NeuralQPathtracer (GPU/deep_learning/neural_q_pathtracer.cu:226-600): renders while
  * training `trainer`'s network, on the device.  Per sample: initialise_ray (:604-643); per
  * bounce b until no path is bouncing or max_bounces: (b > 0) the network's Q at every ray's
@@ -461,6 +531,17 @@ int rt_sarsa_save_q(const rt_sarsa* sarsa, const char* path);
  * radiance_volume.cu:377-440); this resumes training or renders from a saved map.
  * save_q -> load_q -> save_q reproduces the file byte for byte. */
 int rt_sarsa_load_q(rt_sarsa* sarsa, const char* path);
+/* The same file without a map: load_radiance_map_data (NN_Q_Value_Trainer/Source/main.cu:73-116),
+ * the input of the Q-network fit (rt_dqn_fit_create).  First line: the action count; then one
+ * line "x y z Q0 .. Q(A-1)" per row; every value is strtof of its printed token (std::stof).
+ * Host only.  Two passes, like rt_dynet_read: with pos and q NULL the call sizes (*n_rows,
+ * *n_actions out); with both given, *n_rows and *n_actions hold on entry the sizes the arrays
+ * were allocated for (the sizing pass's) and the file must still have them.  pos: n_rows x 3,
+ * q: n_rows x n_actions.  Lines of blanks are skipped.  A missing file, a row with too few or
+ * too many tokens, a token that is not a number, or an action count <= 0 returns RT_E_IO
+ * with the line's number in the message.  rt_sarsa_load_q reads through the same parser. */
+int rt_qtable_read(const char* path, int32_t* n_rows, int32_t* n_actions, float* pos /* n x 3 */,
+                   float* q /* n x n_actions */);
 int rt_sarsa_save_selected(rt_ctx* ctx, const rt_sarsa* sarsa, const char* to_select_path,
                            const char* out_path);
 int rt_sarsa_search_stats(const rt_sarsa* sarsa, int32_t* mode, int32_t* n_classes, int64_t* grid_cells,

@@ -520,6 +520,66 @@ int view_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const 
     return RT_OK;
 }
 
+// The rt_sarsa_save_q / RadianceMap::save_q_vals_to_file format (radiance_map.cu:236-266), read
+// as load_radiance_map_data reads it (NN_Q_Value_Trainer/Source/main.cu:73-116): line 1 the
+// action count, then "x y z Q0 .. Q(A-1)" per line, each value strtof of its whole token
+// (std::stof).  Lines of blanks are skipped.  pos (rows x 3) and q (rows x actions) may be
+// NULL: the rows are then only checked and counted.  RT_E_IO names the line.  The one parser
+// of this format: rt_sarsa_load_q and rt_qtable_read.
+int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<float>* pos, std::vector<float>* q) {
+    std::ifstream in(path);
+    if (!in.is_open()) return err(RT_E_IO, std::string("cannot open ") + path);
+    auto bad = [&](int line, const std::string& what) {
+        return err(RT_E_IO, std::string(path) + ": line " + std::to_string(line) + ": " + what);
+    };
+    const char* blanks = " \t\r\n\v\f";
+    std::string line, tok;
+    int line_no = 0, actions = 0, rows = 0;
+    bool have_header = false;
+    while (std::getline(in, line)) {
+        ++line_no;
+        size_t at = line.find_first_not_of(blanks);
+        if (at == std::string::npos) continue;
+        int count = 0;
+        while (at != std::string::npos) {
+            const size_t end = line.find_first_of(blanks, at);
+            tok.assign(line, at, end == std::string::npos ? std::string::npos : end - at);
+            at = end == std::string::npos ? end : line.find_first_not_of(blanks, end);
+            char* stop = nullptr;
+            if (!have_header) {
+                const long a = strtol(tok.c_str(), &stop, 10);
+                if (stop == tok.c_str() || *stop != '\0' || at != std::string::npos)
+                    return bad(line_no, "the first line must be the action count");
+                if (a <= 0 || a > (1 << 20)) return bad(line_no, "the action count must be positive");
+                actions = (int)a;
+                continue;
+            }
+            const float v = strtof(tok.c_str(), &stop);
+            if (stop == tok.c_str() || *stop != '\0') return bad(line_no, "'" + tok + "' is not a number");
+            if (count >= 3 + actions)
+                return bad(line_no, "more than 3 + " + std::to_string(actions) + " values in the row");
+            if (count < 3) {
+                if (pos) pos->push_back(v);
+            } else if (q) {
+                q->push_back(v);
+            }
+            ++count;
+        }
+        if (!have_header) {
+            have_header = true;
+            continue;
+        }
+        if (count != 3 + actions)
+            return bad(line_no, std::to_string(count) + " values in the row, expected 3 + " + std::to_string(actions));
+        if (rows == INT32_MAX) return bad(line_no, "too many rows");
+        ++rows;
+    }
+    if (!have_header) return bad(1, "the first line must be the action count");
+    *n_rows = rows;
+    *n_actions = actions;
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -908,39 +968,22 @@ int rt_sarsa_save_q(const rt_sarsa* sa, const char* path) {
 int rt_sarsa_load_q(rt_sarsa* sa, const char* path) {
     if (!sa || !path) return err(RT_E_INVALID, "NULL argument");
     const int S = rt::kSarsaSectors;
-    FILE* f = fopen(path, "r");
-    if (!f) return err(RT_E_IO, std::string("cannot open ") + path);
-    std::vector<float> q((size_t)sa->n_vol * S);
-    int rc = RT_OK;
-    int actions = 0;
-    if (fscanf(f, "%d", &actions) != 1 || actions != S) rc = err(RT_E_IO, "first line must be the action count 144");
-    char tok[64];
-    auto next = [&](float* v) {  // std::stof semantics
-        if (fscanf(f, "%63s", tok) != 1) return false;
-        char* end = nullptr;
-        *v = strtof(tok, &end);
-        return end != tok && *end == '\0';
-    };
-    for (int i = 0; rc == RT_OK && i < sa->n_vol; ++i) {
-        for (int c = 0; c < 3 && rc == RT_OK; ++c) {
-            float v;
-            if (!next(&v)) {
-                rc = err(RT_E_IO, "truncated or malformed Q-table file");
-                break;
-            }
+    std::vector<float> fpos, q;
+    int rows = 0, actions = 0;
+    int rc = parse_q_table(path, &rows, &actions, &fpos, &q);
+    if (rc != RT_OK) return rc;
+    if (actions != S) return err(RT_E_IO, "first line must be the action count 144");
+    if (rows < sa->n_vol) return err(RT_E_IO, "truncated Q-table file: fewer volumes than in the map");
+    if (rows > sa->n_vol) return err(RT_E_INVALID, "more volumes in the file than in the map");
+    for (int i = 0; i < sa->n_vol; ++i)
+        for (int c = 0; c < 3; ++c) {
             // the position must be this map's volume i as save_q prints it
             std::ostringstream os;
             os << sa->pos[4 * i + c];
-            if (strtof(os.str().c_str(), nullptr) != v)
-                rc = err(RT_E_INVALID, "volume " + std::to_string(i) + ": position differs from this map's "
-                                       "(another scene or seed)");
+            if (strtof(os.str().c_str(), nullptr) != fpos[(size_t)3 * i + c])
+                return err(RT_E_INVALID, "volume " + std::to_string(i) + ": position differs from this map's "
+                                         "(another scene or seed)");
         }
-        for (int k = 0; k < S && rc == RT_OK; ++k)
-            if (!next(&q[(size_t)i * S + k])) rc = err(RT_E_IO, "truncated or malformed Q-table file");
-    }
-    if (rc == RT_OK && fscanf(f, "%63s", tok) == 1) rc = err(RT_E_INVALID, "more volumes in the file than in the map");
-    fclose(f);
-    if (rc != RT_OK) return rc;
     std::vector<float> accum(sa->n_vol);
     for (int i = 0; i < sa->n_vol; ++i)
         accum[i] = initial_irradiance(&sa->cos_center[(size_t)i * S], &q[(size_t)i * S], sa->lum[i]);
@@ -950,6 +993,27 @@ int rt_sarsa_load_q(rt_sarsa* sa, const char* path) {
     RT_HIPE(hipMemcpy(sa->m.accum, accum.data(), sizeof(float) * accum.size(), hipMemcpyHostToDevice));
     RT_HIPE(rt::launch_sarsa_rebuild(sa->m, 0));
     RT_HIPE(hipDeviceSynchronize());
+    return RT_OK;
+}
+
+int rt_qtable_read(const char* path, int32_t* n_rows, int32_t* n_actions, float* pos, float* q) {
+    if (!path || !n_rows || !n_actions) return err(RT_E_INVALID, "NULL argument");
+    if ((pos == nullptr) != (q == nullptr)) return err(RT_E_INVALID, "pos and q must both be given or both be NULL");
+    int rows = 0, actions = 0;
+    if (!pos) {
+        const int rc = parse_q_table(path, &rows, &actions, nullptr, nullptr);
+        if (rc != RT_OK) return rc;
+        *n_rows = rows;
+        *n_actions = actions;
+        return RT_OK;
+    }
+    std::vector<float> fpos, fq;
+    const int rc = parse_q_table(path, &rows, &actions, &fpos, &fq);
+    if (rc != RT_OK) return rc;
+    if (rows != *n_rows || actions != *n_actions)
+        return err(RT_E_IO, std::string(path) + ": the table's size differs from the sizing pass's");
+    if (!fpos.empty()) memcpy(pos, fpos.data(), sizeof(float) * fpos.size());
+    if (!fq.empty()) memcpy(q, fq.data(), sizeof(float) * fq.size());
     return RT_OK;
 }
 

@@ -25,6 +25,12 @@
 // reductions (loss, gradient norm) go through per-block partials summed in a fixed
 // order (deterministic).  The inference network (rt_dqn, bf16 MFMA) is rebuilt from
 // rt_dqn_trainer_params when the caller wants to render with the trained weights.
+//
+// The same trainer also runs the reference's supervised stage, NN_Q_Value_Trainer
+// (NN_Q_Value_Trainer/Source/main.cu:118-294): the network fitted to a radiance map's Q-table,
+// squared distance over all outputs (k_fit_loss_grad between the shared forward and the shared
+// backward + clip + Adam), a held-out error (k_fit_sqdist) and an epoch driver that never waits
+// for the device between batches (rt_dqn_fit_*, at the end of this file).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
@@ -288,6 +294,112 @@ __global__ __launch_bounds__(256) void k_loss_grad(const float* __restrict__ q, 
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
+// The supervised fit's loss (NN_Q_Value_Trainer/Source/main.cu:234, sum_batches(
+// squared_distance(targets, output))) and its output gradient: every element of the n x n_out
+// matrix, dq = q > 0 ? -2 (target - q) : 0 -- a dead output counts in the loss and passes no
+// gradient, as in k_loss_grad.  Pure streaming, two reads and one write per element: the flat
+// matrix is cut into quads of 4 consecutive elements, thread g of the grid takes quads g,
+// g + threads, .. and adds their squares in element order.  VEC: 16-byte loads and stores (the
+// length a multiple of 4 and the three bases 16-byte aligned; n_out = 144); otherwise one
+// element at a time -- the same quads, the same sums, so the result does not depend on the
+// path.  Every element below `total` is written, so dq needs no memset.  Per-block partial
+// sums in the file's fixed tree (summed in a fixed order by k_finalize).
+constexpr int kFitBlocks = 1024;  // 4 workgroups per CU of the MI355X's 256
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_fit_loss_grad(const float* __restrict__ q,
+                                                       const float* __restrict__ target, size_t total,
+                                                       float* __restrict__ dq, float* __restrict__ partial) {
+    __shared__ float red[256];
+    const size_t quads = (total + 3) / 4;
+    float s = 0.0f;
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < quads; k += (size_t)gridDim.x * 256) {
+        const size_t i = 4 * k;
+        if (VEC) {
+            const float4 qv = *reinterpret_cast<const float4*>(q + i);
+            const float4 tv = *reinterpret_cast<const float4*>(target + i);
+            const float d0 = tv.x - qv.x, d1 = tv.y - qv.y, d2 = tv.z - qv.z, d3 = tv.w - qv.w;
+            s += d0 * d0;
+            s += d1 * d1;
+            s += d2 * d2;
+            s += d3 * d3;
+            float4 g;
+            g.x = qv.x > 0.0f ? -2.0f * d0 : 0.0f;
+            g.y = qv.y > 0.0f ? -2.0f * d1 : 0.0f;
+            g.z = qv.z > 0.0f ? -2.0f * d2 : 0.0f;
+            g.w = qv.w > 0.0f ? -2.0f * d3 : 0.0f;
+            *reinterpret_cast<float4*>(dq + i) = g;
+        } else {
+            const size_t e = i + 4 < total ? i + 4 : total;
+            for (size_t j = i; j < e; ++j) {
+                const float qa = q[j];
+                const float diff = target[j] - qa;
+                s += diff * diff;
+                dq[j] = qa > 0.0f ? -2.0f * diff : 0.0f;
+            }
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// The test loop's error (main.cu:274-276, squared_distance summed over the test rows): the
+// same quads without dq.  Each difference is the fp32 target - q, its square and every sum
+// double.  The grid is kErrBlocks for every chunk of rows; block b adds its tree sum to
+// acc[b] (first: sets it), so a chunk sequence accumulates in chunk order without atomics.
+constexpr int kErrBlocks = 256;
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_fit_sqdist(const float* __restrict__ q, const float* __restrict__ target,
+                                                    size_t total, int first, double* __restrict__ acc) {
+    __shared__ double red[256];
+    const size_t quads = (total + 3) / 4;
+    double s = 0.0;
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < quads; k += (size_t)gridDim.x * 256) {
+        const size_t i = 4 * k;
+        if (VEC) {
+            const float4 qv = *reinterpret_cast<const float4*>(q + i);
+            const float4 tv = *reinterpret_cast<const float4*>(target + i);
+            const double d0 = (double)(tv.x - qv.x), d1 = (double)(tv.y - qv.y);
+            const double d2 = (double)(tv.z - qv.z), d3 = (double)(tv.w - qv.w);
+            s += d0 * d0;
+            s += d1 * d1;
+            s += d2 * d2;
+            s += d3 * d3;
+        } else {
+            const size_t e = i + 4 < total ? i + 4 : total;
+            for (size_t j = i; j < e; ++j) {
+                const double d = (double)(target[j] - q[j]);
+                s += d * d;
+            }
+        }
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) acc[blockIdx.x] = first ? red[0] : acc[blockIdx.x] + red[0];
+}
+
+// out[0] = acc[0] + .. + acc[n - 1]: one wave, lane l sums l, l + 64, .. in order, then the
+// fixed xor-shuffle tree (n = 0: the error of an empty test set, 0)
+__global__ __launch_bounds__(64) void k_fit_sqdist_final(const double* __restrict__ acc, int n,
+                                                         double* __restrict__ out) {
+    const int lane = threadIdx.x;
+    double s = 0.0;
+    for (int i = lane; i < n; i += 64) s += acc[i];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (lane == 0) out[0] = s;
+}
+
 // bias gradient: column sums of the layer's output gradient.  Stage 1: chunk y of the
 // rows per column -> part[y][c], its 4 row groups (rows = rg mod 4) combined in a fixed
 // order; stage 2 (k_sum_slices): the chunks in order.
@@ -480,6 +592,7 @@ struct rt_dqn_trainer {
     float *part_loss = nullptr, *part_g = nullptr, *scal = nullptr;
     float* slices = nullptr;  // split-K partial products of the weight gradients
     size_t slice_cap = 0;
+    double* err_acc = nullptr;  // rt_dqn_fit_error_device: kErrBlocks block sums + the total
     void free_ws() {
         for (float* p : {H[0], H[1], H[2], H[3], D[0], D[1], part_loss, slices}) (void)hipFree(p);
         (void)hipFree(part4);
@@ -494,6 +607,7 @@ struct rt_dqn_trainer {
         free_ws();
         for (float* p : {P, G, Mo, Vo, verts, part_g, scal}) (void)hipFree(p);
         (void)hipFree(fold);
+        (void)hipFree(err_acc);
     }
 };
 
@@ -519,7 +633,8 @@ int ensure_ws(rt_dqn_trainer* t, int n) {
     RT_HIPE(hipMalloc(&t->part4, sizeof(double4) * (size_t)kColChunks * t->dims[1]));
     for (int l = 0; l < 4; ++l) RT_HIPE(hipMalloc(&t->H[l], sizeof(float) * (size_t)cap * t->dims[l + 1]));
     for (int k = 0; k < 2; ++k) RT_HIPE(hipMalloc(&t->D[k], sizeof(float) * (size_t)cap * widest));
-    RT_HIPE(hipMalloc(&t->part_loss, sizeof(float) * (size_t)(cap / 256)));
+    // one partial per 256 rays (k_loss_grad) or per workgroup of the dense loss (k_fit_loss_grad)
+    RT_HIPE(hipMalloc(&t->part_loss, sizeof(float) * (size_t)std::max(cap / 256, kFitBlocks)));
     size_t sl = 0;
     for (int l = 1; l < 4; ++l) {
         const int s = split_for(t->dims[l + 1], t->dims[l], cap);
@@ -643,18 +758,11 @@ int trainer_forward(rt_dqn_trainer* t, const float* d_loc, int n, hipStream_t st
     return RT_OK;
 }
 
-// steps 5-7 of the learning rule on n rays (forward, loss, backward, clipping, Adam)
-int trainer_step(rt_dqn_trainer* t, const float* d_loc, const int32_t* d_action, const float* d_target, int n,
-                 hipStream_t st) {
-    int rc = trainer_forward(t, d_loc, n, st);
-    if (rc != RT_OK) return rc;
+// The rest of a step once the output gradient (D[0], n x n_out) and the loss' n_loss_part
+// block partials (part_loss) are written: backward, clipping, Adam.  Shared by the
+// picked-action step (trainer_step) and the dense one (trainer_fit_step).
+int trainer_backward_update(rt_dqn_trainer* t, const float* d_loc, int n, int n_loss_part, hipStream_t st) {
     const int* d = t->dims;
-    // loss and the output-layer gradient
-    RT_HIPE(hipMemsetAsync(t->D[0], 0, sizeof(float) * (size_t)n * d[4], st));
-    const unsigned nb = blocks_for((size_t)n);
-    hipLaunchKernelGGL(k_loss_grad, dim3(nb), dim3(256), 0, st, t->H[3], d[4], d_action, d_target, n, t->D[0],
-                       t->part_loss);
-    RT_HIPE(hipGetLastError());
     // backward: dW_l = dH_l^T H_{l-1}, db_l = column sums, dH_{l-1} = (dH_l W_l) * [H_{l-1} > 0]
     int cur = 0;
     // chunks of >= 64 rows, at most kColChunks of them (measured: 4096 rays -> 64 chunks,
@@ -696,8 +804,8 @@ int trainer_step(rt_dqn_trainer* t, const float* d_loc, const int32_t* d_action,
     // clipping scale and Adam
     hipLaunchKernelGGL(k_sumsq, dim3(kRedBlocks), dim3(256), 0, st, t->G, t->n_par, t->part_g);
     RT_HIPE(hipGetLastError());
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, st, t->part_loss, (int)nb, t->part_g, kRedBlocks, t->clip,
-                       t->scal);
+    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, st, t->part_loss, n_loss_part, t->part_g, kRedBlocks,
+                       t->clip, t->scal);
     RT_HIPE(hipGetLastError());
     const double u = (double)(t->updates + 1);
     const float lr_t = (float)((double)t->lr * sqrt(1.0 - pow((double)t->b2, u)) / (1.0 - pow((double)t->b1, u)));
@@ -705,6 +813,82 @@ int trainer_step(rt_dqn_trainer* t, const float* d_loc, const int32_t* d_action,
                        t->scal, t->b1, t->b2, t->eps, lr_t);
     RT_HIPE(hipGetLastError());
     t->updates++;
+    return RT_OK;
+}
+
+// steps 5-7 of the learning rule on n rays (forward, loss, backward, clipping, Adam)
+int trainer_step(rt_dqn_trainer* t, const float* d_loc, const int32_t* d_action, const float* d_target, int n,
+                 hipStream_t st) {
+    int rc = trainer_forward(t, d_loc, n, st);
+    if (rc != RT_OK) return rc;
+    const int* d = t->dims;
+    // loss and the output-layer gradient
+    RT_HIPE(hipMemsetAsync(t->D[0], 0, sizeof(float) * (size_t)n * d[4], st));
+    const unsigned nb = blocks_for((size_t)n);
+    hipLaunchKernelGGL(k_loss_grad, dim3(nb), dim3(256), 0, st, t->H[3], d[4], d_action, d_target, n, t->D[0],
+                       t->part_loss);
+    RT_HIPE(hipGetLastError());
+    return trainer_backward_update(t, d_loc, n, (int)nb, st);
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// grid of the two streaming kernels over `total` elements: one thread per quad, at most
+// `most` workgroups (the threads then stride)
+unsigned fit_grid(size_t total, int most) {
+    return (unsigned)std::max<size_t>(1, std::min<size_t>((size_t)most, ((total + 3) / 4 + 255) / 256));
+}
+
+// k_fit_loss_grad over `total` elements: dq and *n_part (<= kFitBlocks, what ensure_ws sizes
+// part_loss for) block partials of the loss
+hipError_t launch_fit_loss_grad(rt_dqn_trainer* t, const float* q, const float* target, size_t total, float* dq,
+                                unsigned* n_part, hipStream_t st) {
+    const unsigned nb = fit_grid(total, kFitBlocks);
+    if (total % 4 == 0 && aligned16(q) && aligned16(target) && aligned16(dq))
+        hipLaunchKernelGGL(k_fit_loss_grad<true>, dim3(nb), dim3(256), 0, st, q, target, total, dq, t->part_loss);
+    else
+        hipLaunchKernelGGL(k_fit_loss_grad<false>, dim3(nb), dim3(256), 0, st, q, target, total, dq, t->part_loss);
+    *n_part = nb;
+    return hipGetLastError();
+}
+
+// one update of the supervised fit on n rows (main.cu:192-238): the dense loss over all
+// outputs between the shared forward and the shared backward + clip + Adam
+int trainer_fit_step(rt_dqn_trainer* t, const float* d_loc, const float* d_target, int n, hipStream_t st) {
+    int rc = trainer_forward(t, d_loc, n, st);
+    if (rc != RT_OK) return rc;
+    unsigned nb = 0;
+    RT_HIPE(launch_fit_loss_grad(t, t->H[3], d_target, (size_t)n * t->dims[4], t->D[0], &nb, st));
+    return trainer_backward_update(t, d_loc, n, (int)nb, st);
+}
+
+// sum_b ||target_b - Q(loc_b)||^2 over n rows into t->err_acc[kErrBlocks] (device), forward in
+// chunks of RT_DQN_FIT_ERROR_CHUNK rows; the workspace must hold min(n, chunk) rows and
+// err_acc exist (ensure_err_acc: allocated before anything is queued, not between launches)
+int ensure_err_acc(rt_dqn_trainer* t) {
+    if (!t->err_acc) RT_HIPE(hipMalloc(&t->err_acc, sizeof(double) * (kErrBlocks + 1)));
+    return RT_OK;
+}
+
+int trainer_fit_error(rt_dqn_trainer* t, const float* d_loc, const float* d_target, int n, hipStream_t st) {
+    const int n_out = t->dims[4];
+    for (int r0 = 0; r0 < n; r0 += RT_DQN_FIT_ERROR_CHUNK) {
+        const int nr = std::min(RT_DQN_FIT_ERROR_CHUNK, n - r0);
+        int rc = trainer_forward(t, d_loc + (size_t)3 * r0, nr, st);
+        if (rc != RT_OK) return rc;
+        const float* tg = d_target + (size_t)r0 * n_out;
+        const size_t total = (size_t)nr * n_out;
+        if (total % 4 == 0 && aligned16(t->H[3]) && aligned16(tg))
+            hipLaunchKernelGGL(k_fit_sqdist<true>, dim3(kErrBlocks), dim3(256), 0, st, t->H[3], tg, total,
+                               r0 == 0 ? 1 : 0, t->err_acc);
+        else
+            hipLaunchKernelGGL(k_fit_sqdist<false>, dim3(kErrBlocks), dim3(256), 0, st, t->H[3], tg, total,
+                               r0 == 0 ? 1 : 0, t->err_acc);
+        RT_HIPE(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_fit_sqdist_final, dim3(1), dim3(64), 0, st, t->err_acc, n > 0 ? kErrBlocks : 0,
+                       t->err_acc + kErrBlocks);
+    RT_HIPE(hipGetLastError());
     return RT_OK;
 }
 
@@ -981,6 +1165,205 @@ int rt_neuralq_render_frame(rt_ctx* ctx, rt_neuralq* q, const rt_camera* cam, co
     RT_HIPE(hipMemcpyAsync(&casts, r.stats + 2, sizeof(casts), hipMemcpyDeviceToHost, st));
     RT_HIPE(hipStreamSynchronize(st));
     if (out_ray_casts) *out_ray_casts = casts;
+    return RT_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// The Q-network fit: NN_Q_Value_Trainer (NN_Q_Value_Trainer/Source/main.cu:118-294), the
+// stage between a saved Q-table and a network to render from.  The data set lives on the
+// device in the order of rt_dqn_fit_order -- training rows, then test rows -- so every batch
+// and the test set are contiguous slices and the epoch reads no index; the epoch's launches
+// (about 25 per step at the reference's batch of 128: launch-bound, unfused) are queued
+// without a host wait, k_fold0 per step because the parameters change under it.
+// ---------------------------------------------------------------------------
+struct rt_dqn_fit {
+    int device = 0;
+    rt_dqn_trainer* tr = nullptr;  // borrowed
+    int n_train = 0, n_test = 0, batch = 128, n_out = 0, epochs = 0;
+    float *pos = nullptr, *q = nullptr;  // n x 3, n x n_out, in fit order
+    double* loss_acc = nullptr;
+    ~rt_dqn_fit() {
+        (void)hipSetDevice(device);
+        (void)hipFree(pos);
+        (void)hipFree(q);
+        (void)hipFree(loss_acc);
+    }
+};
+
+extern "C" {
+
+int rt_dqn_fit_order(uint64_t seed, int32_t n, float train_fraction, int32_t* order, int32_t* n_train) {
+    if (!n_train || (n > 0 && !order)) return err(RT_E_INVALID, "NULL argument");
+    if (n < 0) return err(RT_E_INVALID, "n < 0");
+    if (!(train_fraction > 0.0f && train_fraction <= 1.0f)) return err(RT_E_INVALID, "train_fraction must lie in (0, 1]");
+    std::vector<uint32_t> key((size_t)n);
+    std::vector<int32_t> test;
+    int nt = 0;
+    for (int32_t i = 0; i < n; ++i) {
+        uint32_t w[4];
+        rt::philox4x32_10((uint32_t)i, 0u, 0u, RT_DQN_FIT_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+        key[(size_t)i] = w[1];
+        if (rt::u01(w[0]) < train_fraction) order[nt++] = i;
+        else test.push_back(i);
+    }
+    std::copy(test.begin(), test.end(), order + nt);
+    auto by_key = [&](int32_t a, int32_t b) { return key[(size_t)a] != key[(size_t)b] ? key[(size_t)a] < key[(size_t)b] : a < b; };
+    std::sort(order, order + nt, by_key);
+    std::sort(order + nt, order + n, by_key);
+    *n_train = nt;
+    return RT_OK;
+}
+
+int rt_dqn_fit_step_device(rt_ctx* ctx, rt_dqn_trainer* t, const float* d_loc, const float* d_target, int n,
+                           float* loss_out, float* grad_norm_out, void* stream) {
+    if (!ctx || !t || !d_loc || !d_target) return err(RT_E_INVALID, "NULL argument");
+    if (n <= 0) return err(RT_E_INVALID, "empty batch");
+    RT_HIPE(hipSetDevice(t->device));
+    int rc = ensure_ws(t, n);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = trainer_fit_step(t, d_loc, d_target, n, st);
+    if (rc != RT_OK) return rc;
+    if (loss_out || grad_norm_out) {
+        float h[4];
+        RT_HIPE(hipMemcpyAsync(h, t->scal, sizeof(h), hipMemcpyDeviceToHost, st));
+        RT_HIPE(hipStreamSynchronize(st));
+        if (loss_out) *loss_out = h[0];
+        if (grad_norm_out) *grad_norm_out = h[1];
+    }
+    return RT_OK;
+}
+
+int rt_dqn_fit_loss_device(rt_ctx* ctx, rt_dqn_trainer* t, const float* d_q, const float* d_target, int n,
+                           float* d_dq, float* loss_out, void* stream) {
+    if (!ctx || !t || !d_q || !d_target || !d_dq) return err(RT_E_INVALID, "NULL argument");
+    if (n <= 0) return err(RT_E_INVALID, "empty batch");
+    RT_HIPE(hipSetDevice(t->device));
+    int rc = ensure_ws(t, 1);  // (the block partials: sized for any n)
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned nb = 0;
+    RT_HIPE(launch_fit_loss_grad(t, d_q, d_target, (size_t)n * t->dims[4], d_dq, &nb, st));
+    if (loss_out) {
+        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, st, t->part_loss, (int)nb, t->part_g, 0, t->clip, t->scal);
+        RT_HIPE(hipGetLastError());
+        RT_HIPE(hipMemcpyAsync(loss_out, t->scal, sizeof(float), hipMemcpyDeviceToHost, st));
+        RT_HIPE(hipStreamSynchronize(st));
+    }
+    return RT_OK;
+}
+
+int rt_dqn_fit_error_device(rt_ctx* ctx, rt_dqn_trainer* t, const float* d_loc, const float* d_target, int n,
+                            double* error_out, void* stream) {
+    if (!ctx || !t || !error_out || (n > 0 && (!d_loc || !d_target))) return err(RT_E_INVALID, "NULL argument");
+    if (n < 0) return err(RT_E_INVALID, "n < 0");
+    *error_out = 0.0;
+    if (n == 0) return RT_OK;
+    RT_HIPE(hipSetDevice(t->device));
+    int rc = ensure_ws(t, std::min(n, RT_DQN_FIT_ERROR_CHUNK));
+    if (rc == RT_OK) rc = ensure_err_acc(t);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = trainer_fit_error(t, d_loc, d_target, n, st);
+    if (rc != RT_OK) return rc;
+    RT_HIPE(hipMemcpyAsync(error_out, t->err_acc + kErrBlocks, sizeof(double), hipMemcpyDeviceToHost, st));
+    RT_HIPE(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_dqn_fit_create(rt_ctx* ctx, rt_dqn_trainer* t, const float* pos, const float* q, int32_t n, int32_t n_actions,
+                      uint64_t seed, float train_fraction, int32_t batch_size, rt_dqn_fit** out) {
+    if (!ctx || !t || !pos || !q || !out) return err(RT_E_INVALID, "NULL argument");
+    *out = nullptr;
+    if (n <= 0) return err(RT_E_INVALID, "the data set is empty");
+    if (n_actions != t->dims[4])
+        return err(RT_E_INVALID, "the table has " + std::to_string(n_actions) + " actions, the network " +
+                                     std::to_string(t->dims[4]) + " outputs");
+    if (batch_size <= 0) return err(RT_E_INVALID, "batch_size must be positive");
+    if (t->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "trainer belongs to another device");
+    const size_t A = (size_t)n_actions;
+    for (size_t i = 0; i < (size_t)n * 3; ++i)
+        if (!std::isfinite(pos[i])) return err(RT_E_INVALID, "row " + std::to_string(i / 3) + ": position is not finite");
+    for (size_t i = 0; i < (size_t)n * A; ++i)
+        if (!std::isfinite(q[i])) return err(RT_E_INVALID, "row " + std::to_string(i / A) + ": a Q value is not finite");
+    std::vector<int32_t> order((size_t)n);
+    int32_t n_train = 0;
+    int rc = rt_dqn_fit_order(seed, n, train_fraction, order.data(), &n_train);
+    if (rc != RT_OK) return rc;
+    if (n_train == 0) return err(RT_E_INVALID, "the split leaves no training row");
+    std::vector<float> hp((size_t)n * 3), hq((size_t)n * A);
+    for (size_t r = 0; r < (size_t)n; ++r) {
+        memcpy(&hp[3 * r], pos + (size_t)3 * order[r], sizeof(float) * 3);
+        memcpy(&hq[A * r], q + A * (size_t)order[r], sizeof(float) * A);
+    }
+    RT_HIPE(hipSetDevice(t->device));
+    rt_dqn_fit* f = new (std::nothrow) rt_dqn_fit();
+    if (!f) return err(RT_E_NOMEM, "out of host memory");
+    f->device = t->device;
+    f->tr = t;
+    f->n_train = n_train;
+    f->n_test = n - n_train;
+    f->batch = batch_size;
+    f->n_out = n_actions;
+    hipError_t e = hipMalloc(&f->pos, sizeof(float) * hp.size());
+    if (e == hipSuccess) e = hipMalloc(&f->q, sizeof(float) * hq.size());
+    if (e == hipSuccess) e = hipMalloc(&f->loss_acc, sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(f->pos, hp.data(), sizeof(float) * hp.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(f->q, hq.data(), sizeof(float) * hq.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete f;
+        return err(RT_E_HIP, std::string("rt_dqn_fit_create: ") + hipGetErrorString(e));
+    }
+    *out = f;
+    return RT_OK;
+}
+
+int rt_dqn_fit_destroy(rt_dqn_fit* f) {
+    delete f;
+    return RT_OK;
+}
+
+int rt_dqn_fit_info(const rt_dqn_fit* f, int32_t* n_train, int32_t* n_test, int32_t* n_batches, int32_t* epochs_done) {
+    if (!f) return err(RT_E_INVALID, "NULL argument");
+    if (n_train) *n_train = f->n_train;
+    if (n_test) *n_test = f->n_test;
+    if (n_batches) *n_batches = (int32_t)(((int64_t)f->n_train + f->batch - 1) / f->batch);
+    if (epochs_done) *epochs_done = f->epochs;
+    return RT_OK;
+}
+
+int rt_dqn_fit_epoch(rt_ctx* ctx, rt_dqn_fit* f, double* loss_out, double* error_out, void* stream) {
+    if (!ctx || !f) return err(RT_E_INVALID, "NULL argument");
+    if (f->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "fit belongs to another device");
+    RT_HIPE(hipSetDevice(f->device));
+    rt_dqn_trainer* t = f->tr;
+    // the workspace once, for the largest launch of the epoch: nothing is reallocated (and
+    // nothing waits) between the batches
+    int rc = ensure_ws(t, std::max(std::min(f->batch, f->n_train), std::min(f->n_test, RT_DQN_FIT_ERROR_CHUNK)));
+    if (rc == RT_OK) rc = ensure_err_acc(t);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    RT_HIPE(hipMemsetAsync(f->loss_acc, 0, sizeof(double), st));
+    for (int b0 = 0; b0 < f->n_train; b0 += std::min(f->batch, f->n_train)) {
+        const int nb = std::min(f->batch, f->n_train - b0);
+        rc = trainer_fit_step(t, f->pos + (size_t)3 * b0, f->q + (size_t)f->n_out * b0, nb, st);
+        if (rc != RT_OK) return rc;
+        hipLaunchKernelGGL(k_acc_loss, dim3(1), dim3(64), 0, st, t->scal, f->loss_acc);
+        RT_HIPE(hipGetLastError());
+    }
+    double h_loss = 0.0, h_err = 0.0;
+    if (f->n_test > 0) {
+        rc = trainer_fit_error(t, f->pos + (size_t)3 * f->n_train, f->q + (size_t)f->n_out * f->n_train, f->n_test, st);
+        if (rc != RT_OK) return rc;
+        RT_HIPE(hipMemcpyAsync(&h_err, t->err_acc + kErrBlocks, sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    RT_HIPE(hipMemcpyAsync(&h_loss, f->loss_acc, sizeof(double), hipMemcpyDeviceToHost, st));
+    RT_HIPE(hipStreamSynchronize(st));
+    f->epochs += 1;
+    if (loss_out) *loss_out = h_loss;
+    if (error_out) *error_out = h_err;
     return RT_OK;
 }
 

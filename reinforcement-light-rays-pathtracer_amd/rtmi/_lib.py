@@ -67,6 +67,8 @@ EXPORTS = (
     "rt_ktime_enable", "rt_ktime_read", "rt_ktime_name",
     "rt_sarsa_voronoi_palette", "rt_sarsa_set_view_colours", "rt_render_volume_view",
     "rt_render_volume_view_tiles_device",
+    "rt_qtable_read", "rt_dqn_fit_order", "rt_dqn_fit_step_device", "rt_dqn_fit_loss_device", "rt_dqn_fit_error_device",
+    "rt_dqn_fit_create", "rt_dqn_fit_destroy", "rt_dqn_fit_info", "rt_dqn_fit_epoch",
 )
 
 
@@ -194,6 +196,16 @@ def _declare(lib):
                                       ctypes.c_uint32, _FP, _IP, _IP, _FP]),
         "rt_render_volume_view_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
                                                    ctypes.c_uint32, _IP, i, i, _P, _P]),
+        "rt_qtable_read": (i, [ctypes.c_char_p, _IP, _IP, _FP, _FP]),
+        "rt_dqn_fit_order": (i, [ctypes.c_uint64, ctypes.c_int32, f, _IP, _IP]),
+        "rt_dqn_fit_step_device": (i, [_P, _P, _P, _P, i, _FP, _FP, _P]),
+        "rt_dqn_fit_loss_device": (i, [_P, _P, _P, _P, i, _P, _FP, _P]),
+        "rt_dqn_fit_error_device": (i, [_P, _P, _P, _P, i, ctypes.POINTER(ctypes.c_double), _P]),
+        "rt_dqn_fit_create": (i, [_P, _P, _FP, _FP, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, f,
+                                  ctypes.c_int32, ctypes.POINTER(_P)]),
+        "rt_dqn_fit_destroy": (i, [_P]),
+        "rt_dqn_fit_info": (i, [_P, _IP, _IP, _IP, _IP]),
+        "rt_dqn_fit_epoch": (i, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _P]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),

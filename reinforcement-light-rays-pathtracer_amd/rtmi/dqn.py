@@ -11,6 +11,10 @@
   forward / sample / render / render_tiles_device
   DqnTrainer(ctx, nn_vertices, weights)   Neural-Q training (rt_dqn_trainer_*): TD targets,
                           one Adam step per batch, parameters out for a new Dqn
+  QFit(ctx, trainer, pos, q) / QFit.from_map / QFit.from_file   the reference's NN_Q_Value_Trainer:
+                          the network fitted to a radiance map's Q-table (rt_dqn_fit_*), epoch()
+                          -> (loss, test error); fit_order(seed, n) its split and shuffle;
+                          DqnTrainer.fit_step_device / fit_error_device one dense step / the error
 """
 from __future__ import annotations
 
@@ -335,6 +339,36 @@ class DqnTrainer:
                                              ctypes.byref(gn) if sync else None, ctypes.c_void_p(stream)))
         return (float(loss.value), float(gn.value)) if sync else None
 
+    def fit_step_device(self, loc_ptr: int, target_ptr: int, n: int, stream: int = 0,
+                        sync: bool = True) -> Optional[Tuple[float, float]]:
+        """One Adam step of the supervised fit (rt_dqn_fit_step_device): targets n x n_out, the
+        squared distance over every output.  Returns and waits as step_device does."""
+        loss, gn = ctypes.c_float(0.0), ctypes.c_float(0.0)
+        check(lib().rt_dqn_fit_step_device(self.ctx.handle, self._h, ctypes.c_void_p(loc_ptr),
+                                           ctypes.c_void_p(target_ptr), n,
+                                           ctypes.byref(loss) if sync else None,
+                                           ctypes.byref(gn) if sync else None, ctypes.c_void_p(stream)))
+        return (float(loss.value), float(gn.value)) if sync else None
+
+    def fit_loss_device(self, q_ptr: int, target_ptr: int, n: int, dq_ptr: int, stream: int = 0,
+                        sync: bool = True) -> Optional[float]:
+        """The dense loss and its output gradient alone, on device arrays n x n_out
+        (rt_dqn_fit_loss_device); sync=False leaves the kernel in flight and returns None."""
+        loss = ctypes.c_float(0.0)
+        check(lib().rt_dqn_fit_loss_device(self.ctx.handle, self._h, ctypes.c_void_p(q_ptr),
+                                           ctypes.c_void_p(target_ptr), n, ctypes.c_void_p(dq_ptr),
+                                           ctypes.byref(loss) if sync else None, ctypes.c_void_p(stream)))
+        return float(loss.value) if sync else None
+
+    def fit_error_device(self, loc_ptr: int, target_ptr: int, n: int, stream: int = 0) -> float:
+        """sum_b ||target_b - Q(loc_b)||^2 over n rows in double, no update
+        (rt_dqn_fit_error_device); waits for the stream."""
+        e = ctypes.c_double(0.0)
+        check(lib().rt_dqn_fit_error_device(self.ctx.handle, self._h, ctypes.c_void_p(loc_ptr),
+                                            ctypes.c_void_p(target_ptr), n, ctypes.byref(e),
+                                            ctypes.c_void_p(stream)))
+        return float(e.value)
+
     def params(self) -> Tuple[list, list]:
         W = [np.zeros(s, np.float32) for s in self.shapes]
         b = [np.zeros(s[0], np.float32) for s in self.shapes]
@@ -403,6 +437,88 @@ class NeuralQ:
 
     def __exit__(self, *exc):
         self.close()
+
+
+FIT_TAG = 0x51466974        # RT_DQN_FIT_TAG: word 3 of fit_order's Philox counter
+FIT_ERROR_CHUNK = 4096      # RT_DQN_FIT_ERROR_CHUNK: rows per forward of fit_error_device
+
+
+def fit_order(seed: int, n: int, train_fraction: float = 0.8) -> Tuple[np.ndarray, int]:
+    """(order, n_train) of rt_dqn_fit_order: the seeded train/test split and shuffle of n rows
+    (NN_Q_Value_Trainer's random_shuffle + rand() < 0.8); order[:n_train] are the training
+    rows, order[n_train:] the test rows."""
+    order = np.zeros(max(int(n), 0), np.int32)
+    nt = ctypes.c_int32(0)
+    check(lib().rt_dqn_fit_order(seed, int(n), float(train_fraction), _ip(order), ctypes.byref(nt)))
+    return order, int(nt.value)
+
+
+class QFit:
+    """The reference's NN_Q_Value_Trainer (NN_Q_Value_Trainer/Source/main.cu:118-294) on the
+    device: `trainer`'s network fitted to the rows position -> Q values of a radiance map
+    (rt_dqn_fit_*).  pos (n, 3) and q (n, n_out) are host arrays; they are uploaded once in
+    fit_order(seed, n, train_fraction)'s order.  The trainer is borrowed: it keeps the fitted
+    parameters (trainer.params() -> Dqn / write_dynet) and can go on into NeuralQ."""
+
+    def __init__(self, ctx: Context, trainer: "DqnTrainer", pos: np.ndarray, q: np.ndarray, seed: int = 1984,
+                 train_fraction: float = 0.8, batch_size: int = 128):
+        self.ctx, self.trainer = ctx, trainer
+        self._h = ctypes.c_void_p()
+        pos = np.ascontiguousarray(pos, np.float32)
+        q = np.ascontiguousarray(q, np.float32)
+        if pos.ndim != 2 or pos.shape[1] != 3 or q.ndim != 2 or q.shape[0] != pos.shape[0]:
+            raise ValueError(f"pos must be (n, 3) and q (n, actions), got {pos.shape} and {q.shape}")
+        check(lib().rt_dqn_fit_create(ctx.handle, trainer._h, _fp(pos), _fp(q), pos.shape[0], q.shape[1], seed,
+                                      float(train_fraction), int(batch_size), ctypes.byref(self._h)))
+
+    @classmethod
+    def from_map(cls, ctx: Context, trainer: "DqnTrainer", radiance_map, **kw) -> "QFit":
+        """The fit of a trained rtmi.sarsa.RadianceMap: its volumes' positions and its Q-table as
+        they are on the device (rt_sarsa_volumes + rt_sarsa_read), not the 6 digits of save_q."""
+        return cls(ctx, trainer, radiance_map.volumes()[0], radiance_map.read()[0], **kw)
+
+    @classmethod
+    def from_file(cls, ctx: Context, trainer: "DqnTrainer", path: str, **kw) -> "QFit":
+        """The fit of a radiance_map_data.txt (RadianceMap.save_q), the reference's input."""
+        from .sarsa import read_q
+        return cls(ctx, trainer, *read_q(path), **kw)
+
+    def info(self) -> dict:
+        a, b, c, d = (ctypes.c_int32(0) for _ in range(4))
+        check(lib().rt_dqn_fit_info(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)))
+        return {"n_train": a.value, "n_test": b.value, "n_batches": c.value, "epochs_done": d.value}
+
+    def epoch(self, stream: int = 0) -> Tuple[float, float]:
+        """One pass over the training rows and the test error after it: the reference's printed
+        (Loss, Error) of an epoch (rt_dqn_fit_epoch); waits once, at the end."""
+        loss, e = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        check(lib().rt_dqn_fit_epoch(self.ctx.handle, self._h, ctypes.byref(loss), ctypes.byref(e),
+                                     ctypes.c_void_p(stream)))
+        return float(loss.value), float(e.value)
+
+    @staticmethod
+    def epoch_block(i: int, loss: float, error: float) -> str:
+        """the reference's per-epoch print (main.cu:279-283; ostream defaults, the sums as the
+        floats the reference holds them in)"""
+        return (f"---------------- {i} ----------------\n      Loss: {float(np.float32(loss)):g}\n"
+                f"      Error: {float(np.float32(error)):g}\n-------------------------------------\n\n")
+
+    def close(self) -> None:
+        if self._h:
+            lib().rt_dqn_fit_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def td_targets_device(ctx: Context, seed: int, next_q_ptr: int, terminal_ptr: int, reward_ptr: int,

@@ -8,7 +8,8 @@
                                   sums for a cross-GPU sum (rtmi.dist.sarsa_frame)
   .read() / .volumes() / .nearest(pos, nrm)   Q-table, placement, KD queries (parity)
   .save_q(path) / .load_q(path)   radiance_map_data.txt out and back in (resume a trained map)
-  .set_sampling(SAMPLE_MAX)       sample_max_direction_from_radiance_distribution
+  read_q(path)                    such a file without a map: (positions, Q) for rtmi.dqn.QFit
+  .set_sampling(SAMPLE_MAX)      sample_max_direction_from_radiance_distribution
   .set_td_mode(TD_INFRAME)        the reference's racy in-frame TD update (one GPU)
   .frame_stats() / .append_stats_line(path)   sarsa_training_stats.txt (GPU/main.cu:321-339)
   .view(cam, params, first_sample, aov) / .view_tiles_device(...)   the Voronoi view (GPU/main.cu
@@ -284,6 +285,18 @@ def read_q_file(path: str):
         rows = [np.array(l.split(), np.float64) for l in fh if l.strip()]
     a = np.array(rows).reshape(len(rows), 3 + actions)
     return a[:, :3].astype(np.float32), a[:, 3:].astype(np.float32)
+
+
+def read_q(path: str):
+    """radiance_map_data.txt -> (positions [n, 3], Q [n, actions]) through the library's own
+    parser (rt_qtable_read, the reference trainer's load_radiance_map_data): every value is
+    strtof of its printed token; a malformed file raises RtError naming the line."""
+    n, a = ctypes.c_int32(0), ctypes.c_int32(0)
+    check(lib().rt_qtable_read(os.fsencode(path), ctypes.byref(n), ctypes.byref(a), None, None))
+    pos = np.zeros((n.value, 3), np.float32)
+    q = np.zeros((n.value, a.value), np.float32)
+    check(lib().rt_qtable_read(os.fsencode(path), ctypes.byref(n), ctypes.byref(a), _fp(pos), _fp(q)))
+    return pos, q
 
 
 def read_selected_file(path: str):
