@@ -605,6 +605,53 @@ int rt_render_volume_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sa
                                        const int32_t* tiles, int n_tiles, int tile_size, float* d_out,
                                        void* stream);
 
+/* ---- ground-truth incident radiance at surface points ------------------------
+ * Replaces no reference interface: the thesis judges what a radiance map or a Q-network
+ * learned against "the true incident radiance distribution" at selected points, "calculated by
+ * firing 4096 sampled light paths per sector and averaging their incident radiance
+ * approximation" (Descriptions/write_up/chapters/4_critical_evaluation.tex:92-110,
+ * Images/true_distribution.png beside expected_sarsa_visualisation.png and
+ * neural_q_visualisation.png); the reference ships the picture and no code for it.
+ *
+ * Point p lies on surface tri[p] and takes the scene's normal and tangent frame of that
+ * surface, as rt_dqn_sample does.  Sector k = gx * 12 + gy is the sampler's cell k.  Sample s in
+ * [first_sample, first_sample + params->spp) of (p, k), Philox pixel word pix = ids[p] * 144 + k:
+ *   dir = the direction rt_dqn_sample returns for pixel pix, sample s, bounce 0 when it selects
+ *         cell k: grid_dir(gx + u, gy + v), (u, v) = u01 of words 0, 1 of the block with
+ *         counter (pix, s, 1, 73) -- computed directly, not through a Q vector;
+ *   the ray o = pos + dir * 1e-5f (a multiply, then an add), d = normalize(dir), throughput
+ *         (1, 1, 1): nothing is multiplied in at the probed point, the value is incoming radiance;
+ *   from there the tail of a GPU-preset rt_render path at depth 1: depth == max_bounces before a
+ *         cast ends the path with 0; a miss gives tp * env_light, a light tp * emission, a
+ *         surface takes the preset's bounce step with params->sampler (event 1 + depth, counter
+ *         word 3 = 0); hit rule params->hit_rule, scale params->t_scale.  width, height and
+ *         preset are ignored.
+ * out_rad[p][k] = the mean of the paths' values L; out_irr[p][k] = the mean of L * c, c =
+ * dot(N, d) of the sample's first ray; both by rt_params' sum definition (spp_split chunks, each
+ * summed in sample order, folded ((P0 + P1) + P2) + .., divided by (float)spp; here spp_split may
+ * be any divisor of spp).  out_dir[p][k] = dir of sample first_sample.  out_casts = closest-hit
+ * calls.  A point's result depends on the scene, params, pos[p], tri[p], ids[p] and first_sample
+ * alone -- not on n, the point's place in the list, the launch or the cast route (the scene's
+ * bounce-ray candidate table where it has or may build one, the exact BVH when the accel mode
+ * turns it on, the filter or the scan otherwise: the same hits) -- and is bit-identical run to
+ * run: a multi-GPU split is a split of the point list, and batches of first_sample combine
+ * into longer means and give error bars.
+ * RT_E_INVALID: a NULL required pointer, n < 0, tri[p] outside [0, n_surf), ids[p] >= 2^32 / 144,
+ * spp <= 0 or a split that does not divide it, max_bounces < 1.  n = 0: RT_OK, nothing written.
+ * max_bounces = 1: zeros and 0 casts (out_dir is still written).
+ * rt_probe_radiance_device: the same on device pointers, asynchronous on `stream`; d_casts is
+ * accumulated into; tri and ids are not checked on the host: a point that fails the checks
+ * above gets zeros, casts nothing and leaves its out_dir unwritten.  The chunk sums live in a workspace of the context: its probes run one
+ * after another. */
+#define RT_PROBE_SECTORS 144
+int rt_probe_radiance(rt_ctx* ctx, const rt_scene* scene, const rt_params* params, const float* pos /* n x 3 */,
+                      const int32_t* tri /* n */, const uint32_t* ids /* n */, int n, uint32_t first_sample,
+                      float* out_rad /* n x 144 x 3 */, float* out_irr /* n x 144 x 3, may be NULL */,
+                      float* out_dir /* n x 144 x 3, may be NULL */, uint64_t* out_casts /* may be NULL */);
+int rt_probe_radiance_device(rt_ctx* ctx, const rt_scene* scene, const rt_params* params, const float* d_pos,
+                             const int32_t* d_tri, const uint32_t* d_ids, int n, uint32_t first_sample,
+                             float* d_rad, float* d_irr, float* d_dir, uint64_t* d_casts, void* stream);
+
 /* Device self-tests of numeric building blocks (no reference counterpart): every
  * bit-exact claim against oracle/ rests on them.  result[0] = mismatches, result[1] = the
  * lowest mismatching input bits (0xffffffff: none).
@@ -667,7 +714,8 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 #define RT_KT_DQN_CAMERA 6    /* k_dqn_camera */
 #define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view) */
 #define RT_KT_SARSA_NEAREST 8 /* k_sarsa_nearest: rt_sarsa_nearest's queries (without its copies) */
-#define RT_KT_COUNT 9
+#define RT_KT_PROBE 9         /* k_probe: rt_probe_radiance's paths (without its fold) */
+#define RT_KT_COUNT 10
 int rt_ktime_enable(int on);
 int rt_ktime_read(int kernel, double* total_ms, int64_t* launches);
 const char* rt_ktime_name(int kernel);

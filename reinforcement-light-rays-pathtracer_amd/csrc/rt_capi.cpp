@@ -166,6 +166,7 @@ rt::DeviceScene launch_scene(const rt_scene* sc, bool force_bvh = false) {
 
 namespace rt {
 void release_dqn_workspace(const rt_ctx* ctx);
+void release_probe_workspace(const rt_ctx* ctx);  // rt_probe.hip
 int ctx_device(const rt_ctx* ctx) { return ctx->device; }
 const DeviceScene& scene_device(const rt_scene* s) { return s->dev; }
 // the device view a render launch takes (the BVH fields set when the scene's BVH path is on)
@@ -713,6 +714,7 @@ int rt_ctx_destroy(rt_ctx* ctx) {
     if (!ctx) return RT_OK;
     (void)hipSetDevice(ctx->device);
     rt::release_dqn_workspace(ctx);
+    rt::release_probe_workspace(ctx);
     if (ctx->d_blocks) (void)hipFree(ctx->d_blocks);
     if (ctx->d_cull) (void)hipFree(ctx->d_cull);
     if (ctx->d_csum) (void)hipFree(ctx->d_csum);

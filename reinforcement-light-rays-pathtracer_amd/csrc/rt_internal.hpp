@@ -24,7 +24,8 @@ enum KtimeKernel {
     KT_DQN_CAMERA = 6,
     KT_SARSA_VIEW = 7,  // k_sarsa_view (the radiance-map view)
     KT_SARSA_NEAREST = 8,  // k_sarsa_nearest (rt_sarsa_nearest's queries)
-    KT_COUNT = 9
+    KT_PROBE = 9,  // k_probe (rt_probe_radiance)
+    KT_COUNT = 10
 };
 struct KernelTimer {
     int kernel = -1;  // -1: not timing

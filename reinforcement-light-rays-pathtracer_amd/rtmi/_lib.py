@@ -41,7 +41,8 @@ RT_KT_DQN_BOUNCE = 5
 RT_KT_DQN_CAMERA = 6
 RT_KT_SARSA_VIEW = 7
 RT_KT_SARSA_NEAREST = 8
-RT_KT_COUNT = 9
+RT_KT_PROBE = 9
+RT_KT_COUNT = 10
 
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -69,6 +70,7 @@ EXPORTS = (
     "rt_render_volume_view_tiles_device",
     "rt_qtable_read", "rt_dqn_fit_order", "rt_dqn_fit_step_device", "rt_dqn_fit_loss_device", "rt_dqn_fit_error_device",
     "rt_dqn_fit_create", "rt_dqn_fit_destroy", "rt_dqn_fit_info", "rt_dqn_fit_epoch",
+    "rt_probe_radiance", "rt_probe_radiance_device",
 )
 
 
@@ -206,6 +208,10 @@ def _declare(lib):
         "rt_dqn_fit_destroy": (i, [_P]),
         "rt_dqn_fit_info": (i, [_P, _IP, _IP, _IP, _IP]),
         "rt_dqn_fit_epoch": (i, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _P]),
+        "rt_probe_radiance": (i, [_P, _P, ctypes.POINTER(RtParams), _FP, _IP, _UP, i, ctypes.c_uint32, _FP, _FP, _FP,
+                                  _U64P]),
+        "rt_probe_radiance_device": (i, [_P, _P, ctypes.POINTER(RtParams), _P, _P, _P, i, ctypes.c_uint32, _P, _P, _P,
+                                         _P, _P]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),
