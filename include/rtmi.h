@@ -492,9 +492,20 @@ int rt_sarsa_set_sampling(rt_sarsa* sarsa, int mode);
  *   live Q at every sample, as the reference's scan of its radiance grid does.  Not
  *   reproducible run to run (a launch with one active lane is: the events then run in the
  *   restatement's order); one GPU only: rt_sarsa_td_device and a tile render with apply = 0
- *   return RT_E_UNSUPPORTED in this mode. */
+ *   return RT_E_UNSUPPORTED in this mode.
+ * RT_SARSA_TD_OFF no learning: a frame samples the map as it stands (the CPU engine's
+ *   draw_importance_sampling_path_tracing, Old_CPU_Rendering_Engine/Source/path_tracing/
+ *   importance_sampling_path_tracing.cpp, on the GPU engine's map).  The render kernels are
+ *   instantiated with the TD event, its atomics and its irradiance load compiled out; no
+ *   sum, count, Q, visit, irradiance or CDF changes and nothing is applied at the frame end
+ *   (rt_render_sarsa_tiles_device ignores `apply`, so a frame splits across GPUs with no
+ *   exchange).  `frames` still advances, so successive frames draw fresh samples and can be
+ *   averaged; rt_sarsa_frame_stats works as before; RT_SARSA_SAMPLE_MAX reads the stored
+ *   arg-max.  A frame's image, casts and statistics are those a RT_SARSA_TD_FRAME frame of
+ *   the same map gives, bit for bit. */
 #define RT_SARSA_TD_FRAME 0
 #define RT_SARSA_TD_INFRAME 1
+#define RT_SARSA_TD_OFF 2
 int rt_sarsa_set_td_mode(rt_sarsa* sarsa, int mode);
 int rt_sarsa_get_td_mode(const rt_sarsa* sarsa, int* mode);
 /* Paths in flight of the in-frame rule's render.  Its races -- and with them how fast a frame
@@ -554,6 +565,36 @@ int rt_sarsa_volumes(const rt_sarsa* sarsa, float* pos, float* normal, int32_t* 
  * irradiance_accum (n) after the last applied frame; NULL pointers are skipped. */
 int rt_sarsa_read(const rt_sarsa* sarsa, float* q, float* cdf, uint32_t* visits,
                   float* irradiance);
+/* The counterpart of rt_sarsa_read: host arrays into the volumes [v0, v0 + n) of the map.  Q is
+ * set from q (n x 144); the irradiance estimate and the CDF (with its row ends and arg-max)
+ * are recomputed as rt_sarsa_load_q does, by the same code, with no text file in between;
+ * visits (n x 144) are set, or kept when NULL.  Pending TD sums are left alone.  What a
+ * multi-GPU bake gathers into: each rank bakes a slice, the Q rows are gathered, every rank
+ * writes them.  RT_E_INVALID for a range outside the map; n = 0 is RT_OK. */
+int rt_sarsa_write(rt_sarsa* sarsa, int v0, int n, const float* q /* n x 144 */,
+                   const uint32_t* visits /* n x 144, or NULL: kept */);
+/* Fill the volumes [v0, v0 + n) from ground truth, on the device (k_bake, csrc/rt_bake.hip): the
+ * CPU engine's map, whose volumes are filled by sampling the incoming radiance per sector at
+ * construction (Old_CPU_Rendering_Engine/Source/radiance_volumes/radiance_map.cpp,
+ * radiance_volume.cpp), for the GPU engine's 12 x 12 scalar grid.  With rad what
+ * rt_probe_radiance gives for {pos = the volume's position, tri = its surface, ids = v} under
+ * the same params and first_sample, bit for bit (a volume's sector k is the probe's: both
+ * frames are normal_frame of the surface's stored normal):
+ *   Q[v][k] = max(vol_brdf[v] * ((rad.r + rad.g) + rad.b) / 3, RADIANCE_THRESHOLD)
+ *   (vol_brdf = the surface's luminance / pi; NaN gives the floor), visits[v][k] = spp, the
+ *   sector's pending TD sum and count = 0,
+ * then the volume's irradiance estimate and CDF as rt_sarsa_write computes them from that Q.
+ * vol_brdf * luminance is what the TD rule's own targets converge to; its floor keeps every
+ * sector's pdf above zero, so a render from a baked map stays unbiased; visits = spp makes
+ * later training weigh the baked value as spp observations.  Nothing moves to the host.  A
+ * volume's result depends on neither v0, n, the entry's internal batching nor the cast route.
+ * Asynchronous on `stream` unless out_casts (the closest-hit calls, host) is given.
+ * RT_E_INVALID for a range outside the map and whatever rt_probe_radiance refuses in params
+ * (spp <= 0, spp_split not dividing spp, max_bounces < 1, bad sampler / hit_rule);
+ * RT_E_UNSUPPORTED for a preset other than RT_PRESET_GPU; the map is then untouched.  n = 0 is
+ * RT_OK; max_bounces = 1 gives the floor everywhere and 0 casts. */
+int rt_sarsa_bake(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa, const rt_params* params, int v0,
+                  int n, uint32_t first_sample, uint64_t* out_casts /* may be NULL */, void* stream);
 /* RadianceMap::find_closest_radiance_volume_iterative (radiance_map.cu:149-203), n queries. */
 int rt_sarsa_nearest(rt_ctx* ctx, const rt_sarsa* sarsa, const float* pos, const float* normal,
                      int n, int32_t* out);
@@ -715,7 +756,8 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 #define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view) */
 #define RT_KT_SARSA_NEAREST 8 /* k_sarsa_nearest: rt_sarsa_nearest's queries (without its copies) */
 #define RT_KT_PROBE 9         /* k_probe: rt_probe_radiance's paths (without its fold) */
-#define RT_KT_COUNT 10
+#define RT_KT_BAKE 10         /* k_bake: rt_sarsa_bake's paths (without its finish) */
+#define RT_KT_COUNT 11
 int rt_ktime_enable(int on);
 int rt_ktime_read(int kernel, double* total_ms, int64_t* launches);
 const char* rt_ktime_name(int kernel);

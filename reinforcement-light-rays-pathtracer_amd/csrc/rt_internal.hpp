@@ -25,7 +25,8 @@ enum KtimeKernel {
     KT_SARSA_VIEW = 7,  // k_sarsa_view (the radiance-map view)
     KT_SARSA_NEAREST = 8,  // k_sarsa_nearest (rt_sarsa_nearest's queries)
     KT_PROBE = 9,  // k_probe (rt_probe_radiance)
-    KT_COUNT = 10
+    KT_BAKE = 10,  // k_bake (rt_sarsa_bake's paths, without its finish)
+    KT_COUNT = 11
 };
 struct KernelTimer {
     int kernel = -1;  // -1: not timing
@@ -443,6 +444,10 @@ struct SarsaMap {
     int32_t* qmax = nullptr;               // [n] first sector of largest Q (k_sarsa_apply)
     unsigned long long* stats = nullptr;   // [2] launch: sum of per-pixel int(mean path length), zero paths
     unsigned long long* prof = nullptr;    // [8] RT_SARSA_PROF builds: per-phase s_memtime cycles (rt_sarsa.hip)
+    // 1 = RT_SARSA_TD_OFF: the render samples the map as it stands and changes nothing in it
+    // (k_sarsa_render<.., TD = 2>: the TD event compiled out); takes precedence over td_inframe.  Host
+    // only, and last: the kernels' argument layout of every older field is as it was
+    int td_off = 0;
 };
 #ifndef RT_KD_STACK
 // 30: the SARSA render's 256-lane workgroup then takes 30 KB of LDS and five fit a CU (32 KB held
@@ -457,6 +462,15 @@ hipError_t launch_sarsa_apply(const SarsaMap& m, hipStream_t stream);
 bool sarsa_prof_compiled();  // rt_sarsa.hip was built with RT_SARSA_PROF=1 (per-phase cycle counters)
 bool sarsa_ctab_compiled();  // rt_sarsa.hip was built with RT_SARSA_CTAB=1 (the table route of its persistent kernel)
 hipError_t launch_sarsa_rebuild(const SarsaMap& m, hipStream_t stream);  // CDF + argmax from Q
+hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStream_t stream);  // of [v0, v0 + n)
+// rt_sarsa_bake (rt_bake.hip) works on a map through this view (rt_sarsa_host.cpp: sarsa_bake_view)
+struct SarsaBakeView {
+    SarsaMap m;
+    int device = 0;
+    const int32_t* vol_surf = nullptr;  // [n_vol] the surface each volume lies on
+    float* csum = nullptr;              // the chunk-sum workspace
+    unsigned long long* work = nullptr;  // [2] the queue's counter, the casts
+};
 hipError_t launch_sarsa_nearest(const SarsaMap& m, const float* pos, const float* nrm, int n, int32_t* out,
                                 hipStream_t stream);
 // the radiance-map view (k_sarsa_view): r.sample_base = the first sample index, colours [n_vol] rgb (w unused);

@@ -31,7 +31,7 @@ int g_errors = 0;
 
 const char* const kNames[rt::KT_COUNT] = {"k_render_ps", "k_render", "k_sarsa_render", "k_sarsa_apply",
                                           "k_dqn_mlp", "k_dqn_bounce", "k_dqn_camera", "k_sarsa_view",
-                                          "k_sarsa_nearest", "k_probe"};
+                                          "k_sarsa_nearest", "k_probe", "k_bake"};
 
 // fold every recorded pair into the totals (caller holds g_mu)
 void drain(bool keep) {

@@ -531,6 +531,7 @@ __device__ __forceinline__ void td_event_inframe(const SarsaMap& m, int rv, int 
 template <int TD>
 __device__ __forceinline__ void td_event(const SarsaMap& m, int rv, int sector, float target) {
     if (RT_SARSA_NO_TD) return;
+    if constexpr (TD == 2) return;  // RT_SARSA_TD_OFF: the map is read-only
     if constexpr (TD == 1) {
         td_event_inframe(m, rv, sector, target);
         return;
@@ -564,15 +565,19 @@ __device__ __forceinline__ bool sarsa_step(const RenderLaunch& a, const SarsaMap
     VolPre vp;
     if (is_surf && sv >= 0) vp = vol_load(m, sv);
     if (td) {
-        float target;
-        if (h.tri < 0) {
-            target = P.cur_brdf * a.env_light;
-        } else if (!is_surf) {
-            target = P.cur_brdf * m.tri_lum[h.tri];
-        } else {
-            target = ((TD == 1 ? live_load(&m.accum[rv]) : m.accum[rv]) * kIrrScale) * P.cur_brdf;
+        // TD = 2 (RT_SARSA_TD_OFF, a frozen map): no target, no irradiance load, no atomics; the
+        // path's state moves on exactly as in the learning modes
+        if constexpr (TD != 2) {
+            float target;
+            if (h.tri < 0) {
+                target = P.cur_brdf * a.env_light;
+            } else if (!is_surf) {
+                target = P.cur_brdf * m.tri_lum[h.tri];
+            } else {
+                target = ((TD == 1 ? live_load(&m.accum[rv]) : m.accum[rv]) * kIrrScale) * P.cur_brdf;
+            }
+            td_event<TD>(m, P.cur_rv, P.cur_sector, target);
         }
-        td_event<TD>(m, P.cur_rv, P.cur_sector, target);
         P.cur_rv = rv;
         P.cur_sector = -1;
     } else if (P.depth == 0 && is_surf) {
@@ -1088,6 +1093,13 @@ __global__ __launch_bounds__(256) void k_sarsa_rebuild(const SarsaMap m) {
     rebuild_volume(m, v);
 }
 
+// the same for the volumes [v0, v0 + n) alone (rt_sarsa_write, rt_sarsa_bake)
+__global__ __launch_bounds__(256) void k_sarsa_rebuild_range(const SarsaMap m, int v0, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    rebuild_volume(m, v0 + i);
+}
+
 // nearest-volume queries alone (KD parity): pos/nrm [n][3]
 __global__ __launch_bounds__(256) void k_sarsa_nearest(const SarsaMap m, const float* __restrict__ pos,
                                                        const float* __restrict__ nrm, int n, int32_t* out) {
@@ -1371,12 +1383,20 @@ hipError_t launch_sarsa_render_t(const RenderLaunch& a, const SarsaMap& m, hipSt
 hipError_t launch_sarsa_render(const RenderLaunch& a, const SarsaMap& m, hipStream_t stream) {
     if (a.n_blocks <= 0) return hipSuccess;
     KernelTimer kt(KT_SARSA_RENDER, stream);
+    if (m.td_off) return launch_sarsa_render_t<2>(a, m, stream);
     return m.td_inframe ? launch_sarsa_render_t<1>(a, m, stream) : launch_sarsa_render_t<0>(a, m, stream);
 }
 
 hipError_t launch_sarsa_rebuild(const SarsaMap& m, hipStream_t stream) {
     if (m.n_vol <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_sarsa_rebuild, dim3((unsigned)((m.n_vol + 255) / 256)), dim3(256), 0, stream, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (v0 < 0 || n > m.n_vol - v0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sarsa_rebuild_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, m, v0, n);
     return hipGetLastError();
 }
 

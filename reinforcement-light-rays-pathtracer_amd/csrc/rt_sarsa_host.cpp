@@ -370,12 +370,20 @@ struct rt_sarsa {
     size_t cull_cap = 0;
     // the views' per-volume colour table, rgb in a float4 (rt_sarsa_set_view_colours; in allocs)
     float4* d_view = nullptr;
+    // rt_sarsa_bake: the volumes' surfaces (in allocs), its chunk sums (grown up to its batch
+    // size) and {queue counter, casts}
+    int32_t* d_surf = nullptr;
+    float* d_bake_csum = nullptr;
+    size_t bake_cap = 0;
+    unsigned long long* d_bake_work = nullptr;
     ~rt_sarsa() {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
         if (d_csum) (void)hipFree(d_csum);
         if (d_cull) (void)hipFree(d_cull);
         if (d_work) (void)hipFree(d_work);
+        if (d_bake_csum) (void)hipFree(d_bake_csum);
+        if (d_bake_work) (void)hipFree(d_bake_work);
         if (m.prof) (void)hipFree(m.prof);
     }
     template <class T>
@@ -470,7 +478,8 @@ int render_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, cons
         fprintf(stderr, "{\"sarsa_prof\": {\"trace\": %llu, \"grid\": %llu, \"walks\": %llu, \"step\": %llu, "
                         "\"trips\": %llu, \"active_lanes\": %llu}}\n", v[0], v[1], v[2], v[3], v[4], v[5]);
     }
-    if (apply) RT_HIPE(rt::launch_sarsa_apply(sa->m, stream));
+    // (RT_SARSA_TD_OFF: the frame left no sums and the map stays as it is)
+    if (apply && !sa->m.td_off) RT_HIPE(rt::launch_sarsa_apply(sa->m, stream));
     sa->frames += 1;
     return RT_OK;
 }
@@ -581,6 +590,39 @@ int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<flo
 }
 
 }  // namespace
+
+namespace rt {
+
+// rt_bake.hip's view of a map: its device arrays, the volumes' surfaces and a chunk-sum
+// workspace of at least `floats` floats (grown, never shrunk; launches of one map share it in
+// stream order)
+int sarsa_bake_view(rt_sarsa* sa, size_t floats, SarsaBakeView* out) {
+    RT_HIPE(hipSetDevice(sa->device));
+    if (!sa->d_surf) {
+        RT_HIPE(sa->alloc(&sa->d_surf, (size_t)sa->n_vol));
+        RT_HIPE(hipMemcpy(sa->d_surf, sa->surf.data(), sizeof(int32_t) * (size_t)sa->n_vol, hipMemcpyHostToDevice));
+    }
+    if (floats > sa->bake_cap) {
+        if (sa->d_bake_csum) (void)hipFree(sa->d_bake_csum);  // (waits for the launches that use it)
+        sa->d_bake_csum = nullptr;
+        sa->bake_cap = 0;
+        if (hipMalloc(&sa->d_bake_csum, sizeof(float) * floats) != hipSuccess)
+            return err(RT_E_NOMEM, "rt_sarsa_bake: " + std::to_string(sizeof(float) * floats) + " bytes of chunk sums");
+        sa->bake_cap = floats;
+    }
+    if (!sa->d_bake_work) RT_HIPE(hipMalloc(&sa->d_bake_work, 2 * sizeof(unsigned long long)));
+    out->m = sa->m;
+    out->device = sa->device;
+    out->vol_surf = sa->d_surf;
+    out->csum = sa->d_bake_csum;
+    out->work = sa->d_bake_work;
+    return RT_OK;
+}
+
+int sarsa_n_volumes(const rt_sarsa* sa) { return sa->n_vol; }
+int sarsa_device(const rt_sarsa* sa) { return sa->device; }
+
+}  // namespace rt
 
 extern "C" {
 
@@ -996,6 +1038,27 @@ int rt_sarsa_load_q(rt_sarsa* sa, const char* path) {
     return RT_OK;
 }
 
+int rt_sarsa_write(rt_sarsa* sa, int v0, int n, const float* q, const uint32_t* visits) {
+    if (!sa) return err(RT_E_INVALID, "sarsa is NULL");
+    if (v0 < 0 || n < 0 || n > sa->n_vol - v0)
+        return err(RT_E_INVALID, "volumes [" + std::to_string(v0) + ", " + std::to_string((int64_t)v0 + n) +
+                                 ") outside the map's [0, " + std::to_string(sa->n_vol) + ")");
+    if (n == 0) return RT_OK;
+    if (!q) return err(RT_E_INVALID, "q is NULL");
+    const size_t S = (size_t)rt::kSarsaSectors, first = (size_t)v0 * S, count = (size_t)n * S;
+    std::vector<float> accum((size_t)n);
+    for (int i = 0; i < n; ++i)
+        accum[i] = initial_irradiance(&sa->cos_center[first + (size_t)i * S], q + (size_t)i * S, sa->lum[v0 + i]);
+    RT_HIPE(hipSetDevice(sa->device));
+    RT_HIPE(hipDeviceSynchronize());
+    RT_HIPE(hipMemcpy(sa->m.Q + first, q, sizeof(float) * count, hipMemcpyHostToDevice));
+    if (visits) RT_HIPE(hipMemcpy(sa->m.visits + first, visits, sizeof(uint32_t) * count, hipMemcpyHostToDevice));
+    RT_HIPE(hipMemcpy(sa->m.accum + v0, accum.data(), sizeof(float) * (size_t)n, hipMemcpyHostToDevice));
+    RT_HIPE(rt::launch_sarsa_rebuild_range(sa->m, v0, n, 0));
+    RT_HIPE(hipDeviceSynchronize());
+    return RT_OK;
+}
+
 int rt_qtable_read(const char* path, int32_t* n_rows, int32_t* n_actions, float* pos, float* q) {
     if (!path || !n_rows || !n_actions) return err(RT_E_INVALID, "NULL argument");
     if ((pos == nullptr) != (q == nullptr)) return err(RT_E_INVALID, "pos and q must both be given or both be NULL");
@@ -1025,9 +1088,11 @@ int rt_sarsa_set_sampling(rt_sarsa* sa, int mode) {
 }
 
 int rt_sarsa_set_td_mode(rt_sarsa* sa, int mode) {
+    if (mode != RT_SARSA_TD_FRAME && mode != RT_SARSA_TD_INFRAME && mode != RT_SARSA_TD_OFF)
+        return err(RT_E_INVALID, "bad TD mode " + std::to_string(mode));
     if (!sa) return err(RT_E_INVALID, "NULL argument");
-    if (mode != RT_SARSA_TD_FRAME && mode != RT_SARSA_TD_INFRAME) return err(RT_E_INVALID, "bad TD mode");
     sa->m.td_inframe = mode == RT_SARSA_TD_INFRAME;
+    sa->m.td_off = mode == RT_SARSA_TD_OFF;
     return RT_OK;
 }
 
@@ -1040,7 +1105,7 @@ int rt_sarsa_set_inframe_lanes(rt_sarsa* sa, int lanes) {
 
 int rt_sarsa_get_td_mode(const rt_sarsa* sa, int* mode) {
     if (!sa || !mode) return err(RT_E_INVALID, "NULL argument");
-    *mode = sa->m.td_inframe ? RT_SARSA_TD_INFRAME : RT_SARSA_TD_FRAME;
+    *mode = sa->m.td_off ? RT_SARSA_TD_OFF : (sa->m.td_inframe ? RT_SARSA_TD_INFRAME : RT_SARSA_TD_FRAME);
     return RT_OK;
 }
 

@@ -11,6 +11,10 @@
 //   ./build/reinforcement_demo voronoi <scene.obj> <kind> [frames] [out.bmp] [width height]
 //     (GPU/main.cu:414-495, PATH_TRACING_METHOD 2: the radiance volumes' Voronoi view, one
 //      sample per frame; the last frame is saved)
+//   ./build/reinforcement_demo importance <scene.obj> <kind> [frames] [spp] [out.bmp] [width height] [bake_spp]
+//     (the CPU engine's importance-sampling renderer, Old_CPU_Rendering_Engine/Source/main.cpp:
+//      the radiance map filled from ground truth, bake_spp paths per sector (0: left as
+//      created), then frames rendered from the frozen map; the last frame is saved)
 //   (kind: 1 door_room, 2 archway, 3 complex_light_room; scene "cornell" = the Cornell box)
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +23,7 @@
 #include <string>
 
 #include "../host/camera.h"
+#include "../host/importance_sampling_path_tracing.h"
 #include "../host/reinforcement_path_tracing.h"
 #include "../host/scene.h"
 #include "../host/sdl_screen.h"
@@ -37,7 +42,7 @@ static vec4 camera_for(int kind) {  // GPU/main.cu:100-104
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
+        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi|importance <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
         return 2;
     }
     const bool nq = strcmp(argv[1], "neuralq") == 0;
@@ -49,8 +54,11 @@ int main(int argc, char** argv) {
     const int frames = argc > a ? atoi(argv[a++]) : 4;
     const int spp = (!voronoi && argc > a) ? atoi(argv[a++]) : 32;
     const char* out = argc > a ? argv[a++] : "render.bmp";
-    const int width = (voronoi && argc > a + 1) ? atoi(argv[a]) : 512;
-    const int height = (voronoi && argc > a + 1) ? atoi(argv[a + 1]) : 512;
+    const bool importance = strcmp(argv[1], "importance") == 0;
+    const bool sized = (voronoi || importance) && argc > a + 1;
+    const int width = sized ? atoi(argv[a]) : 512;
+    const int height = sized ? atoi(argv[a + 1]) : 512;
+    const int bake_spp = (importance && argc > a + 2) ? atoi(argv[a + 2]) : 64;
     if (width <= 0 || height <= 0) {
         fprintf(stderr, "bad screen size %d x %d\n", width, height);
         return 2;
@@ -80,6 +88,18 @@ int main(int argc, char** argv) {
             for (int f = 0; f < frames; ++f) {
                 draw_voronoi_trace(screen, map, camera, scene, (uint32_t)f);
                 printf("frame %d: voronoi view\n", f);
+            }
+        } else if (importance) {
+            RadianceMap map(ds);
+            printf("radiance volumes: %d (KD array %d)\n", map.radiance_volumes_count, map.radiance_array_size);
+            if (bake_spp > 0) {
+                const uint64_t casts = map.precompute_radiance_volumes(bake_spp, bake_spp % 4 == 0 ? 4 : 1, height);
+                printf("precomputed %d paths per sector: %llu ray casts\n", bake_spp, (unsigned long long)casts);
+            }
+            for (int f = 0; f < frames; ++f) {
+                const uint64_t casts = draw_importance_sampling_path_tracing(screen, camera, map, scene, spp);
+                printf("frame %d: importance sampling, average path length %.3f\n", f,
+                       (double)casts / ((double)screen.width * screen.height * spp));
             }
         } else if (dqn) {
             PretrainedPathtracer pt(ds, model);

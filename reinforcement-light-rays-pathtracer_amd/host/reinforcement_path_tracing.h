@@ -98,6 +98,25 @@ class RadianceMap {
     void set_in_frame_td(bool on) {
         detail::check(rt_sarsa_set_td_mode(map_, on ? RT_SARSA_TD_INFRAME : RT_SARSA_TD_FRAME));
     }
+    // no learning: frames sample the map as it stands (draw_importance_sampling_path_tracing,
+    // importance_sampling_path_tracing.h, sets and restores this around its frame)
+    void set_frozen(bool on) { detail::check(rt_sarsa_set_td_mode(map_, on ? RT_SARSA_TD_OFF : RT_SARSA_TD_FRAME)); }
+    // The CPU engine fills its map's volumes by sampling the incoming radiance per sector when
+    // the map is built (Old_CPU_Rendering_Engine/Source/radiance_volumes/radiance_map.cpp,
+    // radiance_volume.cpp); here on the device, for every volume, `spp` ground-truth paths per
+    // sector in chunks of spp / spp_split (rt_sarsa_bake).  Returns the ray casts.
+    uint64_t precompute_radiance_volumes(int spp = 64, int spp_split = 4, int screen_height = 720,
+                                         uint32_t first_sample = 0) {
+        rt_params p;
+        rt_params_default(RT_PRESET_GPU, &p);
+        p.t_scale = (float)screen_height;
+        p.spp = spp;
+        p.spp_split = spp_split;
+        uint64_t casts = 0;
+        detail::check(rt_sarsa_bake(ds_.ctx(), ds_.scene(), map_, &p, 0, radiance_volumes_count, first_sample, &casts,
+                                    nullptr));
+        return casts;
+    }
     // paths in flight of the in-frame rule (its races depend on it; the reference's GTX 1070 Ti
     // held about 4,864: the setting its training logs are matched at); 0: the whole device
     void set_in_frame_lanes(int lanes) { detail::check(rt_sarsa_set_inframe_lanes(map_, lanes)); }

@@ -7,7 +7,7 @@ does not touch the GPU.
 from ._lib import (LIB_PATH, RT_HIT_NONE, RT_HIT_RULE_CPU, RT_HIT_RULE_GPU, RT_HIT_TYPE_LIGHT,
                    RT_HIT_TYPE_SURFACE, RT_PRESET_CPU, RT_PRESET_GPU, RT_SAMPLER_COSINE,
                    RT_SAMPLER_UNIFORM, RT_KT_RENDER_PS, RT_KT_RENDER, RT_KT_SARSA_RENDER, RT_KT_SARSA_APPLY,
-                   RT_KT_DQN_MLP, RT_KT_DQN_BOUNCE, RT_KT_DQN_CAMERA, RT_KT_SARSA_VIEW, RT_KT_SARSA_NEAREST, RT_KT_PROBE, RT_KT_COUNT, RtCamera, RtError,
+                   RT_KT_DQN_MLP, RT_KT_DQN_BOUNCE, RT_KT_DQN_CAMERA, RT_KT_SARSA_VIEW, RT_KT_SARSA_NEAREST, RT_KT_PROBE, RT_KT_BAKE, RT_KT_COUNT, RtCamera, RtError,
                    RtParams, check, lib)
 from .api import (CAMERAS, OBJ_KINDS, Context, Geometry, Scene, camera, cornell_geometry,
                   default_params, filter_records, intersect, intersect_device, intersect_method, intersect_cand,
@@ -26,6 +26,6 @@ __all__ = [
     "intersect_device", "obj_geometry", "pack_argb", "rect_candidates", "ctab_candidates", "render", "render_tiles_device", "save_bmp", "save_png",
     "dist", "dqn", "metrics", "probe", "sarsa", "tiles", "check", "ktime_enable", "ktime_read", "ktime_name",
     "RT_KT_RENDER_PS", "RT_KT_RENDER", "RT_KT_SARSA_RENDER", "RT_KT_SARSA_APPLY", "RT_KT_DQN_MLP",
-    "RT_KT_DQN_BOUNCE", "RT_KT_DQN_CAMERA", "RT_KT_SARSA_VIEW", "RT_KT_SARSA_NEAREST", "RT_KT_PROBE", "RT_KT_COUNT",
+    "RT_KT_DQN_BOUNCE", "RT_KT_DQN_CAMERA", "RT_KT_SARSA_VIEW", "RT_KT_SARSA_NEAREST", "RT_KT_PROBE", "RT_KT_BAKE", "RT_KT_COUNT",
     "intersect_cand", "CAND_TABLE", "CAND_GIVEN", "CAND_CAP_TABLE", "CAND_CAP_SHARED",
 ]

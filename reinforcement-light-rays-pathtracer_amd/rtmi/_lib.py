@@ -42,7 +42,8 @@ RT_KT_DQN_CAMERA = 6
 RT_KT_SARSA_VIEW = 7
 RT_KT_SARSA_NEAREST = 8
 RT_KT_PROBE = 9
-RT_KT_COUNT = 10
+RT_KT_BAKE = 10
+RT_KT_COUNT = 11
 
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -71,6 +72,7 @@ EXPORTS = (
     "rt_qtable_read", "rt_dqn_fit_order", "rt_dqn_fit_step_device", "rt_dqn_fit_loss_device", "rt_dqn_fit_error_device",
     "rt_dqn_fit_create", "rt_dqn_fit_destroy", "rt_dqn_fit_info", "rt_dqn_fit_epoch",
     "rt_probe_radiance", "rt_probe_radiance_device",
+    "rt_sarsa_write", "rt_sarsa_bake",
 )
 
 
@@ -212,6 +214,8 @@ def _declare(lib):
                                   _U64P]),
         "rt_probe_radiance_device": (i, [_P, _P, ctypes.POINTER(RtParams), _P, _P, _P, i, ctypes.c_uint32, _P, _P, _P,
                                          _P, _P]),
+        "rt_sarsa_write": (i, [_P, i, i, _FP, _UP]),
+        "rt_sarsa_bake": (i, [_P, _P, _P, ctypes.POINTER(RtParams), i, i, ctypes.c_uint32, _U64P, _P]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),

@@ -367,7 +367,7 @@ def save_png(path: str, argb: np.ndarray) -> None:
 def ktime_enable(on: bool = True) -> None:
     """Start (clearing the totals) or stop the library's per-kernel launch timing: HIP events
     on each launch's own stream around k_render_ps, k_render, k_sarsa_render, k_sarsa_apply,
-    k_dqn_mlp, k_dqn_bounce, k_dqn_camera, k_sarsa_view, k_sarsa_nearest and k_probe (rt_ktime_enable)."""
+    k_dqn_mlp, k_dqn_bounce, k_dqn_camera, k_sarsa_view, k_sarsa_nearest, k_probe and k_bake (rt_ktime_enable)."""
     check(lib().rt_ktime_enable(int(bool(on))))
 
 

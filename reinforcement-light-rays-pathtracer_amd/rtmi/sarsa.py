@@ -11,6 +11,9 @@
   read_q(path)                    such a file without a map: (positions, Q) for rtmi.dqn.QFit
   .set_sampling(SAMPLE_MAX)      sample_max_direction_from_radiance_distribution
   .set_td_mode(TD_INFRAME)        the reference's racy in-frame TD update (one GPU)
+  .set_td_mode(TD_OFF)            render from the map as it stands, learning nothing
+  .bake(scene, params, v0, n)     fill volumes from ground truth on the device (rt_sarsa_bake)
+  .write(q, visits, v0)           Q rows (and visits) from host arrays into the map (rt_sarsa_write)
   .frame_stats() / .append_stats_line(path)   sarsa_training_stats.txt (GPU/main.cu:321-339)
   .view(cam, params, first_sample, aov) / .view_tiles_device(...)   the Voronoi view (GPU/main.cu
                                   method 2): each camera hit in its nearest volume's colour
@@ -34,6 +37,7 @@ SAMPLE_CDF = 0   # RT_SARSA_SAMPLE_CDF
 SAMPLE_MAX = 1   # RT_SARSA_SAMPLE_MAX
 TD_FRAME = 0     # RT_SARSA_TD_FRAME
 TD_INFRAME = 1   # RT_SARSA_TD_INFRAME
+TD_OFF = 2       # RT_SARSA_TD_OFF
 
 SECTORS = 144  # GRID_RESOLUTION^2
 
@@ -94,8 +98,9 @@ class RadianceMap:
         check(lib().rt_sarsa_set_sampling(self._h, mode))
 
     def set_td_mode(self, mode: int) -> None:
-        """TD_FRAME (default: frame-synchronous, deterministic) or TD_INFRAME (the reference's
-        in-frame read-modify-write, radiance_volume.cu:282-301; racy, one GPU only)."""
+        """TD_FRAME (default: frame-synchronous, deterministic), TD_INFRAME (the reference's
+        in-frame read-modify-write, radiance_volume.cu:282-301; racy, one GPU only) or TD_OFF
+        (a frozen map: frames sample it and change nothing in it)."""
         check(lib().rt_sarsa_set_td_mode(self._h, mode))
 
     def set_inframe_lanes(self, lanes: int) -> None:
@@ -150,6 +155,33 @@ class RadianceMap:
         check(lib().rt_sarsa_read(self._h, _fp(q), _fp(cdf), vis.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
                                   _fp(acc)))
         return q, cdf, vis, acc
+
+    def write(self, q, visits=None, v0: int = 0) -> None:
+        """The counterpart of read(): Q rows (n, 144) into the volumes [v0, v0 + n); the irradiance
+        estimate and the CDF are recomputed as load_q does; visits (n, 144) are set, or kept when
+        None (rt_sarsa_write)."""
+        qa = np.ascontiguousarray(q, np.float32)
+        if qa.ndim != 2 or qa.shape[1] != SECTORS:
+            raise ValueError(f"q must be (n, {SECTORS}), got {qa.shape}")
+        va = None
+        if visits is not None:
+            va = np.ascontiguousarray(visits, np.uint32)
+            if va.shape != qa.shape:
+                raise ValueError(f"visits must be {qa.shape}, got {va.shape}")
+        check(lib().rt_sarsa_write(self._h, int(v0), qa.shape[0], _fp(qa),
+                                   None if va is None else va.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+
+    def bake(self, scene: Scene, params, v0: int = 0, n: int | None = None, first_sample: int = 0) -> int:
+        """Fill the volumes [v0, v0 + n) (n None: to the end of the map) from ground truth on the
+        device: per sector the luminance of rtmi.probe.radiance at the volume, times the
+        surface's luminance / pi, floored at RADIANCE_THRESHOLD; visits = spp; irradiance and CDF
+        follow (rt_sarsa_bake).  Returns the closest-hit calls."""
+        if n is None:
+            n = self.n_volumes - int(v0)
+        casts = ctypes.c_uint64(0)
+        check(lib().rt_sarsa_bake(self.ctx.handle, scene.handle, self._h, ctypes.byref(params), int(v0), int(n),
+                                  int(first_sample), ctypes.byref(casts), None))
+        return int(casts.value)
 
     def nearest(self, pos: np.ndarray, nrm: np.ndarray) -> np.ndarray:
         p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)

@@ -1,0 +1,201 @@
+// sarsa_write_main.cpp — rt_sarsa_write's range and size arithmetic (csrc/rt_sarsa_host.cpp)
+// under the host sanitizers, with no GPU: a stand-alone program that compiles the host file
+// itself and stands in for what it links against.  "Device" memory is host memory of exactly
+// the requested size (hipMalloc = malloc), so a copy or a rebuild that leaves a volume's rows is
+// an AddressSanitizer report; the ranged rebuild is the kernel's loop on the host.
+//
+//   c++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+//       -D__HIP_PLATFORM_AMD__ -I$ROCM/include tools/sanitize/sarsa_write_main.cpp \
+//       reinforcement-light-rays-pathtracer_amd/csrc/rt_sarsa_host.cpp -o sarsa_write_san && ./sarsa_write_san
+//
+// Prints "sarsa_write: ok" and exits 0 when every case behaves and no sanitizer fired.
+#include <hip/hip_runtime_api.h>
+
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../../include/rtmi.h"
+#include "../../reinforcement-light-rays-pathtracer_amd/csrc/rt_internal.hpp"
+
+// ---- the HIP runtime, on the host ----
+extern "C" {
+hipError_t hipMalloc(void** p, size_t n) {
+    *p = malloc(n ? n : 1);
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void* p) {
+    free(p);
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
+    memcpy(d, s, n);
+    return hipSuccess;
+}
+hipError_t hipMemset(void* d, int v, size_t n) {
+    memset(d, v, n);
+    return hipSuccess;
+}
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) {
+    memset(d, v, n);
+    return hipSuccess;
+}
+hipError_t hipSetDevice(int) { return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+const char* hipGetErrorString(hipError_t) { return "hip stub"; }
+}
+
+// ---- the rest of the library, as far as rt_sarsa_host.cpp refers to it ----
+namespace {
+std::string g_error;
+// two surfaces of area 2 each (a 2 x 2 square)
+const float kTri[18] = {-1, -1, 0, 1, -1, 0, 1, 1, 0, -1, -1, 0, 1, 1, 0, -1, 1, 0};
+const float kNormals[6] = {0, 0, 1, 0, 0, 1};
+const float kAlbedo[6] = {0.75f, 0.5f, 0.25f, 0.1f, 0.9f, 0.4f};
+}  // namespace
+
+namespace rt {
+int set_error(int code, const char* msg) {
+    g_error = msg;
+    return code;
+}
+int ctx_device(const rt_ctx*) { return 0; }
+const DeviceScene& scene_device(const rt_scene*) {
+    static DeviceScene s;
+    return s;
+}
+void scene_host(const rt_scene*, const float** tri, const float** normals, const float** albedo,
+                const float** emission, int* n_surf, int* n_light) {
+    *tri = kTri;
+    *normals = kNormals;
+    *albedo = kAlbedo;
+    *emission = nullptr;
+    *n_surf = 2;
+    *n_light = 0;
+}
+int ctx_blocks(rt_ctx*, const int32_t*, int, int, int, int, const BlockDesc**, int*) { return RT_E_UNSUPPORTED; }
+RenderLaunch render_launch(const rt_scene*, const rt_camera*, const rt_params*) { return RenderLaunch(); }
+int scene_ensure_ctab(const rt_scene*, int, float, bool) { return RT_OK; }
+bool ctab_wanted(const rt_scene*, const rt_camera*, const rt_params*, int) { return false; }
+bool sarsa_prof_compiled() { return false; }
+hipError_t launch_sarsa_render(const RenderLaunch&, const SarsaMap&, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_sarsa_apply(const SarsaMap&, hipStream_t) { return hipErrorNotSupported; }
+hipError_t launch_sarsa_view(const RenderLaunch&, const SarsaMap&, const float4*, int32_t*, int32_t*, float*,
+                             hipStream_t) {
+    return hipErrorNotSupported;
+}
+hipError_t launch_sarsa_nearest(const SarsaMap&, const float*, const float*, int, int32_t*, hipStream_t) {
+    return hipErrorNotSupported;
+}
+
+// rebuild_volume (rt_sarsa.hip) on the host: every array it touches, at the kernel's indices
+static void rebuild_volume(const SarsaMap& m, int v) {
+    const size_t b = (size_t)v * kSarsaSectors;
+    float total = 0.0000000001f;
+    for (int k = 0; k < kSarsaSectors; ++k) {
+        const float t = m.Q[b + k] * m.cos_center[b + k];
+        total += t > 0.0f ? t : 0.0f;
+    }
+    float prev = 0.0f;
+    float* top = reinterpret_cast<float*>(m.cdf_top + (size_t)v * 4);
+    int mi = 0;
+    for (int k = 0; k < kSarsaSectors; ++k) {
+        float t = m.Q[b + k] * m.cos_center[b + k];
+        t = t > 0.0f ? t : 0.0f;
+        const float rad = t / total + prev;
+        m.cdf[b + k] = rad;
+        if (k == 0) top[0] = rad;
+        if (k % kGridRes == kGridRes - 1) top[1 + k / kGridRes] = rad;
+        prev = rad;
+        if (m.Q[b + mi] < m.Q[b + k]) mi = k;
+    }
+    m.qmax[v] = mi;
+}
+hipError_t launch_sarsa_rebuild(const SarsaMap& m, hipStream_t) {
+    for (int v = 0; v < m.n_vol; ++v) rebuild_volume(m, v);
+    return hipSuccess;
+}
+hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStream_t) {
+    if (n <= 0) return hipSuccess;
+    if (v0 < 0 || n > m.n_vol - v0) return hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i) rebuild_volume(m, v0 + i);
+    return hipSuccess;
+}
+}  // namespace rt
+
+#define EXPECT(cond)                                                            \
+    do {                                                                        \
+        if (!(cond)) {                                                          \
+            fprintf(stderr, "line %d: %s (last error: %s)\n", __LINE__, #cond, g_error.c_str()); \
+            return 1;                                                           \
+        }                                                                       \
+    } while (0)
+
+int main() {
+    rt_ctx* ctx = reinterpret_cast<rt_ctx*>(&g_error);  // opaque to the host file: never dereferenced
+    const rt_scene* scene = reinterpret_cast<const rt_scene*>(&g_error);
+    rt_sarsa* map = nullptr;
+    EXPECT(rt_sarsa_create_density(ctx, scene, 1984, 0.3f, &map) == RT_OK);
+    int32_t n = 0;
+    EXPECT(rt_sarsa_info(map, &n, nullptr, nullptr) == RT_OK);
+    EXPECT(n == 12);  // floor(2 / 0.3) per surface
+    const size_t S = 144;
+    std::vector<float> q0(n * S), cdf0(n * S), irr0(n), q(n * S), cdf(n * S), irr(n);
+    std::vector<uint32_t> vis0(n * S), vis(n * S);
+    EXPECT(rt_sarsa_read(map, q0.data(), cdf0.data(), vis0.data(), irr0.data()) == RT_OK);
+
+    // exactly sized inputs: a read past n x 144 is a heap overflow report
+    auto rows = [&](int count, float base) {
+        std::vector<float> r((size_t)count * S);
+        for (size_t i = 0; i < r.size(); ++i) r[i] = base + 0.001f * (float)(i % 97);
+        return r;
+    };
+    // refusals leave the map alone
+    const std::vector<float> two = rows(2, 0.5f);
+    EXPECT(rt_sarsa_write(nullptr, 0, 1, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, -1, 1, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, 0, -1, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, n - 1, 2, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, n, 1, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, n + 1, 0, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, 0x7fffffff, 0x7fffffff, two.data(), nullptr) == RT_E_INVALID);  // v0 + n overflows int
+    EXPECT(rt_sarsa_write(map, 0x7fffffff, 1, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, 1, 0x7fffffff, two.data(), nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_write(map, 0, 1, nullptr, nullptr) == RT_E_INVALID);
+    EXPECT(rt_sarsa_read(map, q.data(), cdf.data(), vis.data(), irr.data()) == RT_OK);
+    EXPECT(q == q0 && cdf == cdf0 && vis == vis0 && irr == irr0);
+    // n = 0 anywhere inside [0, n_vol], q may be NULL
+    EXPECT(rt_sarsa_write(map, 0, 0, nullptr, nullptr) == RT_OK);
+    EXPECT(rt_sarsa_write(map, n, 0, nullptr, nullptr) == RT_OK);
+
+    // the last volume alone, the first, an inner range with visits, the whole map
+    struct Case {
+        int v0, count;
+        bool visits;
+    } cases[] = {{n - 1, 1, false}, {0, 1, true}, {3, 5, true}, {0, n, false}, {0, n, true}};
+    for (const Case& c : cases) {
+        EXPECT(rt_sarsa_read(map, q0.data(), cdf0.data(), vis0.data(), irr0.data()) == RT_OK);
+        const std::vector<float> in = rows(c.count, 0.25f + 0.1f * (float)c.v0);
+        const std::vector<uint32_t> vin((size_t)c.count * S, 7u + (uint32_t)c.v0);
+        EXPECT(rt_sarsa_write(map, c.v0, c.count, in.data(), c.visits ? vin.data() : nullptr) == RT_OK);
+        EXPECT(rt_sarsa_read(map, q.data(), cdf.data(), vis.data(), irr.data()) == RT_OK);
+        for (int v = 0; v < n; ++v) {
+            const bool inside = v >= c.v0 && v < c.v0 + c.count;
+            for (size_t k = 0; k < S; ++k) {
+                const size_t e = (size_t)v * S + k;
+                EXPECT(q[e] == (inside ? in[(size_t)(v - c.v0) * S + k] : q0[e]));
+                EXPECT(vis[e] == (inside && c.visits ? vin[0] : vis0[e]));
+                if (!inside) EXPECT(cdf[e] == cdf0[e]);
+            }
+            if (!inside) EXPECT(irr[v] == irr0[v]);
+            if (inside) EXPECT(cdf[(size_t)v * S + S - 1] > 0.999f && cdf[(size_t)v * S + S - 1] < 1.001f && irr[v] > 0.f);
+        }
+    }
+    EXPECT(rt_sarsa_destroy(map) == RT_OK);
+    printf("sarsa_write: ok\n");
+    return 0;
+}
