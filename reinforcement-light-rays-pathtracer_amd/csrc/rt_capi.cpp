@@ -1270,7 +1270,7 @@ int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* 
         RT_HIP(hipFree(a.prof));
         fprintf(stderr, "{\"ps_prof\": {\"primary\": %llu, \"shade\": %llu, \"masks\": %llu, \"exact\": %llu, "
                         "\"bounce_total\": %llu, \"trips\": %llu, \"light_passes\": %llu, \"sparse_trips\": %llu, "
-                        "\"max_pool\": %llu, \"pretest\": %llu}}\n", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8],
+                        "\"max_settle\": %llu, \"pretest\": %llu}}\n", v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8],
                 v[9]);
     }
     return RT_OK;

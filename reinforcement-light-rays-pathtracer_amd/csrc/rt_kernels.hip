@@ -629,20 +629,16 @@ __global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
     }
 }
 
-// The table-route kernel defers the retraces of the light pre-test to one pooled trip of the
-// workgroup (ps_pool) instead of keeping each in its lane for the wave's next trip.
-#ifndef RT_PS_POOL_SPAN
-// entries of the pooled trip a wave takes per step.  Cornell workgroups defer 10-35 samples, so
-// at 64 the first wave serves them all in one step; a build with a small span (4) puts the same
-// frames through every wave and through several steps (test builds)
-#define RT_PS_POOL_SPAN 64
-#endif
-// whether k_render_ps<.., MF, CT> runs the pooled trip: its two barriers are compiled in or not
-// with this constant alone, never chosen at run time
+// The table-route kernel does not keep a light pre-test pass in its lane for the wave's next
+// trip: the wave settles the pass on the spot (ps_body's pipelined loop).  Whether
+// k_render_ps<.., MF, CT> is that variant (the name is from the pooled trip of the workgroup that
+// traced the passes before, DESIGN.md section 7, rounds 7 and 10): a constant of the template, never
+// chosen at run time
 __host__ __device__ constexpr bool ps_pooled(int mf, bool ct) { return ct && mf == 1; }
-// a deferred sample's slot code: the surface to shade (the terminal ray's origin) and the
-// path's first surface -- the table route has at most 64 triangles, so 6 bits each
-__device__ __forceinline__ int ps_defer_code(int hit_tri, int f_tri0) { return (1 << 12) | (f_tri0 << 6) | hit_tri; }
+// lane l's value of v (l wave-uniform)
+__device__ __forceinline__ float readlane_f(float v, int l) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
+}
 
 // the next direction from the surface hit (pos, hit_tri) at bounce depth dep of sample cur of
 // pixel lpix: cos theta and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the
@@ -778,13 +774,10 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
 // the work of k_render_ps for one wave with at least one pixel; returns the lane's casts.
 // CT: the bounce casts from the scene's candidate table (the launcher checked it serves this
 // launch) -- the matrix-core path is not compiled in, so the kernel's registers allow more waves.
-// With the pooled trip (ps_pooled) the wave stops after its bounce loop: *n_deferred is the
-// number of samples it left for ps_pool (listed at the front of its queue), and the kernel runs
-// ps_finish after the pool; otherwise the wave finishes here.
 template <int SAMPLER, int RULE, int MF, bool CT = false>
 __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceScene& ms, float* wl,
                                             const BlockDesc& blk, int q, int chunk, int lane, int lx, int ly, int px,
-                                            int py, bool valid, int* n_deferred) {
+                                            int py, bool valid) {
     extern __shared__ float s_ps[];
     const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
     const float4* __restrict__ shade = ms.shade;  // (the workgroup's LDS copy, when the kernel staged one)
@@ -924,27 +917,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     bool live = false;
     // the slot of the live path's sample
     auto own_slot = [&]() -> float* { return wslots + (own_e >> 6) * kPsFields * 64 + (own_e & 63); };
-    // Deferred samples (ps_pooled): a lane whose light pre-test passed has re-parked its sample
-    // (`deferred`, set in the loop below) and lists the slot's entry at the front of the wave's
-    // queue, for ps_pool.  The front is dead: every deferred sample was claimed before, so
-    // n_def <= q_next and no unclaimed entry is overwritten.
-    int n_def = 0;        // wave-uniform
-    bool deferred = false;
-    auto list_deferred = [&](bool def, int e) {  // wave-level: the lanes with def list their entry e
-        const uint64_t dm = __ballot(def);
-        if (dm != 0ull) {
-            if (def)
-                queue[n_def + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32),
-                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u))] =
-                    (uint16_t)e;
-            n_def += __builtin_popcountll(dm);
-        }
-    };
     auto claim = [&]() {  // wave-level: lanes without a path take the next queued samples
-        if constexpr (ps_pooled(MF, CT)) {
-            list_deferred(deferred, own_e);
-            deferred = false;
-        }
         const uint64_t need = __ballot(!live);
         if (need == 0ull || q_next >= q_total) return;
         const int j = q_next + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
@@ -984,19 +957,15 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     // percent of rays) -> the path stays live and the next trip traces the same ray (same
     // Philox draw) in full.  Terminal casts thus stop taking slots of the matrix-core trips:
     // the image and the ray casts are k_render's bit for bit.
-    // With the pooled trip (ps_pooled) a pass does not stay in its lane: those retraces arrive
-    // after the wave's queue has drained, so most waves ran one more trip with a handful of live
-    // lanes at the cost of a full one.  The lane re-parks the sample in its slot (the hit point
-    // to shade, and ps_defer_code as its code) and is free for new work; ps_pool traces the
-    // workgroup's deferred samples together once its four waves are done.  The terminal ray and
-    // its fold need (pos, hit_tri, f_tri0) and draws keyed by the slot alone, so nothing else is
-    // kept.  (`pool` is always true in the pooled variant: launch_render refuses the CPU preset
-    // above two bounces.)
+    // In the table-route variant (ps_pooled) a pass does not stay in its lane either: those
+    // retraces arrive after the wave's queue has drained, so most waves ran one more trip with a
+    // handful of live lanes at the cost of a full one.  The wave settles the pass where the
+    // pre-test finds it (pretest_pending, below).
     const bool split = use_mf && a.max_bounces >= 1 &&
                        (a.scene.n_tri - n_surf) <= kPsSplitLights;
-    const bool pool = ps_pooled(MF, CT) && a.max_bounces <= 2;
 #if RT_PROF
     unsigned n_pass = 0;  // the lane's light pre-test passes
+    unsigned max_settle = 0;  // wave-uniform: the most lanes settled in one pre-test pass
 #endif
     // the pre-test of the terminal ray from (pos, hit_tri) at depth dep = max_bounces - 1
     auto light_pass = [&](int dep) -> bool {
@@ -1009,32 +978,29 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     uint64_t t_pre = 0;  // wave cycles inside the light pre-test
 #endif
     bool piped = false;  // the pipelined loop has done the bounces: the loop after it does not run
-    // The pipelined loop (pooled trip with the pre-test on: every live lane ends its path in
-    // the trip that claimed it, so every trip starts with all lanes free and the paths at depth
-    // 0).  Invariant: deferrals come only from this loop.  launch_render refuses the CPU preset
-    // above two bounces, so in the pooled variant `pool` is true, this loop runs whenever the
-    // pre-test is on, and the loop after it runs only with the pre-test off: its deferral
-    // branch, the `deferred` flag and its listing in claim() never execute.  (Deleting them was
-    // measured and cost 2.6 % of the bench frame through register allocation alone: DESIGN.md
-    // §7, round 9.)  The cast's table lookup opens with two dependent global loads that nothing in the
-    // lane's own chain covers, and the pre-test that follows a surface hit shares no data with
-    // the lane's next sample.  So a sample whose cast hit a surface does not run its pre-test on
+    // The pipelined loop (the table-route variant with the pre-test on: every live lane ends its
+    // path in the trip that claimed it, so every trip starts with all lanes free and the paths at
+    // depth 0; launch_render refuses the CPU preset above two bounces).  In this variant the loop
+    // after it runs only with the pre-test off.  The cast's table lookup opens with two dependent
+    // global loads that nothing in the lane's own chain covers, and the pre-test that follows a
+    // surface hit shares no data with the lane's next sample.  So a sample whose cast hit a surface does not run its pre-test on
     // the spot: the lane keeps it as pending (the hit point, and the slot's entry packed with
     // the two triangles) and goes free.  Next trip: claim, shade the new sample, issue its lookup
     // (closest_hit_ctab_begin), then run the pending sample's pre-test -- its keys re-derived
-    // from the entry as claim() derives them -- store its value or its deferral and list the
-    // deferrals (their samples were claimed a trip ago: n_def <= q_next holds), and only then
+    // from the entry as claim() derives them -- settle the passes, store its value, and only then
     // use the lookup's words (closest_hit_ctab_finish).  Loads return in the order of their
     // issue, so a wait inside the pre-test for its surface's shading frame would wait for the
     // lookup's words as well: the frame is loaded where the sample becomes pending, ahead of the
     // next trip's loads, and pinned in registers (ps_pin) at the top of that trip, on every
     // path.  (Pinned later, after the new sample's shading on one path and where a lane has no
-    // new sample on the other, the compiler still waits inside the pre-test.)  Every sample runs
+    // new sample on the other, the compiler still waits inside the pre-test.)  The fold of a
+    // settled ray that ends on a light loads its rows from global memory and so waits for the
+    // lookup's words too: it is under its own branch, off the common path.  Every sample runs
     // the same float operations on the same operands as in the loop below, and the casts are
     // counted at the same events: the image and the ray casts are unchanged.  When the queue has
     // drained, the pre-tests still pending run after the loop.  Nothing but the pending sample
     // and wave-uniform counters is carried from trip to trip.
-    if constexpr (ps_pooled(MF, CT)) piped = pool && split;
+    if constexpr (ps_pooled(MF, CT)) piped = split;
     if constexpr (ps_pooled(MF, CT)) {
         if (piped) {
             const CtabDev& tab = ms.ctab[RULE];
@@ -1042,29 +1008,77 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
             f3 p_pos = make3(0.0f, 0.0f, 0.0f);
             int p_pack = 0;  // the entry << 12 | f_tri0 << 6 | hit_tri
             float4 pN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pT = pN, pB = pN;  // its surface's shading frame
-            // the pending samples' pre-tests and the listing of those that pass (wave-level)
+            // the pending samples' pre-tests, the passes settled on the spot (wave-level)
             auto pretest_pending = [&]() {
 #if RT_PROF
                 const uint64_t tp = __builtin_amdgcn_s_memtime();
 #endif
                 const int e = p_pack >> 12, ol = e & 63, kk = e >> 6;
                 bool pass = false;
+                PsKeys key;
+                key.pix = 0u;
+                key.cur = 0;
+                float c = 0.0f;
+                f3 lo = cam, ld = make3(0.0f, 0.0f, 1.0f);
                 if (pend) {
-                    const PsKeys key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), e);
-                    float c;
-                    f3 lo, ld;
+                    key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), e);
                     ps_shade_dir<SAMPLER>(a, pN, pT, pB, key.pix, key.cur, a.max_bounces - 1, p_pos, &c, &lo, &ld);
                     pass = ps_light_pass<RULE>(a, ms, lo, ld);
-                    f3 v = make3(0.0f, 0.0f, 0.0f);
-                    if (pass) {
-                        // the retrace waits for ps_pool: the hit to shade goes back into the slot
-                        v = p_pos;
-                        set_code_at(kk, ol, (1 << 12) | (p_pack & 4095));  // ps_defer_code(hit_tri, f_tri0)
+                }
+                // The passes are settled here, one ray at a time by the whole wave: lane j tests
+                // triangle j against the passing lane's ray (exact_tv on the LDS records, the
+                // function the cast's own-lane tests and shared phase call), and the scan's window
+                // runs in index order over the triangles that pass.  A triangle outside the
+                // table's candidate mask fails the test for this ray and a failing one is +inf,
+                // which no window accepts: `tri` is the cast's hit.
+                int tri = -1;
+                uint64_t pm = __ballot(pass);
+                if (pm != 0ull) {
 #if RT_PROF
-                        ++n_pass;
+                    n_pass += pass ? 1u : 0u;
+                    max_settle = max(max_settle, (unsigned)__builtin_popcountll(pm));
 #endif
-                    } else {
-                        ++n_casts;  // the terminal cast: no light triangle can be its hit
+                    const float nDx = -(ld.x * a.t_scale), nDy = -(ld.y * a.t_scale), nDz = -(ld.z * a.t_scale);
+                    do {
+                        const int pl = __builtin_ctzll(pm);
+                        pm &= pm - 1ull;
+                        const f3 ro = make3(readlane_f(lo.x, pl), readlane_f(lo.y, pl), readlane_f(lo.z, pl));
+                        const float rx = readlane_f(nDx, pl), ry = readlane_f(nDy, pl), rz = readlane_f(nDz, pl);
+                        float tj = __builtin_inff();
+                        if (lane < a.scene.n_tri) tj = exact_tv<RULE>(ms.isect, lane, ro, rx, ry, rz);
+                        uint64_t hits = __ballot(tj != __builtin_inff());
+                        float best = (RULE == 0) ? FLT_MAX : 999999.0f;
+                        int bt = -1;
+                        while (hits != 0ull) {
+                            const int b = __builtin_ctzll(hits);
+                            hits &= hits - 1ull;
+                            const float t = readlane_f(tj, b);
+                            if ((RULE == 0) ? (t < best + kEps) : (t < best)) {
+                                best = t;
+                                bt = b;
+                            }
+                        }
+                        tri = (lane == pl) ? bt : tri;
+                    } while (pm != 0ull);
+                }
+                if (pend) {
+                    ++n_casts;  // the terminal cast: settled above, or no light triangle can be its hit
+                    f3 v = make3(0.0f, 0.0f, 0.0f);
+                    if (tri >= n_surf) {
+                        // a light: its emission folded back through both bounces, as the general
+                        // loop folds it (the pre-test's own cos at this surface, then the path's
+                        // first surface with the cos its shading at depth 0 drew)
+                        const int dep = a.max_bounces - 1;
+                        const float4 em = shade[tri * kShadeF4 + 3];
+                        v = make3(em.x, em.y, em.z);
+                        if (dep >= 1) ps_fold<SAMPLER>(shade, v, p_pack & 63, c);
+                        float f_c0 = c;
+                        if (SAMPLER == 0 && dep >= 1) {
+                            float r1, r2;
+                            draw2(key.pix, (uint32_t)key.cur, 1u, a.seed_lo, a.seed_hi, &r1, &r2);
+                            f_c0 = r1;
+                        }
+                        ps_fold<SAMPLER>(shade, v, (p_pack >> 6) & 63, f_c0);
                     }
                     float* own = wslots + kk * kPsFields * 64 + ol;
                     own[0 * 64] = v.x;
@@ -1072,7 +1086,6 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
                     own[2 * 64] = v.z;
                     pend = false;
                 }
-                list_deferred(pass, e);
 #if RT_PROF
                 t_pre += __builtin_amdgcn_s_memtime() - tp;
 #endif
@@ -1226,14 +1239,6 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
 #if RT_PROF
                     ++n_pass;
 #endif
-                    if (pool) {
-                        // the retrace waits for ps_pool: the hit to shade goes back into the slot
-                        // in place of a value (below), and the next claim() lists the slot
-                        L = pos;
-                        set_code_at(own_e >> 6, own_e & 63, ps_defer_code(hit_tri, f_tri0));
-                        deferred = true;
-                        terminal = true;
-                    }
                 }
             }
         }
@@ -1251,102 +1256,10 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     if (a.prof != nullptr && lane == 0) {
         for (int i = 0; i < 8; ++i) atomicAdd(a.prof + i, (unsigned long long)pt[i]);
         atomicAdd(a.prof + 9, (unsigned long long)t_pre);
+        atomicMax(a.prof + 8, (unsigned long long)max_settle);
     }
 #endif
-    *n_deferred = n_def;
-    // (with the pooled trip the kernel finishes the wave after ps_pool; acc is still 0 there)
-    if constexpr (!ps_pooled(MF, CT)) ps_finish(a, blk, chunk, lane, lx, ly, valid, acc);
-    return n_casts;
-}
-
-// The pooled trip of k_render_ps (ps_pooled): the terminal casts that the four waves of the
-// workgroup deferred (counts[w] entries at the front of wave w's queue), traced together.
-// Every wave of the workgroup calls this between the kernel's two pool barriers, also a wave
-// without pixels.  Wave w takes entries [64 w, 64 w + 64) of the concatenated list, and again in
-// steps of 256 while entries remain (64: RT_PS_POOL_SPAN).  A lane shades its entry's parked
-// hit at depth max_bounces - 1 with the owner's keys (pixel and sample from the owner's wave,
-// slot and lane, as claim() derives them), traces the ray in full and folds a light hit back as
-// the bounce loop does -- the same functions on the same operands, so the same bits -- then
-// writes the sample's value (0 for a surface or a miss) into the owner's slot.  Returns the
-// lane's casts.
-template <int SAMPLER, int RULE>
-__device__ __forceinline__ unsigned ps_pool(const RenderLaunch& a, const DeviceScene& ms, float* wl,
-                                            const BlockDesc& blk, int q0, int lane, const unsigned* counts) {
-    extern __shared__ float s_ps[];
-    const float4* __restrict__ shade = ms.shade;
-    const int pc = a.per_chunk;
-    const int c0 = (int)counts[0], c1 = (int)counts[1], c2 = (int)counts[2];
-    const int total = ((c0 + c1) + c2) + (int)counts[3];
-    const int dep = a.max_bounces - 1;
-    unsigned n_casts = 0;
-#if RT_PROF
-    uint64_t trips = 0, sparse = 0;
-    const uint64_t t0 = __builtin_amdgcn_s_memtime();
-#endif
-    constexpr int span = RT_PS_POOL_SPAN;
-    static_assert(span >= 1 && span <= 64, "a wave takes at most one entry per lane");
-    for (int base = (int)(threadIdx.x >> 6) * span; base < total; base += 4 * span) {  // wave-uniform bounds
-        const bool has = lane < span && base + lane < total;
-        int j = base + lane, ow = 0;  // owner wave and position in its list
-        if (j >= c0) { j -= c0; ow = 1; }
-        if (ow == 1 && j >= c1) { j -= c1; ow = 2; }
-        if (ow == 2 && j >= c2) { j -= c2; ow = 3; }
-        float* own = s_ps;
-        int hit_tri = 0, f_tri0 = 0, cur = 0;
-        uint32_t lpix = 0;
-        float s_cos = 0.0f;
-        f3 o = make3(0.0f, 0.0f, 0.0f), d = make3(0.0f, 0.0f, 1.0f);
-        if (has) {
-            float* const ws = s_ps + (size_t)ow * ps_wave_floats(pc);
-            const uint16_t* oqueue = reinterpret_cast<const uint16_t*>(ws + pc * kPsFields * 64 + pc * 32);
-            const uint32_t e = oqueue[j];
-            const int ol = (int)(e & 63u), kk = (int)(e >> 6);
-            own = ws + kk * kPsFields * 64 + ol;
-            const int code = (int)reinterpret_cast<const int16_t*>(ws + pc * kPsFields * 64)[kk * 64 + ol];
-            hit_tri = code & 63;
-            f_tri0 = (code >> 6) & 63;
-            const int ot = ow * 64 + ol;  // the owner's threadIdx.x
-            const int oq = q0 + (ot >> a.split_log2);
-            lpix = (uint32_t)(blk.py0 + (oq >> 4)) * (uint32_t)a.width + (uint32_t)(blk.px0 + (oq & 15));
-            cur = (ot & (a.split - 1)) * pc + kk;
-            const f3 pos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
-            ps_shade_hit<SAMPLER>(a, shade, lpix, cur, dep, pos, hit_tri, &s_cos, &o, &d);
-        }
-#if RT_PROF
-        trips += 1;
-        sparse += __builtin_popcountll(__ballot(has)) < 16 ? 1 : 0;
-#endif
-        // wave-level: a lane without an entry casts a finite ray with no candidates
-        const Hit h = closest_hit_ctab<RULE, 1, kCtPairCap>(ms, ms.ctab[RULE], hit_tri, o, d, a.t_scale, has, wl);
-        if (has) {
-            ++n_casts;
-            f3 L = make3(0.0f, 0.0f, 0.0f);
-            if (h.tri >= a.scene.n_surf) {
-                const float4 e = shade[h.tri * kShadeF4 + 3];
-                L = make3(e.x, e.y, e.z);
-                if (dep >= 1) ps_fold<SAMPLER>(shade, L, hit_tri, s_cos);
-                // cos theta of the path's first bounce: the draw its shading at depth 0 used
-                float f_cos0 = s_cos;
-                if (SAMPLER == 0 && dep >= 1) {
-                    float r1, r2;
-                    draw2(lpix, (uint32_t)cur, 1u, a.seed_lo, a.seed_hi, &r1, &r2);
-                    f_cos0 = r1;
-                }
-                ps_fold<SAMPLER>(shade, L, f_tri0, f_cos0);
-            }
-            own[0 * 64] = L.x;
-            own[1 * 64] = L.y;
-            own[2 * 64] = L.z;
-        }
-    }
-#if RT_PROF
-    if (a.prof != nullptr && lane == 0) {
-        atomicAdd(a.prof + 4, (unsigned long long)(__builtin_amdgcn_s_memtime() - t0));
-        atomicAdd(a.prof + 5, (unsigned long long)trips);
-        atomicAdd(a.prof + 7, (unsigned long long)sparse);
-        if (threadIdx.x == 0) atomicMax(a.prof + 8, (unsigned long long)total);
-    }
-#endif
+    ps_finish(a, blk, chunk, lane, lx, ly, valid, acc);
     return n_casts;
 }
 
@@ -1407,23 +1320,10 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
         }
         __syncthreads();
     }
-    int n_def = 0;  // the wave's samples left for the pooled trip
+    // (a wave without pixels does nothing until the casts barrier below, the kernel's only one
+    // after the staging)
     unsigned n_casts = 0;
-    if (vmask != 0ull)
-        n_casts = ps_body<SAMPLER, RULE, MF, CT>(a, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid, &n_def);
-    if constexpr (ps_pooled(MF, CT)) {
-        // The pooled trip.  Its two barriers stand here, at the kernel's top level: outside every
-        // loop and under no condition but the template's constant, so all four waves reach both
-        // -- a wave without pixels too (it skipped ps_body above, publishes 0 and serves the
-        // pool like the others), and also a launch that defers nothing (the light pre-test off).
-        // wg_casts carries the waves' deferred counts first; the second barrier frees it for
-        // the casts below and makes the pool's values visible to the slots' owners.
-        if (lane == 0) wg_casts[threadIdx.x >> 6] = (unsigned)n_def;
-        __syncthreads();
-        n_casts += ps_pool<SAMPLER, RULE>(a, ms, wl, blk, q - ((int)threadIdx.x >> lg), lane, wg_casts);
-        __syncthreads();
-        if (vmask != 0ull) ps_finish(a, blk, chunk, lane, lx, ly, valid, make3(0.0f, 0.0f, 0.0f));
-    }
+    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT>(a, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
     if (a.casts != nullptr) {
         const unsigned total = wave_sum(n_casts);
         if (lane == 0) wg_casts[threadIdx.x >> 6] = total;
