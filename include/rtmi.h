@@ -646,6 +646,73 @@ int rt_render_volume_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sa
                                        const int32_t* tiles, int n_tiles, int tile_size, float* d_out,
                                        void* stream);
 
+/* The k nearest radiance volumes, and the irradiance render of the map on top of them: the CPU
+ * engine's fifth drawing mode, draw_radiance_map_path_tracing
+ * (Old_CPU_Rendering_Engine/Source/path_tracing/precompute_irradiance_path_tracing.cpp:3-53): one
+ * camera ray per sample, no bounce, the pixel the map's own irradiance estimate at the hit point,
+ * interpolated over the closest volumes (RadianceMap::get_irradiance_estimate,
+ * radiance_map.cpp:93-128; RadianceTree::find_closest_radiance_volumes(n, max_dist, position,
+ * normal), radiance_tree.cpp:111-177; CLOSEST_QUERY_COUNT and MAX_DIST,
+ * constants/radiance_volumes_settings.h:14-15).
+ *
+ * rt_sarsa_knn (k_sarsa_knn): for query (p, N) let S be the volumes v whose stored normal equals
+ *   N component by component under float == (the reference's rv_normal != vec3(normal) test) and
+ *   whose distance d(v) = sqrtf((x x + y y) + z z) of vol_pos[v] - p, every operation rounded on
+ *   its own, is < radius.  The result is the min(k, |S|) members of S ascending by (d, v): nearest
+ *   first, equal float distances by volume index.  out_vol, out_dist: n x k, unused slots -1 and
+ *   +inf; out_count: that number.  A query with a non-finite coordinate, or a normal no volume has,
+ *   finds nothing.  The result of a query depends on neither n nor its place in the list.
+ *   The search reads the per-normal grid of the map (whatever rt_sarsa_set_search says), which
+ *   answers exactly up to rt_sarsa_knn_reach's radius: the grid's accept radius,
+ *   sqrt(MAX_DIST) * 0.999 ~ 0.0547; 0 for a map without a grid (host only).
+ *   Unlike the reference: its tree walk prunes subtrees by |delta| < max_dist and never tests a
+ *   volume's own distance, so with fewer than n volumes in range it can return farther ones.  This
+ *   entry never returns a volume at or beyond radius.  Expected neighbours at the reach are
+ *   pi reach^2 / area_per_sample: 9.4 at the default 0.001, under 1 at 0.01.
+ *   RT_E_INVALID: k outside [1, RT_SARSA_KNN_MAX] or radius not > 0 (both checked before any
+ *   pointer), NULL arguments, radius beyond the reach; RT_E_UNSUPPORTED: a map without a grid
+ *   (there is no other method behind it).
+ * rt_render_irradiance (k_sarsa_irr): per sample s in [first_sample, first_sample + spp) of every
+ *   pixel, rt_render_volume_view's camera ray, closest hit and hit point (out_tri and out_pos are
+ *   that call's, bit for bit); at a surface hit the opts->k nearest volumes of (hit point, the
+ *   surface's stored normal) within opts->radius as rt_sarsa_knn finds them, e_i = irradiance[v_i]
+ *   * ((2 pi) / 144) of each (rt_sarsa_read's fourth array), nearest first, and
+ *     RT_IRR_MEAN: L = ((e_0 + e_1) + ..) / count -- the reference (its barycentric branch tests
+ *                  u + v + w == 1.f on floats and in practice falls through to this mean);
+ *     RT_IRR_CONE: w_i = 1 - d_i / radius, L = ((w_0 e_0 + w_1 e_1) + ..) / ((w_0 + w_1) + ..),
+ *                  the mean where the weights sum to 0;
+ *   L = 0 with no volume in range (the reference returns vec3(0)).  The sample is (L, L, L), or
+ *   with opts->tint != 0 albedo * (L / luminance), luminance = 0.5 (max + min) of the albedo (the
+ *   reference's irradiance *= diffuse_c; 0 where the luminance is 0).  A light gives its emission,
+ *   a miss params->env_light.  Every operation is IEEE fp32, rounded once.  The pixel is the sum of
+ *   its spp_split chunk sums in order, divided by spp.  max_bounces and sampler are ignored.
+ *   out_vol, out_dist (W x H x k, may be NULL): the volumes of sample first_sample and their
+ *   distances (-1, +inf: none, or no surface hit).  The map is read only in every TD mode, and
+ *   not even rt_sarsa_search_stats' kd_fallbacks moves.  Refusals as rt_sarsa_knn's (opts->k,
+ *   opts->radius and opts->weight by value first) and rt_render_volume_view's.
+ * rt_render_irradiance_tiles_device: the same over a tile list into device memory, stream-ordered;
+ *   tiles and output layout as rt_render_sarsa_tiles_device. */
+#define RT_SARSA_KNN_MAX 8
+#define RT_IRR_MEAN 0 /* the reference: the plain average of the volumes found */
+#define RT_IRR_CONE 1 /* weights 1 - d / radius */
+typedef struct {
+    int32_t k;      /* volumes to interpolate over, [1, RT_SARSA_KNN_MAX] (CLOSEST_QUERY_COUNT) */
+    float radius;   /* (0, rt_sarsa_knn_reach] */
+    int32_t weight; /* RT_IRR_MEAN / RT_IRR_CONE */
+    int32_t tint;   /* != 0: times the surface's albedo / luminance */
+} rt_irr_opts;
+int rt_sarsa_knn_reach(const rt_sarsa* sarsa, float* radius);
+int rt_sarsa_knn(rt_ctx* ctx, const rt_sarsa* sarsa, const float* pos /* n x 3 */, const float* normal /* n x 3 */,
+                 int n, int k, float radius, int32_t* out_vol /* n x k */, float* out_dist /* n x k, may be NULL */,
+                 int32_t* out_count /* n, may be NULL */);
+int rt_render_irradiance(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa, const rt_camera* cam,
+                         const rt_params* params, const rt_irr_opts* opts, uint32_t first_sample, float* out_rgb,
+                         int32_t* out_tri, float* out_pos, int32_t* out_vol /* W x H x k */,
+                         float* out_dist /* W x H x k */);
+int rt_render_irradiance_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa, const rt_camera* cam,
+                                      const rt_params* params, const rt_irr_opts* opts, uint32_t first_sample,
+                                      const int32_t* tiles, int n_tiles, int tile_size, float* d_out, void* stream);
+
 /* ---- ground-truth incident radiance at surface points ------------------------
  * Replaces no reference interface: the thesis judges what a radiance map or a Q-network
  * learned against "the true incident radiance distribution" at selected points, "calculated by

@@ -477,6 +477,13 @@ hipError_t launch_sarsa_nearest(const SarsaMap& m, const float* pos, const float
 // out_tri / out_vol / out_pos: optional per-pixel AOVs of that first sample, in r.out's pixel layout
 hipError_t launch_sarsa_view(const RenderLaunch& r, const SarsaMap& m, const float4* colours, int32_t* out_tri,
                              int32_t* out_vol, float* out_pos, hipStream_t stream);
+// the k nearest same-normal volumes within radius (k_sarsa_knn; a map with a grid, radius <= grid_h):
+// out_vol / out_dist [n][k] ascending by (distance, volume), -1 / +inf past out_count[i]
+hipError_t launch_sarsa_knn(const SarsaMap& m, const float* pos, const float* nrm, int n, int k, float radius,
+                            int32_t* out_vol, float* out_dist, int32_t* out_count, hipStream_t stream);
+// the irradiance render (k_sarsa_irr): r as launch_sarsa_view's; out_vol / out_dist [pixel][k]
+hipError_t launch_sarsa_irr(const RenderLaunch& r, const SarsaMap& m, int k, float radius, int cone, int tint,
+                            int32_t* out_tri, float* out_pos, int32_t* out_vol, float* out_dist, hipStream_t stream);
 
 hipError_t launch_intersect(const DeviceScene& s, const float* orig, const float* dir, int n,
                             float t_scale, int hit_rule, int use_filter, float* out_t,

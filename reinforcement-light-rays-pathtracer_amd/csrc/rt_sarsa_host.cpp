@@ -1304,4 +1304,170 @@ int rt_render_volume_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sa
                       nullptr, (hipStream_t)stream);
 }
 
+int rt_sarsa_knn_reach(const rt_sarsa* sa, float* radius) {
+    if (!sa || !radius) return err(RT_E_INVALID, "NULL argument");
+    *radius = sa->grid_cells > 0 ? sa->m.grid_h : 0.0f;
+    return RT_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// what rt_sarsa_knn and rt_render_irradiance refuse by value, before any handle is looked at
+int check_knn_values(int k, float radius) {
+    if (k < 1 || k > RT_SARSA_KNN_MAX)
+        return err(RT_E_INVALID, "k = " + std::to_string(k) + " outside [1, " + std::to_string(RT_SARSA_KNN_MAX) + "]");
+    if (!(radius > 0.0f)) return err(RT_E_INVALID, "radius must be > 0");
+    return RT_OK;
+}
+
+// ... and by the map: a grid, and a radius within its reach
+int check_knn_map(const rt_sarsa* sa, float radius) {
+    if (sa->grid_cells <= 0)
+        return err(RT_E_UNSUPPORTED, "the map has no nearest-volume grid: no k-nearest search");
+    if (!(radius <= sa->m.grid_h))
+        return err(RT_E_INVALID, "radius " + std::to_string(radius) + " beyond the grid's reach " +
+                                 std::to_string(sa->m.grid_h) + " (rt_sarsa_knn_reach)");
+    return RT_OK;
+}
+
+int check_irr_opts(const rt_irr_opts* o) {
+    if (!o) return RT_OK;  // (refused as a NULL argument by the caller)
+    const int rc = check_knn_values(o->k, o->radius);
+    if (rc != RT_OK) return rc;
+    if (o->weight != RT_IRR_MEAN && o->weight != RT_IRR_CONE) return err(RT_E_INVALID, "bad weight mode");
+    return RT_OK;
+}
+
+// one irradiance launch (rt_render_irradiance*): reads the map, moves no counter of it
+int irr_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const rt_params* p, const rt_irr_opts* o,
+              uint32_t first_sample, const rt::BlockDesc* d_blocks, int n_blocks, int out_pitch, float* d_out,
+              int32_t* d_tri, float* d_pos, int32_t* d_vol, float* d_dist, hipStream_t stream) {
+    rt::RenderLaunch a = rt::render_launch(scene, cam, p);
+    a.blocks = d_blocks;
+    a.n_blocks = n_blocks;
+    a.clip_x1 = p->width;
+    a.clip_y1 = p->height;
+    a.out_pitch = out_pitch;
+    a.out = d_out;
+    a.sample_base = first_sample;
+    RT_HIPE(rt::launch_sarsa_irr(a, sa->m, o->k, o->radius, o->weight == RT_IRR_CONE, o->tint != 0, d_tri, d_pos, d_vol,
+                                 d_dist, stream));
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_sarsa_knn(rt_ctx* ctx, const rt_sarsa* sa, const float* pos, const float* normal, int n, int k, float radius,
+                 int32_t* out_vol, float* out_dist, int32_t* out_count) {
+    int rc = check_knn_values(k, radius);
+    if (rc != RT_OK) return rc;
+    if (n < 0) return err(RT_E_INVALID, "n < 0");
+    if (!ctx || !sa || (n > 0 && (!pos || !normal || !out_vol))) return err(RT_E_INVALID, "NULL argument");
+    rc = check_knn_map(sa, radius);
+    if (rc != RT_OK) return rc;
+    if (n == 0) return RT_OK;
+    if ((int64_t)n * k > (int64_t)INT32_MAX) return err(RT_E_INVALID, "n * k too large");
+    RT_HIPE(hipSetDevice(sa->device));
+    float *d_p = nullptr, *d_n = nullptr, *d_d = nullptr;
+    int32_t *d_v = nullptr, *d_c = nullptr;
+    const size_t b3 = sizeof(float) * 3 * (size_t)n, bk = sizeof(float) * (size_t)n * (size_t)k;
+    hipError_t e = hipMalloc(&d_p, b3);
+    if (e == hipSuccess) e = hipMalloc(&d_n, b3);
+    if (e == hipSuccess) e = hipMalloc(&d_v, bk);
+    if (e == hipSuccess && out_dist) e = hipMalloc(&d_d, bk);
+    if (e == hipSuccess && out_count) e = hipMalloc(&d_c, sizeof(int32_t) * (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(d_p, pos, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_n, normal, b3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rt::launch_sarsa_knn(sa->m, d_p, d_n, n, k, radius, d_v, d_d, d_c, 0);
+    if (e == hipSuccess) e = hipMemcpy(out_vol, d_v, bk, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_dist) e = hipMemcpy(out_dist, d_d, bk, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_count) e = hipMemcpy(out_count, d_c, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost);
+    (void)hipFree(d_p);
+    (void)hipFree(d_n);
+    (void)hipFree(d_v);
+    (void)hipFree(d_d);
+    (void)hipFree(d_c);
+    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_sarsa_knn: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_render_irradiance(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,
+                         const rt_params* params, const rt_irr_opts* opts, uint32_t first_sample, float* out_rgb,
+                         int32_t* out_tri, float* out_pos, int32_t* out_vol, float* out_dist) {
+    int rc = check_irr_opts(opts);
+    if (rc != RT_OK) return rc;
+    if (!ctx || !scene || !sa || !cam || !opts || !out_rgb) return err(RT_E_INVALID, "NULL argument");
+    rc = check_sarsa_params(params, true);
+    if (rc != RT_OK) return rc;
+    rc = check_knn_map(sa, opts->radius);
+    if (rc != RT_OK) return rc;
+    if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
+    RT_HIPE(hipSetDevice(sa->device));
+    const int W = params->width, H = params->height;
+    std::vector<rt::BlockDesc> blocks;
+    for (int by = 0; by < H; by += 16)
+        for (int bx = 0; bx < W; bx += 16) blocks.push_back({bx, by, bx, by});
+    rt::BlockDesc* d_blocks = nullptr;
+    float *d_out = nullptr, *d_pos = nullptr, *d_dist = nullptr;
+    int32_t *d_tri = nullptr, *d_vol = nullptr;
+    const size_t np = (size_t)W * H, nk = np * (size_t)opts->k;
+    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
+    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
+    if (e == hipSuccess && out_tri) e = hipMalloc(&d_tri, sizeof(int32_t) * np);
+    if (e == hipSuccess && out_pos) e = hipMalloc(&d_pos, sizeof(float) * 3 * np);
+    if (e == hipSuccess && out_vol) e = hipMalloc(&d_vol, sizeof(int32_t) * nk);
+    if (e == hipSuccess && out_dist) e = hipMalloc(&d_dist, sizeof(float) * nk);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
+    rc = RT_OK;
+    if (e == hipSuccess)
+        rc = irr_frame(sa, scene, cam, params, opts, first_sample, d_blocks, (int)blocks.size(), W, d_out, d_tri, d_pos,
+                       d_vol, d_dist, 0);
+    if (rc == RT_OK && e == hipSuccess) e = hipDeviceSynchronize();
+    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_tri)
+        e = hipMemcpy(out_tri, d_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_pos)
+        e = hipMemcpy(out_pos, d_pos, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_vol)
+        e = hipMemcpy(out_vol, d_vol, sizeof(int32_t) * nk, hipMemcpyDeviceToHost);
+    if (rc == RT_OK && e == hipSuccess && out_dist)
+        e = hipMemcpy(out_dist, d_dist, sizeof(float) * nk, hipMemcpyDeviceToHost);
+    (void)hipFree(d_blocks);
+    (void)hipFree(d_out);
+    (void)hipFree(d_tri);
+    (void)hipFree(d_pos);
+    (void)hipFree(d_vol);
+    (void)hipFree(d_dist);
+    if (rc != RT_OK) return rc;
+    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_irradiance: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_render_irradiance_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,
+                                      const rt_params* params, const rt_irr_opts* opts, uint32_t first_sample,
+                                      const int32_t* tiles, int n_tiles, int tile_size, float* d_out, void* stream) {
+    int rc = check_irr_opts(opts);
+    if (rc != RT_OK) return rc;
+    if (!ctx || !scene || !sa || !cam || !opts) return err(RT_E_INVALID, "NULL argument");
+    rc = check_sarsa_params(params, true);
+    if (rc != RT_OK) return rc;
+    rc = check_knn_map(sa, opts->radius);
+    if (rc != RT_OK) return rc;
+    if (n_tiles < 0 || (n_tiles > 0 && (!tiles || !d_out))) return err(RT_E_INVALID, "bad tiles/out");
+    if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
+    RT_HIPE(hipSetDevice(sa->device));
+    if (n_tiles == 0) return RT_OK;
+    const rt::BlockDesc* d_blocks = nullptr;
+    int n_blocks = 0;
+    rc = rt::ctx_blocks(ctx, tiles, n_tiles, tile_size, params->width, params->height, &d_blocks, &n_blocks);
+    if (rc != RT_OK) return rc;
+    return irr_frame(sa, scene, cam, params, opts, first_sample, d_blocks, n_blocks, tile_size, d_out, nullptr, nullptr,
+                     nullptr, nullptr, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -15,6 +15,10 @@
 //     (the CPU engine's importance-sampling renderer, Old_CPU_Rendering_Engine/Source/main.cpp:
 //      the radiance map filled from ground truth, bake_spp paths per sector (0: left as
 //      created), then frames rendered from the frozen map; the last frame is saved)
+//   ./build/reinforcement_demo irradiance <scene.obj> <kind> [frames] [bake_spp] [out.bmp] [width height] [k]
+//     (the CPU engine's irradiance render of the map, draw_radiance_map_path_tracing: the map
+//      filled from ground truth, bake_spp paths per sector, then each camera hit drawn as the
+//      average estimate of its k closest volumes; one sample per frame, the last frame is saved)
 //   (kind: 1 door_room, 2 archway, 3 complex_light_room; scene "cornell" = the Cornell box)
 #include <stdio.h>
 #include <stdlib.h>
@@ -24,6 +28,7 @@
 
 #include "../host/camera.h"
 #include "../host/importance_sampling_path_tracing.h"
+#include "../host/precompute_irradiance_path_tracing.h"
 #include "../host/reinforcement_path_tracing.h"
 #include "../host/scene.h"
 #include "../host/sdl_screen.h"
@@ -42,7 +47,7 @@ static vec4 camera_for(int kind) {  // GPU/main.cu:100-104
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi|importance <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
+        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi|importance|irradiance <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
         return 2;
     }
     const bool nq = strcmp(argv[1], "neuralq") == 0;
@@ -55,10 +60,12 @@ int main(int argc, char** argv) {
     const int spp = (!voronoi && argc > a) ? atoi(argv[a++]) : 32;
     const char* out = argc > a ? argv[a++] : "render.bmp";
     const bool importance = strcmp(argv[1], "importance") == 0;
-    const bool sized = (voronoi || importance) && argc > a + 1;
+    const bool irradiance = strcmp(argv[1], "irradiance") == 0;  // (its spp argument is bake_spp)
+    const bool sized = (voronoi || importance || irradiance) && argc > a + 1;
     const int width = sized ? atoi(argv[a]) : 512;
     const int height = sized ? atoi(argv[a + 1]) : 512;
     const int bake_spp = (importance && argc > a + 2) ? atoi(argv[a + 2]) : 64;
+    const int query_count = (irradiance && argc > a + 2) ? atoi(argv[a + 2]) : 3;
     if (width <= 0 || height <= 0) {
         fprintf(stderr, "bad screen size %d x %d\n", width, height);
         return 2;
@@ -100,6 +107,15 @@ int main(int argc, char** argv) {
                 const uint64_t casts = draw_importance_sampling_path_tracing(screen, camera, map, scene, spp);
                 printf("frame %d: importance sampling, average path length %.3f\n", f,
                        (double)casts / ((double)screen.width * screen.height * spp));
+            }
+        } else if (irradiance) {
+            RadianceMap map(ds);
+            printf("radiance volumes: %d (KD array %d)\n", map.radiance_volumes_count, map.radiance_array_size);
+            const uint64_t casts = map.precompute_radiance_volumes(spp, spp % 4 == 0 ? 4 : 1, height);
+            printf("precomputed %d paths per sector: %llu ray casts\n", spp, (unsigned long long)casts);
+            for (int f = 0; f < frames; ++f) {
+                draw_radiance_map_path_tracing(screen, map, camera, scene, query_count, (uint32_t)f);
+                printf("frame %d: irradiance view, %d closest volumes\n", f, query_count);
             }
         } else if (dqn) {
             PretrainedPathtracer pt(ds, model);

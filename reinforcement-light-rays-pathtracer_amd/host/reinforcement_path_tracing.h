@@ -117,6 +117,29 @@ class RadianceMap {
                                     nullptr));
         return casts;
     }
+    // RadianceTree::find_closest_radiance_volumes (Old_CPU_Rendering_Engine/Source/radiance_volumes/
+    // radiance_tree.cpp:111-177) on the device (rt_sarsa_knn): the up to n volumes with this normal
+    // closer than max_dist to position, nearest first (equal distances by index), as volume indices.
+    // max_dist is a distance and at most max_query_dist(); unlike the reference's walk, a volume at or
+    // beyond it is never returned.  distances: optional, the volumes' distances.
+    std::vector<int32_t> find_closest_radiance_volumes(int n, float max_dist, const vec4& position, const vec4& normal,
+                                                       std::vector<float>* distances = nullptr) const {
+        const float p[3] = {position.x, position.y, position.z}, nr[3] = {normal.x, normal.y, normal.z};
+        std::vector<int32_t> vol((size_t)(n > 0 ? n : 0));
+        std::vector<float> dist(vol.size());
+        int32_t count = 0;
+        detail::check(rt_sarsa_knn(ds_.ctx(), map_, p, nr, 1, n, max_dist, vol.data(), dist.data(), &count));
+        vol.resize((size_t)count);
+        dist.resize((size_t)count);
+        if (distances) *distances = dist;
+        return vol;
+    }
+    // the largest max_dist find_closest_radiance_volumes answers (rt_sarsa_knn_reach)
+    float max_query_dist() const {
+        float r = 0.f;
+        detail::check(rt_sarsa_knn_reach(map_, &r));
+        return r;
+    }
     // paths in flight of the in-frame rule (its races depend on it; the reference's GTX 1070 Ti
     // held about 4,864: the setting its training logs are matched at); 0: the whole device
     void set_in_frame_lanes(int lanes) { detail::check(rt_sarsa_set_inframe_lanes(map_, lanes)); }

@@ -45,6 +45,10 @@ RT_KT_PROBE = 9
 RT_KT_BAKE = 10
 RT_KT_COUNT = 11
 
+RT_SARSA_KNN_MAX = 8
+RT_IRR_MEAN = 0
+RT_IRR_CONE = 1
+
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
     "rt_params_default", "rt_ctx_create", "rt_ctx_destroy", "rt_last_error",
@@ -73,6 +77,7 @@ EXPORTS = (
     "rt_dqn_fit_create", "rt_dqn_fit_destroy", "rt_dqn_fit_info", "rt_dqn_fit_epoch",
     "rt_probe_radiance", "rt_probe_radiance_device",
     "rt_sarsa_write", "rt_sarsa_bake",
+    "rt_sarsa_knn_reach", "rt_sarsa_knn", "rt_render_irradiance", "rt_render_irradiance_tiles_device",
 )
 
 
@@ -90,6 +95,11 @@ class RtParams(ctypes.Structure):
 
     def to_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtIrrOpts(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int32), ("radius", ctypes.c_float), ("weight", ctypes.c_int32),
+                ("tint", ctypes.c_int32)]
 
 
 class RtError(RuntimeError):
@@ -216,6 +226,12 @@ def _declare(lib):
                                          _P, _P]),
         "rt_sarsa_write": (i, [_P, i, i, _FP, _UP]),
         "rt_sarsa_bake": (i, [_P, _P, _P, ctypes.POINTER(RtParams), i, i, ctypes.c_uint32, _U64P, _P]),
+        "rt_sarsa_knn_reach": (i, [_P, _FP]),
+        "rt_sarsa_knn": (i, [_P, _P, _FP, _FP, i, i, f, _IP, _FP, _IP]),
+        "rt_render_irradiance": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                     ctypes.POINTER(RtIrrOpts), ctypes.c_uint32, _FP, _IP, _FP, _IP, _FP]),
+        "rt_render_irradiance_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                                  ctypes.POINTER(RtIrrOpts), ctypes.c_uint32, _IP, i, i, _P, _P]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),

@@ -17,6 +17,10 @@
   .frame_stats() / .append_stats_line(path)   sarsa_training_stats.txt (GPU/main.cu:321-339)
   .view(cam, params, first_sample, aov) / .view_tiles_device(...)   the Voronoi view (GPU/main.cu
                                   method 2): each camera hit in its nearest volume's colour
+  .knn(pos, nrm, k, radius) / .knn_reach()   the k nearest same-normal volumes within radius (rt_sarsa_knn)
+  .irradiance_view(cam, params, k, radius, weight, tint) / .irradiance_view_tiles_device(...)   the CPU
+                                  engine's draw_radiance_map_path_tracing: each camera hit as the map's
+                                  irradiance estimate there, interpolated over the k nearest volumes
   .set_view_colours(rgb)          the view's per-volume colours; voronoi_palette(seed, n) the default,
                                   irradiance_colours / visits_colours / max_q_colours from read()
 """
@@ -27,7 +31,7 @@ import os
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import RT_IRR_CONE, RT_IRR_MEAN, RT_SARSA_KNN_MAX, RtIrrOpts, check, lib
 
 from .api import Context, Scene, _fp, _ip
 
@@ -244,6 +248,67 @@ class RadianceMap:
         check(lib().rt_render_volume_view_tiles_device(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
                                                        ctypes.byref(params), first_sample, _ip(t), t.shape[0],
                                                        tile_size, ctypes.c_void_p(out_ptr), ctypes.c_void_p(stream)))
+
+    def knn_reach(self) -> float:
+        """The largest radius knn() answers: the grid's accept radius, sqrt(MAX_DIST) * 0.999; 0
+        for a map without a grid (rt_sarsa_knn_reach)."""
+        r = ctypes.c_float(0)
+        check(lib().rt_sarsa_knn_reach(self._h, ctypes.byref(r)))
+        return float(r.value)
+
+    def _irr_opts(self, k, radius, weight, tint) -> RtIrrOpts:
+        return RtIrrOpts(int(k), self.knn_reach() if radius is None else float(radius), int(weight), int(bool(tint)))
+
+    def knn(self, pos: np.ndarray, nrm: np.ndarray, k: int, radius: float | None = None):
+        """Per query the volumes with its normal closer than radius (None: the reach), the k
+        nearest ascending by (distance, index): (vol (n, k) int32, dist (n, k), count (n)); unused
+        slots hold -1 and +inf (rt_sarsa_knn)."""
+        p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+        n_ = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        n, kk = p.shape[0], max(int(k), 0)
+        vol = np.zeros((n, kk), np.int32)
+        dist = np.zeros((n, kk), np.float32)
+        cnt = np.zeros(n, np.int32)
+        check(lib().rt_sarsa_knn(self.ctx.handle, self._h, _fp(p), _fp(n_), n, int(k),
+                                 self.knn_reach() if radius is None else float(radius), _ip(vol), _fp(dist), _ip(cnt)))
+        return vol, dist, cnt
+
+    def irradiance_view(self, cam, params, k: int = 3, radius: float | None = None, weight: int = RT_IRR_MEAN,
+                        tint: bool = True, first_sample: int = 0, aov: bool = False):
+        """The irradiance render of the map (draw_radiance_map_path_tracing of the CPU engine;
+        rt_render_irradiance): every camera hit as the mean (RT_IRR_MEAN) or cone-weighted mean
+        (RT_IRR_CONE) of the irradiance estimates of its k nearest volumes within radius (None: the
+        reach), times albedo / luminance with tint.  Returns rgb (H, W, 3); with aov, (rgb, tri,
+        pos, vol (H, W, k), dist (H, W, k)) of sample first_sample.  The map is left as it is."""
+        h, w = params.height, params.width
+        o = self._irr_opts(k, radius, weight, tint)
+        out = np.zeros((h, w, 3), np.float32)
+        if not aov:
+            check(lib().rt_render_irradiance(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
+                                             ctypes.byref(params), ctypes.byref(o), first_sample, _fp(out), None, None,
+                                             None, None))
+            return out
+        kk = max(int(k), 0)
+        tri = np.zeros((h, w), np.int32)
+        pos = np.zeros((h, w, 3), np.float32)
+        vol = np.zeros((h, w, kk), np.int32)
+        dist = np.zeros((h, w, kk), np.float32)
+        check(lib().rt_render_irradiance(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
+                                         ctypes.byref(params), ctypes.byref(o), first_sample, _fp(out), _ip(tri), _fp(pos),
+                                         _ip(vol), _fp(dist)))
+        return out, tri, pos, vol, dist
+
+    def irradiance_view_tiles_device(self, cam, params, tiles: np.ndarray, tile_size: int, out_ptr: int, stream: int,
+                                     k: int = 3, radius: float | None = None, weight: int = RT_IRR_MEAN,
+                                     tint: bool = True, first_sample: int = 0) -> None:
+        """irradiance_view over a tile list into device memory, stream-ordered; tiles and output
+        layout as render_tiles_device (rt_render_irradiance_tiles_device)."""
+        t = np.ascontiguousarray(tiles, np.int32).reshape(-1, 2)
+        o = self._irr_opts(k, radius, weight, tint)
+        check(lib().rt_render_irradiance_tiles_device(self.ctx.handle, self.scene.handle, self._h, ctypes.byref(cam),
+                                                      ctypes.byref(params), ctypes.byref(o), first_sample, _ip(t),
+                                                      t.shape[0], tile_size, ctypes.c_void_p(out_ptr),
+                                                      ctypes.c_void_p(stream)))
 
     def td_device(self):
         """Device pointers of the frame's TD sums (int64, fixed point 2^-32) and counts (uint32)."""

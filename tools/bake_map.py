@@ -11,6 +11,9 @@ One JSON line:
                    frames of --render-spp and then rendered frozen, (c) "baked": a fresh map baked
                    at --spp paths per sector and rendered frozen; mape8 on the packed 8-bit frames
                    (the reference's Graphing/mape.py), mape_f on the float frames
+  irradiance       the same errors of the one-sample irradiance render of the baked map
+                   (rt_render_irradiance: no bounce, the map's own estimate at each camera hit) for
+                   (k = 1, mean), (k = 3, mean) and (k = 8, cone) at the map's reach
   bake             volumes, paths, casts, the wall seconds of each of --runs bakes of the whole map
                    (the first builds the scene's candidate table), k_bake's own milliseconds
                    (rt_ktime), paths/s and casts/s of the fastest
@@ -115,6 +118,10 @@ def main():
                            "paths_per_s": paths / min(secs), "casts_per_s": casts / min(secs)}
             rm.set_td_mode(S.TD_OFF)
             out["baked"] = errors(ref, rm.render(cam, p)[0])
+            p1 = gp(width=args.size, height=args.size, spp=1)
+            out["irradiance"] = {name: errors(ref, rm.irradiance_view(cam, p1, k, None, weight))
+                                 for name, k, weight in (("k1_mean", 1, rtmi.RT_IRR_MEAN), ("k3_mean", 3, rtmi.RT_IRR_MEAN),
+                                                         ("k8_cone", 8, rtmi.RT_IRR_CONE))}
             out["map_tv"] = {"baked": map_tv(ctx, sc, rm, pb, args.spp), "trained": tv_trained}
             if args.frame_time:
                 pf = gp(width=args.frame_size, height=args.frame_size, spp=args.frame_spp, spp_split=8)

@@ -91,6 +91,14 @@ hipError_t launch_sarsa_view(const RenderLaunch&, const SarsaMap&, const float4*
 hipError_t launch_sarsa_nearest(const SarsaMap&, const float*, const float*, int, int32_t*, hipStream_t) {
     return hipErrorNotSupported;
 }
+hipError_t launch_sarsa_knn(const SarsaMap&, const float*, const float*, int, int, float, int32_t*, float*, int32_t*,
+                            hipStream_t) {
+    return hipErrorNotSupported;
+}
+hipError_t launch_sarsa_irr(const RenderLaunch&, const SarsaMap&, int, float, int, int, int32_t*, float*, int32_t*,
+                            float*, hipStream_t) {
+    return hipErrorNotSupported;
+}
 
 // rebuild_volume (rt_sarsa.hip) on the host: every array it touches, at the kernel's indices
 static void rebuild_volume(const SarsaMap& m, int v) {

@@ -2,13 +2,16 @@
 """Radiance-map views of a scene as PNGs: what each camera hit's nearest radiance volume is
 (the reference's Voronoi view, GPU/main.cu PATH_TRACING_METHOD 2) and what the map has learned.
 
-    python tools/volume_view.py door_room [--train N] [--width 720] [--spp 4] [--out DIR]
+    python tools/volume_view.py door_room [--train N] [--width 720] [--spp 4] [--irradiance K] [--out DIR]
 
 Optionally trains N Expected-SARSA frames first, then writes
     <scene>_voronoi.png     the random per-volume palette of the map's seed
     <scene>_irradiance.png  each volume's irradiance estimate as grey
     <scene>_visits.png      each volume's visits, log scale
     <scene>_max_q.png       the sector of largest Q as hue / value
+and with --irradiance K
+    <scene>_irradiance_k<K>.png  the irradiance render (rt_render_irradiance): each hit as the mean
+                            estimate of its K nearest volumes times the surface's colour, lights lit
 """
 import argparse
 import os
@@ -27,6 +30,8 @@ def main():
     ap.add_argument("--width", type=int, default=720)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--spp", type=int, default=4, help="samples per pixel of the views")
+    ap.add_argument("--irradiance", type=int, default=0, metavar="K",
+                    help="also the irradiance render interpolated over the K nearest volumes (1..8)")
     ap.add_argument("--area-per-sample", type=float, default=None, help="volume density (default 0.001)")
     ap.add_argument("--seed", type=int, default=1984)
     ap.add_argument("--out", default=".")
@@ -56,6 +61,10 @@ def main():
             rm.set_view_colours(table)
             path = os.path.join(args.out, f"{args.scene}_{name}.png")
             rtmi.save_png(path, rtmi.pack_argb(rm.view(cam, p)))
+            print("wrote", path)
+        if args.irradiance > 0:
+            path = os.path.join(args.out, f"{args.scene}_irradiance_k{args.irradiance}.png")
+            rtmi.save_png(path, rtmi.pack_argb(rm.irradiance_view(cam, p, args.irradiance)))
             print("wrote", path)
 
 
