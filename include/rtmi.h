@@ -785,6 +785,12 @@ int rt_selftest(rt_ctx* ctx, int which, uint64_t* result /* 2 */);
 int rt_filter_build(const float* tri_v, int n, float* out_filt /* n x 20 */);
 int rt_rect_candidates(const float* filt, int n_tri, const rt_camera* cam, const rt_params* params,
                        int px0, int py0, int px1, int py1, uint64_t* masks /* ceil(n_tri / 64) */);
+/* rt_rect_candidates by the route the kernels take: the camera-and-triangle half of the cull
+ * once per triangle (what k_cull_forms writes for a launch), the rectangle half after it.
+ * The same float operations on the same operands: the masks equal rt_rect_candidates' bit for
+ * bit, which is what tests hold it to. */
+int rt_rect_candidates_forms(const float* filt, int n_tri, const rt_camera* cam, const rt_params* params,
+                             int px0, int py0, int px1, int py1, uint64_t* masks /* ceil(n_tri / 64) */);
 /* The same masks computed by the kernel (k_cull_ps) for the launch rt_render would make
  * for the rectangle (x0, y0, w, h): 4 words per wave, waves in launch order (16x16 blocks
  * row-major, `spp_split` workgroups each, 4 waves per workgroup).  *n_words: capacity of

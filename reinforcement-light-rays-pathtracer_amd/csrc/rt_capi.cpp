@@ -65,7 +65,29 @@ struct rt_ctx {
     float* d_csum = nullptr;
     size_t csum_cap = 0;
     unsigned long long* d_work = nullptr;
+    // The primary-ray cull's forms (k_cull_forms; ctx_cull_forms below): one buffer per stream
+    // that has rendered on this context, with the key its rows were last computed for.
+    struct CullFormsKey {
+        float cam[5];  // position, cos and sin of the yaw
+        int width, height;
+        float t_scale;
+        int hit_rule;
+        const void* filt;   // the scene's filter records ..
+        uint64_t filt_gen;  // .. and their generation (a later scene may get the same address)
+        int n_tri;
+    };
+    struct CullFormsBuf {
+        hipStream_t stream = nullptr;
+        float4* d_forms = nullptr;
+        CullFormsKey key;
+        bool valid = false;
+    };
+    std::vector<CullFormsBuf> cull_forms;
 };
+
+namespace {
+std::atomic<uint64_t> g_filt_gen{0};
+}
 
 struct rt_scene {
     rt_ctx* ctx = nullptr;
@@ -75,6 +97,9 @@ struct rt_scene {
     std::vector<float> tri;      // host copy, n_tri x 9 (surfaces then lights)
     std::vector<float> albedo;   // n_surf x 3
     std::vector<float> emission; // n_light x 3
+    // generation of dev.filt (built once per scene): tells this scene's records from those of
+    // an earlier scene at the same address (rt_ctx::CullFormsKey)
+    uint64_t filt_gen = ++g_filt_gen;
     // exact BVH path (rt_bvh.cpp): built for scenes above RT_BVH_AUTO_MIN triangles or on
     // request (rt_scene_set_accel)
     int accel = RT_ACCEL_AUTO;
@@ -265,6 +290,66 @@ int ctx_chunks(rt_ctx* ctx, RenderLaunch* a) {
     }
     a->cull = ctx->d_cull;
     return RT_OK;
+}
+
+// The cull forms of a launch of k_render_ps / k_cull_ps on `stream` (rt_cull.hpp's two halves):
+// *cf gets the camera constants and, where the launch takes that kernel, the stream's forms
+// buffer -- k_cull_forms runs on the stream ahead of the caller's launch when the buffer's key
+// differs (another camera, frame size, t_scale, hit rule or scene), and not at all otherwise.
+// Every stream has its own buffer, so a frame in flight on one stream never sees the rows of
+// another's camera; past kCullFormsStreams streams, or when the buffer cannot be allocated, the
+// launch gets no forms and its kernel runs the whole cull itself: the same masks, the same image
+// (RT_FORMS_TEST_FAIL=1 forces that, for the tests).
+constexpr size_t kCullFormsStreams = 8;
+void ctx_cull_forms(rt_ctx* ctx, const rt_scene* scene, const RenderLaunch& a, hipStream_t stream, CullLaunch* cf) {
+    cf->forms = nullptr;
+    cf->cam = make_cam_const(a.cam_x, a.cam_y, a.cam_z, a.cos_y, a.sin_y, a.width, a.height, a.t_scale);
+    // launch_render_t's condition for k_render_ps (rt_cull_masks_device checked the same)
+    if (a.preset != RT_PRESET_CPU || !a.use_filter || a.scene.filt == nullptr || a.scene.n_tri <= 0 ||
+        a.scene.n_tri > 64 * kRenderCullWords || a.scene.bvh_nodes != nullptr)
+        return;
+    rt_ctx::CullFormsBuf* buf = nullptr;
+    for (auto& b : ctx->cull_forms)
+        if (b.stream == stream) buf = &b;
+    if (buf == nullptr) {
+        if (ctx->cull_forms.size() >= kCullFormsStreams) return;
+        const char* force = getenv("RT_FORMS_TEST_FAIL");
+        float4* d = nullptr;
+        hipError_t e = (force && atoi(force) != 0) ? hipErrorOutOfMemory : hipSuccess;
+        if (e == hipSuccess) e = hipMalloc(&d, sizeof(float4) * kCullFormRows * kCullFormStride);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();  // the failed allocation must not fail the render's own launches
+            static std::atomic<bool> warned{false};
+            if (!warned.exchange(true))
+                fprintf(stderr, "rtmi: no buffer for the primary-ray cull's forms (%s); the render kernel computes them\n",
+                        hipGetErrorString(e));
+            return;
+        }
+        ctx->cull_forms.emplace_back();
+        buf = &ctx->cull_forms.back();
+        buf->stream = stream;
+        buf->d_forms = d;
+    }
+    rt_ctx::CullFormsKey key;
+    memset(&key, 0, sizeof(key));
+    key.cam[0] = a.cam_x; key.cam[1] = a.cam_y; key.cam[2] = a.cam_z; key.cam[3] = a.cos_y; key.cam[4] = a.sin_y;
+    key.width = a.width;
+    key.height = a.height;
+    key.t_scale = a.t_scale;
+    key.hit_rule = a.hit_rule;
+    key.filt = a.scene.filt;
+    key.filt_gen = scene->filt_gen;
+    key.n_tri = a.scene.n_tri;
+    if (!buf->valid || memcmp(&buf->key, &key, sizeof(key)) != 0) {
+        buf->valid = false;
+        if (launch_cull_forms(a.scene.filt, a.scene.n_tri, cf->cam, buf->d_forms, stream) != hipSuccess) {
+            (void)hipGetLastError();
+            return;
+        }
+        buf->key = key;
+        buf->valid = true;
+    }
+    cf->forms = buf->d_forms;
 }
 }  // namespace rt
 
@@ -719,6 +804,8 @@ int rt_ctx_destroy(rt_ctx* ctx) {
     if (ctx->d_cull) (void)hipFree(ctx->d_cull);
     if (ctx->d_csum) (void)hipFree(ctx->d_csum);
     if (ctx->d_work) (void)hipFree(ctx->d_work);
+    for (auto& b : ctx->cull_forms)
+        if (b.d_forms) (void)hipFree(b.d_forms);
     delete ctx;
     return RT_OK;
 }
@@ -1210,7 +1297,11 @@ int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt
         a.out = d_out;
         a.casts = d_casts;
         if (rt::ctx_chunks(ctx, &a) != RT_OK) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) e = rt::launch_render(a, 0);
+        if (e == hipSuccess) {
+            rt::CullLaunch cf;
+            rt::ctx_cull_forms(ctx, scene, a, 0, &cf);
+            e = rt::launch_render(a, 0, &cf);
+        }
     }
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out, out_bytes, hipMemcpyDeviceToHost);
@@ -1262,7 +1353,9 @@ int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* 
     static const bool prof = getenv("RT_PS_PROF") != nullptr;
     if (prof) RT_HIP(hipMalloc(&a.prof, 10 * sizeof(unsigned long long)));
     if (prof) RT_HIP(hipMemsetAsync(a.prof, 0, 10 * sizeof(unsigned long long), (hipStream_t)stream));
-    RT_HIP(rt::launch_render(a, (hipStream_t)stream));
+    rt::CullLaunch cf;
+    rt::ctx_cull_forms(ctx, scene, a, (hipStream_t)stream, &cf);
+    RT_HIP(rt::launch_render(a, (hipStream_t)stream, &cf));
     if (prof) {
         unsigned long long v[10];
         RT_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -1357,7 +1450,9 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
         rc = rt::ctx_cull(ctx, &a);
         if (rc != RT_OK) e = hipErrorOutOfMemory;
     }
-    if (e == hipSuccess) e = rt::launch_cull(a, 0);
+    rt::CullLaunch cf{};
+    if (e == hipSuccess) rt::ctx_cull_forms(ctx, scene, a, 0, &cf);
+    if (e == hipSuccess) e = rt::launch_cull(a, 0, &cf);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, a.cull, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToHost);
     (void)hipFree(d_blocks);
@@ -1379,6 +1474,27 @@ int rt_rect_candidates(const float* filt, int n_tri, const rt_camera* cam, const
     for (int i = 0; i < n_tri; ++i) {
         const bool cull = (p->hit_rule == RT_HIT_RULE_CPU) ? rt::rect_cull<0>(f + (size_t)i * rt::kFiltF4, c)
                                                            : rt::rect_cull<1>(f + (size_t)i * rt::kFiltF4, c);
+        if (!cull) masks[i / 64] |= 1ull << (i % 64);
+    }
+    return RT_OK;
+}
+
+int rt_rect_candidates_forms(const float* filt, int n_tri, const rt_camera* cam, const rt_params* p, int px0, int py0,
+                             int px1, int py1, uint64_t* masks) {
+    if (!filt || !cam || !p || !masks || n_tri <= 0) return fail(RT_E_INVALID, "bad arguments");
+    if (p->preset != RT_PRESET_CPU) return fail(RT_E_UNSUPPORTED, "the primary-ray phase is CPU-preset only");
+    if (px0 > px1 || py0 > py1) return fail(RT_E_INVALID, "empty rectangle");
+    const rt::CamConst k = rt::make_cam_const(cam->pos[0], cam->pos[1], cam->pos[2], (float)cos((double)cam->yaw_y),
+                                              (float)sin((double)cam->yaw_y), p->width, p->height, p->t_scale);
+    const rt::CamRect c = rt::cam_rect_of(k, px0, px1, py0, py1);
+    const float4* f = reinterpret_cast<const float4*>(filt);
+    for (int g = 0; g < (n_tri + 63) / 64; ++g) masks[g] = 0;
+    for (int i = 0; i < n_tri; ++i) {
+        // through the rows, as the kernels read them
+        float4 r[rt::kCullFormRows];
+        rt::cull_forms_rows(rt::cull_forms(f + (size_t)i * rt::kFiltF4, k), r);
+        const rt::CullForms o = rt::cull_forms_of_rows(r);
+        const bool cull = (p->hit_rule == RT_HIT_RULE_CPU) ? rt::rect_cull_forms<0>(o, c) : rt::rect_cull_forms<1>(o, c);
         if (!cull) masks[i / 64] |= 1ull << (i % 64);
     }
     return RT_OK;

@@ -508,8 +508,14 @@ hipError_t launch_selftest(int which, unsigned long long* mism, unsigned* first,
 int read_locations(const char* path, std::vector<float>* loc, std::vector<float>* nrm);
 
 // returns hipErrorInvalidValue for combinations the kernels do not instantiate
-hipError_t launch_render(const RenderLaunch& a, hipStream_t stream);
+// cf: the launch's cull forms (rt_cull.hpp; k_render_ps only), or nullptr
+struct CullLaunch;
+struct CamConst;
+hipError_t launch_render(const RenderLaunch& a, hipStream_t stream, const CullLaunch* cf = nullptr);
 // k_cull_ps alone (the primary-ray candidate masks into a.cull)
-hipError_t launch_cull(const RenderLaunch& a, hipStream_t stream);
+hipError_t launch_cull(const RenderLaunch& a, hipStream_t stream, const CullLaunch* cf = nullptr);
+// k_cull_forms: cull_forms of the scene's n_tri filter records for the camera constants k, into
+// forms (kCullFormRows * kCullFormStride float4)
+hipError_t launch_cull_forms(const float4* filt, int n_tri, const CamConst& k, float4* forms, hipStream_t stream);
 
 }  // namespace rt

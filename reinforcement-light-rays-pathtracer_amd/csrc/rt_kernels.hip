@@ -595,6 +595,21 @@ constexpr int kPsSplitLights = 8;  // the light pre-test runs when the scene has
 __host__ __device__ constexpr int ps_wave_floats(int pc) { return pc * kPsFields * 64 + pc * 32 + pc * 32; }
 
 
+// The rectangle-independent half of the primary-ray cull (cull_forms, rt_cull.hpp), one thread
+// per triangle: row k of triangle i to forms[k * kCullFormStride + i].  Threads past the scene
+// zero their column, so every lane of a cull wave reads initialised rows.
+__global__ __launch_bounds__(kCullFormStride) void k_cull_forms(const float4* __restrict__ filt, int n_tri,
+                                                               const CamConst k, float4* __restrict__ forms) {
+    const int i = threadIdx.x;
+    float4 r[kCullFormRows];
+    if (i < n_tri) {
+        cull_forms_rows(cull_forms(filt + (size_t)i * kFiltF4, k), r);
+    } else {
+        for (int j = 0; j < kCullFormRows; ++j) r[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    for (int j = 0; j < kCullFormRows; ++j) forms[j * kCullFormStride + i] = r[j];
+}
+
 // Candidate masks of the primary-ray phase: wave w of workgroup b writes
 // cull[(b * 4 + w) * kRenderCullWords + g], bit j = triangle 64 g + j may be the hit of a
 // camera ray through the wave's pixel rectangle (rect_cull, rt_trace.hpp).  Same grid
@@ -604,8 +619,10 @@ __host__ __device__ constexpr int ps_wave_floats(int pc) { return pc * kPsFields
 // (rect_cull); never a bit past the scene.  All lanes of the wave take part.
 // The masks alone, as k_render_ps computes them, into a.cull (wave w of workgroup b at
 // words (b * 4 + w) * kRenderCullWords ..): the diagnostic rt_cull_masks_device.
+// cf.forms (k_cull_forms' rows for this launch's camera): the split cull of k_render_ps; without,
+// wave_candidates.
 template <int RULE>
-__global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
+__global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a, const CullLaunch cf) {
     const int lg = a.split_log2;
     const BlockDesc blk = a.blocks[blockIdx.x >> lg];
     const int part = blockIdx.x & (a.split - 1);
@@ -617,6 +634,8 @@ __global__ __launch_bounds__(256) void k_cull_ps(const RenderLaunch a) {
     uint64_t cm[kRenderCullWords];
     if (__ballot(valid) == 0ull) {
         for (int g = 0; g < kRenderCullWords; ++g) cm[g] = 0ull;
+    } else if (cf.forms != nullptr) {
+        wave_candidates_forms<RULE>(a, cf, blk, q, lane, cm);
     } else {
         wave_candidates<RULE>(a, valid, px, py, lane, cm);
     }
@@ -747,9 +766,16 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
         parkf[2 * 64 + lane] = acc.z;
         wave_lds_sync();
         if (valid && chunk < 3) {
-            const float* src = parkf + chunk * 64 + base;
-            float t = src[0];
-            for (int kk = 1; kk < a.split; ++kk) t = t + src[kk];
+            // four chunk sums per LDS read (the pixel's piece of the row starts on a multiple of
+            // split >= 4 floats of a 256-byte-aligned row), added in the same order
+            const float4* src = reinterpret_cast<const float4*>(parkf + chunk * 64 + base);
+            float4 v = src[0];
+            float t = ((v.x + v.y) + v.z) + v.w;
+            for (int k4 = 1; k4 < (a.split >> 2); ++k4) {
+                v = src[k4];
+                t = ((t + v.x) + v.y) + v.z;
+                t = t + v.w;
+            }
             float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
             dst[chunk] = t / (float)a.spp;
         }
@@ -775,8 +801,8 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
 // CT: the bounce casts from the scene's candidate table (the launcher checked it serves this
 // launch) -- the matrix-core path is not compiled in, so the kernel's registers allow more waves.
 template <int SAMPLER, int RULE, int MF, bool CT = false>
-__device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceScene& ms, float* wl,
-                                            const BlockDesc& blk, int q, int chunk, int lane, int lx, int ly, int px,
+__device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLaunch& cf, const DeviceScene& ms,
+                                            float* wl, const BlockDesc& blk, int q, int chunk, int lane, int lx, int ly, int px,
                                             int py, bool valid) {
     extern __shared__ float s_ps[];
     const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
@@ -792,8 +818,12 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
     const f3 cam = make3(a.cam_x, a.cam_y, a.cam_z);
 
     // ---- candidate triangles of the wave's pixel rectangle (rect_cull, rt_cull.hpp) ----
+    // (from the launch's precomputed forms; a launch without them runs the whole cull here)
     uint64_t cm[kRenderCullWords];
-    wave_candidates<RULE>(a, valid, px, py, lane, cm);
+    if (cf.forms != nullptr)
+        wave_candidates_forms<RULE>(a, cf, blk, q, lane, cm);
+    else
+        wave_candidates<RULE>(a, valid, px, py, lane, cm);
 
     // ---- phase P: primary rays of the lane's samples ----
     unsigned n_casts = 0;
@@ -1273,7 +1303,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const DeviceS
 #define RT_PS_CT_WAVES 6
 #endif
 template <int SAMPLER, int RULE, int MF, bool CT = false>
-__global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_render_ps(const RenderLaunch a) {
+__global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_render_ps(const RenderLaunch a,
+                                                                                                const CullLaunch cf) {
     const int lg = a.split_log2;
     const BlockDesc blk = a.blocks[blockIdx.x >> lg];
     // XCD-aware parts: workgroups go to the 8 XCDs round-robin by blockIdx, so the
@@ -1323,9 +1354,13 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
     // (a wave without pixels does nothing until the casts barrier below, the kernel's only one
     // after the staging)
     unsigned n_casts = 0;
-    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT>(a, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
+    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT>(a, cf, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
     if (a.casts != nullptr) {
-        const unsigned total = wave_sum(n_casts);
+        // the wave's sum bit-sliced through ballots (a lane's count is at most 3 per_chunk: a few
+        // bits), no cross-lane permutes
+        unsigned total = 0;
+        for (int b = 0; __ballot((n_casts >> b) != 0u) != 0ull; ++b)
+            total += (unsigned)__builtin_popcountll(__ballot((n_casts >> b) & 1u)) << b;
         if (lane == 0) wg_casts[threadIdx.x >> 6] = total;
         __syncthreads();
         if (threadIdx.x == 0)
@@ -1485,7 +1520,7 @@ hipError_t launch_intersect_cand(const DeviceScene& s, const float* orig, const 
 #endif
 
 template <int PRESET, int SAMPLER, int RULE>
-static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
+static void launch_render_t(const RenderLaunch& a, hipStream_t stream, const CullLaunch& cf) {
     if (PRESET == 0 && a.use_filter && a.scene.n_tri <= 64 * kRenderCullWords &&
         a.scene.bvh_nodes == nullptr) {
         const size_t ps_lds = (size_t)4 * ps_wave_floats(a.per_chunk) * sizeof(float);
@@ -1507,13 +1542,13 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
             const dim3 grid((unsigned)(a.n_blocks * a.split));
             KernelTimer kt(KT_RENDER_PS, stream);
             if (ct)
-                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1, true>), grid, dim3(256), ps_lds + mf_lds, stream, a);
+                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1, true>), grid, dim3(256), ps_lds + mf_lds, stream, a, cf);
             else if (mf_lds > 0 && a.scene.n_tri <= 64)
-                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1>), grid, dim3(256), ps_lds + mf_lds, stream, a);
+                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1>), grid, dim3(256), ps_lds + mf_lds, stream, a, cf);
             else if (mf_lds > 0)
-                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 4>), grid, dim3(256), ps_lds + mf_lds, stream, a);
+                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 4>), grid, dim3(256), ps_lds + mf_lds, stream, a, cf);
             else
-                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 0>), grid, dim3(256), ps_lds, stream, a);
+                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 0>), grid, dim3(256), ps_lds, stream, a, cf);
             return;
         }
     }
@@ -1553,7 +1588,7 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
                     RenderLaunch c = b;  // one workgroup per 16x16 block: the masks of its four 16x4 rectangles
                     c.split = 1;
                     c.split_log2 = 0;
-                    hipLaunchKernelGGL((k_cull_ps<RULE>), dim3((unsigned)a.n_blocks), dim3(256), 0, stream, c);
+                    hipLaunchKernelGGL((k_cull_ps<RULE>), dim3((unsigned)a.n_blocks), dim3(256), 0, stream, c, CullLaunch{});
                     const unsigned wct = (unsigned)min(a.n_blocks * a.split, RT_PQ_CT_WAVES * device_cu_count());
                     if (one)
                         hipLaunchKernelGGL((k_render_pq<SAMPLER, RULE, 1, true>), dim3(wct), dim3(256), 0, stream, b);
@@ -1589,31 +1624,39 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream) {
     }
 }
 
-hipError_t launch_cull(const RenderLaunch& a, hipStream_t stream) {
-    if (a.n_blocks <= 0 || a.cull == nullptr || a.scene.filt == nullptr) return hipErrorInvalidValue;
-    if (a.hit_rule == 0)
-        hipLaunchKernelGGL((k_cull_ps<0>), dim3((unsigned)(a.n_blocks * a.split)), dim3(256), 0, stream, a);
-    else
-        hipLaunchKernelGGL((k_cull_ps<1>), dim3((unsigned)(a.n_blocks * a.split)), dim3(256), 0, stream, a);
+hipError_t launch_cull_forms(const float4* filt, int n_tri, const CamConst& k, float4* forms, hipStream_t stream) {
+    if (filt == nullptr || forms == nullptr || n_tri <= 0 || n_tri > kCullFormStride) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_cull_forms, dim3(1), dim3(kCullFormStride), 0, stream, filt, n_tri, k, forms);
     return hipGetLastError();
 }
 
-hipError_t launch_render(const RenderLaunch& a, hipStream_t stream) {
+hipError_t launch_cull(const RenderLaunch& a, hipStream_t stream, const CullLaunch* cfp) {
+    if (a.n_blocks <= 0 || a.cull == nullptr || a.scene.filt == nullptr) return hipErrorInvalidValue;
+    const CullLaunch cf = cfp != nullptr ? *cfp : CullLaunch{};
+    if (a.hit_rule == 0)
+        hipLaunchKernelGGL((k_cull_ps<0>), dim3((unsigned)(a.n_blocks * a.split)), dim3(256), 0, stream, a, cf);
+    else
+        hipLaunchKernelGGL((k_cull_ps<1>), dim3((unsigned)(a.n_blocks * a.split)), dim3(256), 0, stream, a, cf);
+    return hipGetLastError();
+}
+
+hipError_t launch_render(const RenderLaunch& a, hipStream_t stream, const CullLaunch* cfp) {
     if (a.n_blocks <= 0) return hipSuccess;
+    const CullLaunch cf = cfp != nullptr ? *cfp : CullLaunch{};
     if (a.preset == 0 && a.max_bounces > 2) return hipErrorInvalidValue;
     if (a.split < 1 || a.split > 64 || (a.split & (a.split - 1)) != 0 || (1 << a.split_log2) != a.split ||
         a.per_chunk * a.split != a.spp)
         return hipErrorInvalidValue;
     const int key = a.preset * 4 + a.sampler * 2 + a.hit_rule;
     switch (key) {
-        case 0: launch_render_t<0, 0, 0>(a, stream); break;
-        case 1: launch_render_t<0, 0, 1>(a, stream); break;
-        case 2: launch_render_t<0, 1, 0>(a, stream); break;
-        case 3: launch_render_t<0, 1, 1>(a, stream); break;
-        case 4: launch_render_t<1, 0, 0>(a, stream); break;
-        case 5: launch_render_t<1, 0, 1>(a, stream); break;
-        case 6: launch_render_t<1, 1, 0>(a, stream); break;
-        case 7: launch_render_t<1, 1, 1>(a, stream); break;
+        case 0: launch_render_t<0, 0, 0>(a, stream, cf); break;
+        case 1: launch_render_t<0, 0, 1>(a, stream, cf); break;
+        case 2: launch_render_t<0, 1, 0>(a, stream, cf); break;
+        case 3: launch_render_t<0, 1, 1>(a, stream, cf); break;
+        case 4: launch_render_t<1, 0, 0>(a, stream, cf); break;
+        case 5: launch_render_t<1, 0, 1>(a, stream, cf); break;
+        case 6: launch_render_t<1, 1, 0>(a, stream, cf); break;
+        case 7: launch_render_t<1, 1, 1>(a, stream, cf); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -1327,6 +1327,39 @@ __device__ __forceinline__ void wave_candidates(const RenderLaunch& a, bool vali
     }
 }
 
+// wave_candidates from the launch's precomputed forms (k_cull_forms; rt_cull.hpp's two halves),
+// for k_render_ps and k_cull_ps: a wave with at least one valid pixel whose lane 0 holds pixel
+// q (index in the 16x16 block, wave-uniform) and whose lanes hold 64 >> split_log2 consecutive
+// pixels from there.  Those are whole rows of the block or an aligned piece of one row, and the
+// valid ones are its intersection with the clip, so the rectangle wave_candidates reduces out
+// of the lanes is this closed form; the masks are wave_candidates' bit for bit.
+template <int RULE>
+__device__ __forceinline__ void wave_candidates_forms(const RenderLaunch& a, const CullLaunch& cf,
+                                                      const BlockDesc& blk, int q, int lane, uint64_t* cm) {
+    const int q0 = __builtin_amdgcn_readfirstlane(q);
+    const int q1 = q0 + (64 >> a.split_log2) - 1;
+    const int x0 = blk.px0 + (q0 & 15), y0 = blk.py0 + (q0 >> 4);
+    const int x1 = min(blk.px0 + (q1 & 15), a.clip_x1 - 1), y1 = min(blk.py0 + (q1 >> 4), a.clip_y1 - 1);
+    const CamRect c = cam_rect_of(cf.cam, x0, x1, y0, y1);
+    const int n_tri = a.scene.n_tri;
+    cfloat4* __restrict__ forms = as_const(cf.forms);
+#pragma unroll
+    for (int g = 0; g < kRenderCullWords; ++g) {
+        if (g * 64 >= n_tri) {  // (wave-uniform) no triangle in this word
+            cm[g] = 0ull;
+            continue;
+        }
+        const int i = g * 64 + lane;
+        const bool in_range = i < n_tri;
+        // (rows past the scene's triangles are zero-filled: every lane reads a record)
+        float4 r[kCullFormRows];
+#pragma unroll
+        for (int k = 0; k < kCullFormRows; ++k) r[k] = ldc(forms + k * kCullFormStride + i);
+        const bool keep = in_range && !rect_cull_forms<RULE>(cull_forms_of_rows(r), c);
+        cm[g] = __ballot(keep) & tri_mask(n_tri, g);
+    }
+}
+
 __device__ __forceinline__ unsigned wave_sum(unsigned v) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);

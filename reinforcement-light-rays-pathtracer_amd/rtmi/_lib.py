@@ -78,6 +78,7 @@ EXPORTS = (
     "rt_probe_radiance", "rt_probe_radiance_device",
     "rt_sarsa_write", "rt_sarsa_bake",
     "rt_sarsa_knn_reach", "rt_sarsa_knn", "rt_render_irradiance", "rt_render_irradiance_tiles_device",
+    "rt_rect_candidates_forms",
 )
 
 
@@ -152,6 +153,8 @@ def _declare(lib):
                                      _U64P, ctypes.POINTER(ctypes.c_int64)]),
         "rt_rect_candidates": (i, [_FP, i, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams), i, i, i, i,
                                    _U64P]),
+        "rt_rect_candidates_forms": (i, [_FP, i, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams), i, i, i, i,
+                                         _U64P]),
         "rt_ctab_candidates": (i, [_FP, i, i, i, _IP, _FP, _FP, i, _U64P, ctypes.POINTER(ctypes.c_int64)]),
         "rt_dynet_read": (i, [ctypes.c_char_p, i, _IP, _IP, _FP, ctypes.POINTER(i),
                               ctypes.POINTER(ctypes.c_int64)]),

@@ -311,14 +311,16 @@ def filter_records(tri_all: np.ndarray) -> np.ndarray:
 
 
 def rect_candidates(filt: np.ndarray, cam: RtCamera, params: RtParams, px0: int, py0: int, px1: int,
-                    py1: int) -> np.ndarray:
+                    py1: int, forms: bool = False) -> np.ndarray:
     """Boolean (n_tri,) mask: the triangles the CPU-preset primary-ray phase keeps for camera
-    rays through pixels [px0, px1] x [py0, py1] (the cull of k_cull_ps, run on the host)."""
+    rays through pixels [px0, px1] x [py0, py1] (the cull of k_cull_ps, run on the host).
+    forms: by the kernels' two halves (rt_rect_candidates_forms) instead of the definition."""
     f = np.ascontiguousarray(filt, np.float32)
     n = f.shape[0]
     words = np.zeros((n + 63) // 64, np.uint64)
-    check(lib().rt_rect_candidates(_fp(f), n, ctypes.byref(cam), ctypes.byref(params), px0, py0, px1, py1,
-                                   words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    fn = lib().rt_rect_candidates_forms if forms else lib().rt_rect_candidates
+    check(fn(_fp(f), n, ctypes.byref(cam), ctypes.byref(params), px0, py0, px1, py1,
+             words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
     bits = np.unpackbits(words.view(np.uint8), bitorder="little")
     return bits[:n].astype(bool)
 
