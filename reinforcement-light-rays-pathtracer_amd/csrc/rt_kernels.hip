@@ -28,6 +28,8 @@
 
 #include <float.h>
 
+#include <type_traits>
+
 #include "rt_trace.hpp"
 
 namespace rt {
@@ -586,13 +588,30 @@ __global__ __launch_bounds__(256) void k_fold_chunks(const RenderLaunch a) {
 // and one int16 row of hit codes:
 //   continuing: the hit point x, y, z, triangle;  ended: L.x, L.y, L.z, -1.
 // (int16 codes: 13 KB of slots per 256-lane workgroup at 4 samples per lane instead of 16 KB --
-// with the table route's pair list that is 25.6 KB per workgroup, six per CU)
+// with the table route's pair list that is 25.6 KB per workgroup, six per CU; the table-route
+// variant's codes are bytes, ps_wave_floats)
 constexpr int kPsFields = 3;     // float rows per sample slot
 constexpr int kPsPrimBatch = 4;  // samples per candidate pass of phase P
 constexpr int kPsSplitLights = 8;  // the light pre-test runs when the scene has at most this many light triangles
 // floats of LDS per wave: the sample slots' float rows, their int16 codes, then the wave's
-// queue of continuing samples, one u16 (k << 6 | lane) per slot
-__host__ __device__ constexpr int ps_wave_floats(int pc) { return pc * kPsFields * 64 + pc * 32 + pc * 32; }
+// queue of continuing samples, one u16 (k << 6 | lane) per slot.
+// narrow (the table-route variant up to kPsNarrowChunk samples per lane: its codes are triangles
+// below 64 or -1, its entries k << 6 | lane below 256): a byte per code and per entry, the block
+// rounded up to 256 bytes (ps_finish reads the wave's first rows 16 bytes at a time).  The
+// layout is a constant of the kernel's template (NARROW), chosen by the launcher: picked at run
+// time inside one kernel, the two queue paths cost the bench frame 2 % (DESIGN.md section 7,
+// round 12).
+constexpr int kPsNarrowChunk = 4;
+__host__ __device__ constexpr bool ps_narrow(bool ct, int pc) { return ct && pc <= kPsNarrowChunk; }
+__host__ __device__ constexpr int ps_wave_floats(int pc, bool narrow) {
+    return narrow ? (pc * kPsFields * 64 + pc * 16 + pc * 16 + 63) & ~63 : pc * kPsFields * 64 + pc * 32 + pc * 32;
+}
+// The table-route variant's shading records in LDS, kPsFrameF4 rows per triangle:
+// [N.xyz, F.x] [T.xyz, F.y] [B.xyz, F.z] -- the frame, and in the w lanes the one colour a fold
+// reads there: a surface's fold row for the kernel's sampler, a light's emission
+constexpr int kPsFrameF4 = 3;
+static_assert(ps_wave_floats(4, true) == 896, "the narrow wave block at 4 samples per lane");
+static_assert(ps_wave_floats(3, true) % 64 == 0 && ps_wave_floats(1, true) % 64 == 0, "wave blocks are 256-byte multiples");
 
 
 // The rectangle-independent half of the primary-ray cull (cull_forms, rt_cull.hpp), one thread
@@ -688,22 +707,38 @@ __device__ __forceinline__ void ps_shade_dir(const RenderLaunch& a, const float4
     *o_out = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
     *d_out = normalize(sd);
 }
-// v.xyz stay in their registers from here on: whatever load produced them is waited for at this
-// point, and no later use waits again (an empty statement for the compiler's scheduling only)
-__device__ __forceinline__ void ps_pin(float4& v) { asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(v.z)); }
-template <int SAMPLER>
+// (LF: shade is the table-route variant's LDS copy, kPsFrameF4 rows per triangle)
+template <int SAMPLER, bool LF = false>
 __device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4* __restrict__ shade, uint32_t lpix,
                                              int cur, int dep, const f3& pos, int hit_tri, float* cos_out, f3* o_out,
                                              f3* d_out) {
-    const float4 N = shade[hit_tri * kShadeF4 + 0];
-    const float4 T = shade[hit_tri * kShadeF4 + 1];
-    const float4 B = shade[hit_tri * kShadeF4 + 2];
+    constexpr int rows = LF ? kPsFrameF4 : kShadeF4;
+    const float4 N = shade[hit_tri * rows + 0];
+    const float4 T = shade[hit_tri * rows + 1];
+    const float4 B = shade[hit_tri * rows + 2];
     ps_shade_dir<SAMPLER>(a, N, T, B, lpix, cur, dep, pos, cos_out, o_out, d_out);
 }
+// the colour in the w lanes of triangle tri's rows of the LDS copy (kPsFrameF4)
+__device__ __forceinline__ float4 ps_frame_colour(const float4* __restrict__ frames, int tri) {
+    return make_float4(frames[tri * kPsFrameF4 + 0].w, frames[tri * kPsFrameF4 + 1].w, frames[tri * kPsFrameF4 + 2].w,
+                       0.0f);
+}
+// the emission of light triangle tri
+template <bool LF = false>
+__device__ __forceinline__ float4 ps_emission(const float4* __restrict__ shade, int tri) {
+    if constexpr (LF)
+        return ps_frame_colour(shade, tri);
+    else
+        return shade[tri * kShadeF4 + 3];
+}
 // folds the light L back through the bounce at surface tri whose direction had cos theta = c
-template <int SAMPLER>
+template <int SAMPLER, bool LF = false>
 __device__ __forceinline__ void ps_fold(const float4* __restrict__ shade, f3& L, int tri, float cosv) {
-    const float4 c = shade[tri * kShadeF4 + (SAMPLER == 0 ? 3 : 4)];
+    float4 c;
+    if constexpr (LF)
+        c = ps_frame_colour(shade, tri);
+    else
+        c = shade[tri * kShadeF4 + (SAMPLER == 0 ? 3 : 4)];
     if (SAMPLER == 0) {
         L.x = div_rho((L.x * c.x) * cosv);
         L.y = div_rho((L.y * c.y) * cosv);
@@ -741,11 +776,11 @@ __device__ __forceinline__ bool ps_light_pass(const RenderLaunch& a, const Devic
 // the end of k_render_ps for one wave with at least one pixel: every lane sums its own slots
 // in sample order onto acc (ended samples hold their value in fields 0..2), the
 // chunk sums of a pixel fold in chunk order and the pixel is stored
-__device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc& blk, int chunk, int lane, int lx,
-                                          int ly, bool valid, f3 acc) {
-    extern __shared__ float s_ps[];
+// (wslots: the wave's block of ps_wave_floats floats)
+__device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc& blk, float* wslots, int chunk, int lane,
+                                          int lx, int ly, bool valid, f3 acc) {
     const int pc = a.per_chunk;
-    const float* const slots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc) + lane;
+    const float* const slots = wslots + lane;
     for (int kk = 0; kk < pc; ++kk) {
         const float* sl = slots + kk * kPsFields * 64;
         acc.x = acc.x + sl[0 * 64];
@@ -760,7 +795,7 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
     // the same operands as the shuffle fold below, which keeps all 64 lanes busy for
     // split - 1 dependent rounds of three cross-lane reads each.
     if (a.split >= 4) {
-        float* const parkf = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(a.per_chunk);
+        float* const parkf = wslots;
         parkf[0 * 64 + lane] = acc.x;
         parkf[1 * 64 + lane] = acc.y;
         parkf[2 * 64 + lane] = acc.z;
@@ -800,7 +835,8 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
 // the work of k_render_ps for one wave with at least one pixel; returns the lane's casts.
 // CT: the bounce casts from the scene's candidate table (the launcher checked it serves this
 // launch) -- the matrix-core path is not compiled in, so the kernel's registers allow more waves.
-template <int SAMPLER, int RULE, int MF, bool CT = false>
+// NARROW: the launch's wave blocks are the narrow ones (ps_wave_floats; the launcher: ps_narrow).
+template <int SAMPLER, int RULE, int MF, bool CT = false, bool NARROW = false>
 __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLaunch& cf, const DeviceScene& ms,
                                             float* wl, const BlockDesc& blk, int q, int chunk, int lane, int lx, int ly, int px,
                                             int py, bool valid) {
@@ -809,12 +845,18 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     const float4* __restrict__ shade = ms.shade;  // (the workgroup's LDS copy, when the kernel staged one)
     const int n_surf = a.scene.n_surf;
     const int pc = a.per_chunk;
-    float* const wslots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc);
+    // the table-route variant: shade is the kernel's LDS copy of the frames (kPsFrameF4), its slot
+    // codes are bytes, and so are its queue's entries in the narrow layout (ps_wave_floats)
+    constexpr bool LF = ps_pooled(MF, CT);
+    static_assert(LF || !NARROW, "only the table-route variant has the narrow layout");
+    constexpr bool narrow = NARROW;
+    float* const wslots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc, narrow);
     float* const slots = wslots + lane;
     // a slot's hit code: the triangle a continuing path's primary hit is on, or -1 (ended)
-    int16_t* const wcodes = reinterpret_cast<int16_t*>(wslots + pc * kPsFields * 64);
+    using code_t = std::conditional_t<LF, int8_t, int16_t>;
+    code_t* const wcodes = reinterpret_cast<code_t*>(wslots + pc * kPsFields * 64);
     auto code_at = [&](int kk, int ln) -> int { return (int)wcodes[kk * 64 + ln]; };
-    auto set_code_at = [&](int kk, int ln, int c) { wcodes[kk * 64 + ln] = (int16_t)c; };
+    auto set_code_at = [&](int kk, int ln, int c) { wcodes[kk * 64 + ln] = (code_t)c; };
     const f3 cam = make3(a.cam_x, a.cam_y, a.cam_z);
 
     // ---- candidate triangles of the wave's pixel rectangle (rect_cull, rt_cull.hpp) ----
@@ -846,7 +888,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
             v0 = v1 = v2 = 0.0f;  // PRESET 0: a miss contributes 0
             code = -1;
         } else if (h.tri >= n_surf) {
-            const float4 e = shade[h.tri * kShadeF4 + 3];
+            const float4 e = ps_emission<LF>(shade, h.tri);
             v0 = e.x; v1 = e.y; v2 = e.z;  // the light's emission, no surface bounce to fold
             code = -1;
         } else if (a.max_bounces == 0) {
@@ -932,13 +974,22 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     // only its own: the wave runs ceil(casts / 64) trips instead of its busiest lane's.
     // A finished sample's value goes back into its slot; every lane then sums its own
     // slots in sample order (the fixed-chunk sum: the image is unchanged).
-    uint16_t* const queue = reinterpret_cast<uint16_t*>(wslots + pc * kPsFields * 64 + pc * 32);
+    // (after the codes: pc * 64 of them, int16 or bytes)
+    uint16_t* const queue = reinterpret_cast<uint16_t*>(wcodes + pc * 64);
+    uint8_t* const queue8 = reinterpret_cast<uint8_t*>(queue);  // the narrow layout's
+    auto queue_at = [&](int j) -> uint32_t { return narrow ? (uint32_t)queue8[j] : (uint32_t)queue[j]; };
+    auto set_queue_at = [&](int j, int e) {
+        if (narrow)
+            queue8[j] = (uint8_t)e;
+        else
+            queue[j] = (uint16_t)e;
+    };
     int q_total = 0;
     for (int kk = 0; kk < pc; ++kk) {
         const bool cont = valid && code_at(kk, lane) >= 0;
         const uint64_t m = __ballot(cont);
-        if (cont) queue[q_total + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                      __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)((kk << 6) | lane);
+        if (cont) set_queue_at(q_total + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                         __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)), (kk << 6) | lane);
         q_total += __builtin_popcountll(m);
     }
     int q_next = 0;       // wave-uniform: next queue entry
@@ -953,7 +1004,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
         const int j = q_next + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(need >> 32),
                                                               __builtin_amdgcn_mbcnt_lo((uint32_t)need, 0u));
         if (!live && j < q_total) {
-            const uint32_t e = queue[j];
+            const uint32_t e = queue_at(j);
             const int ol = (int)(e & 63u), kk = (int)(e >> 6);
             own_e = (int)e;
             const float* own = wslots + kk * kPsFields * 64 + ol;
@@ -975,7 +1026,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     // the next direction from the surface hit (pos, hit_tri) at bounce depth dep: cos theta
     // and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the path's Philox draw
     auto shade_hit = [&](int dep, float* cos_out, f3* o_out, f3* d_out) {
-        ps_shade_hit<SAMPLER>(a, shade, lpix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
+        ps_shade_hit<SAMPLER, LF>(a, shade, lpix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
     };
     // Light pre-test.  The terminal cast of a path (the one at depth
     // max_bounces) adds light only if its closest hit is a light triangle; a surface or a miss
@@ -1019,13 +1070,10 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     // (closest_hit_ctab_begin), then run the pending sample's pre-test -- its keys re-derived
     // from the entry as claim() derives them -- settle the passes, store its value, and only then
     // use the lookup's words (closest_hit_ctab_finish).  Loads return in the order of their
-    // issue, so a wait inside the pre-test for its surface's shading frame would wait for the
-    // lookup's words as well: the frame is loaded where the sample becomes pending, ahead of the
-    // next trip's loads, and pinned in registers (ps_pin) at the top of that trip, on every
-    // path.  (Pinned later, after the new sample's shading on one path and where a lane has no
-    // new sample on the other, the compiler still waits inside the pre-test.)  The fold of a
-    // settled ray that ends on a light loads its rows from global memory and so waits for the
-    // lookup's words too: it is under its own branch, off the common path.  Every sample runs
+    // issue, so a wait inside the pre-test for a global load would wait for the lookup's words as
+    // well: the pre-test issues none.  Its surface's shading frame, the hit-test records and
+    // the rows a settled ray that ends on a light folds with all come from the workgroup's LDS
+    // (the frame by the hit triangle packed in the entry).  Every sample runs
     // the same float operations on the same operands as in the loop below, and the casts are
     // counted at the same events: the image and the ray casts are unchanged.  When the queue has
     // drained, the pre-tests still pending run after the loop.  Nothing but the pending sample
@@ -1037,7 +1085,6 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
             bool pend = false;
             f3 p_pos = make3(0.0f, 0.0f, 0.0f);
             int p_pack = 0;  // the entry << 12 | f_tri0 << 6 | hit_tri
-            float4 pN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pT = pN, pB = pN;  // its surface's shading frame
             // the pending samples' pre-tests, the passes settled on the spot (wave-level)
             auto pretest_pending = [&]() {
 #if RT_PROF
@@ -1052,7 +1099,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 f3 lo = cam, ld = make3(0.0f, 0.0f, 1.0f);
                 if (pend) {
                     key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), e);
-                    ps_shade_dir<SAMPLER>(a, pN, pT, pB, key.pix, key.cur, a.max_bounces - 1, p_pos, &c, &lo, &ld);
+                    ps_shade_hit<SAMPLER, LF>(a, shade, key.pix, key.cur, a.max_bounces - 1, p_pos, p_pack & 63, &c, &lo,
+                                              &ld);
                     pass = ps_light_pass<RULE>(a, ms, lo, ld);
                 }
                 // The passes are settled here, one ray at a time by the whole wave: lane j tests
@@ -1099,16 +1147,16 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                         // loop folds it (the pre-test's own cos at this surface, then the path's
                         // first surface with the cos its shading at depth 0 drew)
                         const int dep = a.max_bounces - 1;
-                        const float4 em = shade[tri * kShadeF4 + 3];
+                        const float4 em = ps_emission<LF>(shade, tri);
                         v = make3(em.x, em.y, em.z);
-                        if (dep >= 1) ps_fold<SAMPLER>(shade, v, p_pack & 63, c);
+                        if (dep >= 1) ps_fold<SAMPLER, LF>(shade, v, p_pack & 63, c);
                         float f_c0 = c;
                         if (SAMPLER == 0 && dep >= 1) {
                             float r1, r2;
                             draw2(key.pix, (uint32_t)key.cur, 1u, a.seed_lo, a.seed_hi, &r1, &r2);
                             f_c0 = r1;
                         }
-                        ps_fold<SAMPLER>(shade, v, (p_pack >> 6) & 63, f_c0);
+                        ps_fold<SAMPLER, LF>(shade, v, (p_pack >> 6) & 63, f_c0);
                     }
                     float* own = wslots + kk * kPsFields * 64 + ol;
                     own[0 * 64] = v.x;
@@ -1126,9 +1174,6 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 pt[5] += 1;
                 pt[7] += q_total - q_next < 16 ? 1 : 0;
 #endif
-                ps_pin(pN);
-                ps_pin(pT);
-                ps_pin(pB);
                 // claim(): every lane is free, lane l takes entry q_next + l
                 const int qj = q_next + lane;
                 const bool has = qj < q_total;
@@ -1138,19 +1183,16 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 f3 so = cam, sd = make3(0.0f, 0.0f, 1.0f);  // (a lane without a sample: a finite ray, no candidates)
                 CtabLook<1> look = ctab_no_look<1>();
                 if (has) {
-                    s_e = (int)queue[qj];
+                    s_e = (int)queue_at(qj);
                     const int ol = s_e & 63, kk = s_e >> 6;
                     const float* own = wslots + kk * kPsFields * 64 + ol;
                     const f3 spos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
                     s_tri = code_at(kk, ol);
-                    // the new sample's loads: its shading frame and its patch frame (the lookup's
-                    // first link) ahead of the Philox block
-                    const float4 N = shade[s_tri * kShadeF4 + 0];
-                    const float4 T = shade[s_tri * kShadeF4 + 1];
-                    const float4 B = shade[s_tri * kShadeF4 + 2];
+                    // the new sample's one global load, its patch frame (the lookup's first link),
+                    // ahead of the Philox block; its shading frame is in LDS
                     const CtabFrame R = ctab_frame(tab, s_tri);
                     const PsKeys key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), s_e);  // the owner's
-                    ps_shade_dir<SAMPLER>(a, N, T, B, key.pix, key.cur, 0, spos, &s_cos, &so, &sd);
+                    ps_shade_hit<SAMPLER, LF>(a, shade, key.pix, key.cur, 0, spos, s_tri, &s_cos, &so, &sd);
                     look = closest_hit_ctab_begin<1>(tab, R, so, sd, true);
                 }
 #if RT_PROF
@@ -1171,17 +1213,14 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                     p_pos = make3(so.x + h.t * (sd.x * a.t_scale), so.y + h.t * (sd.y * a.t_scale),
                                   so.z + h.t * (sd.z * a.t_scale));
                     p_pack = (s_e << 12) | (s_tri << 6) | h.tri;
-                    pN = shade[h.tri * kShadeF4 + 0];
-                    pT = shade[h.tri * kShadeF4 + 1];
-                    pB = shade[h.tri * kShadeF4 + 2];
                     pend = true;
                     continue;
                 }
                 f3 L = make3(0.0f, 0.0f, 0.0f);  // a miss, or a surface at max_bounces
                 if (h.tri >= n_surf) {
-                    const float4 e = shade[h.tri * kShadeF4 + 3];
+                    const float4 e = ps_emission<LF>(shade, h.tri);
                     L = make3(e.x, e.y, e.z);
-                    ps_fold<SAMPLER>(shade, L, s_tri, s_cos);  // (depth 1: the path's first bounce)
+                    ps_fold<SAMPLER, LF>(shade, L, s_tri, s_cos);  // (depth 1: the path's first bounce)
                 }
                 float* own = wslots + (s_e >> 6) * kPsFields * 64 + (s_e & 63);
                 own[0 * 64] = L.x;
@@ -1243,11 +1282,11 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
         if (h.tri < 0) {
             // miss: 0
         } else if (h.tri >= n_surf) {
-            const float4 e = shade[h.tri * kShadeF4 + 3];
+            const float4 e = ps_emission<LF>(shade, h.tri);
             L = make3(e.x, e.y, e.z);
             // fold back through the surface bounces: depth 2 (this shading), then depth 1
-            if (depth >= 2) ps_fold<SAMPLER>(shade, L, s_tri, s_cos);
-            ps_fold<SAMPLER>(shade, L, f_tri0, f_cos0);
+            if (depth >= 2) ps_fold<SAMPLER, LF>(shade, L, s_tri, s_cos);
+            ps_fold<SAMPLER, LF>(shade, L, f_tri0, f_cos0);
         } else if (depth == a.max_bounces) {
             // bounces == MAX_RAY_BOUNCES -> vec3(0)
         } else {
@@ -1289,7 +1328,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
         atomicMax(a.prof + 8, (unsigned long long)max_settle);
     }
 #endif
-    ps_finish(a, blk, chunk, lane, lx, ly, valid, acc);
+    ps_finish(a, blk, wslots, chunk, lane, lx, ly, valid, acc);
     return n_casts;
 }
 
@@ -1297,12 +1336,15 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
 #define RT_PS_MIN_WAVES 4  // the matrix-core filter's operands: ~99 VGPRs
 #endif
 #ifndef RT_PS_CT_WAVES
-// occupancy floor of the table-route variant: 6 (80 VGPRs, 9 spilled) -- with the int16 slot codes
-// its workgroup takes 26.7 KB of LDS and six fit a CU (Cornell 512^2 x 256: 2.39 -> 2.24 ms,
-// profiles/r6v/; at the 28.7-KB layout LDS held it to five and 6 only added spills)
+// occupancy floor of the table-route variant: 6 (80 VGPRs, 3 spilled) -- with the narrow wave
+// blocks its workgroup takes 26.4 KB of LDS, shading frames included, and six fit a CU (Cornell
+// 512^2 x 256 at the int16 codes' 26.7 KB: 2.39 -> 2.24 ms, profiles/r6v/; at the 28.7-KB layout
+// LDS held it to five and 6 only added spills)
 #define RT_PS_CT_WAVES 6
 #endif
-template <int SAMPLER, int RULE, int MF, bool CT = false>
+// NARROW: the wave blocks of this launch are the narrow ones (ps_wave_floats); the table-route
+// variant only, chosen by the launcher (ps_narrow)
+template <int SAMPLER, int RULE, int MF, bool CT = false, bool NARROW = false>
 __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_render_ps(const RenderLaunch a,
                                                                                                 const CullLaunch cf) {
     const int lg = a.split_log2;
@@ -1326,35 +1368,54 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
     // wave put 16 MB per launch of atomic write traffic on a 3 MB frame
     __shared__ unsigned wg_casts[4];
     // LDS after the sample slots (launch_render_t sizes it): the waves' exact-phase
-    // regions, then the scene's hit-test records and, when not CT, its shading records
+    // regions, then the scene's hit-test records and its shading records (the table-route
+    // variant: the frames and one colour per triangle, kPsFrameF4)
     DeviceScene ms = a.scene;
     float* wl = nullptr;
     if (MF > 0) {
         extern __shared__ float s_ps[];
-        float* const mf_base = s_ps + (size_t)4 * ps_wave_floats(a.per_chunk);
+        float* const mf_base = s_ps + (size_t)4 * ps_wave_floats(a.per_chunk, NARROW);
         // (the table route's wave blocks hold a shorter pair list: mf_wave_floats)
         constexpr int wf = CT ? mf_wave_floats(kCtPairCap, RULE) : kMfWaveFloats;
         wl = mf_base + (size_t)(threadIdx.x >> 6) * wf;
         // hit-test and shading records of the scene (divergent per-lane reads: LDS latency
-        // instead of L1/L2).  The table-route kernel reads its shading records from L1/L2: with
-        // the shorter pair list that kept the workgroup at 29.4 KB of LDS, five per CU (Cornell
-        // 512^2 x 256: 2.33 ms, in LDS 2.37-2.40; the 35.6-KB layout of round 5 held four per
-        // CU: 2.63 ms, profiles/r6f/ab.log)
+        // instead of L1/L2).  The table-route kernel stages what ps_body reads of a shading
+        // record, 48 of its 80 bytes: rows N, T, B, and in their w lanes the surface's fold row
+        // for this sampler or the light's emission.  The byte codes and queue of its wave blocks
+        // pay for them: the bench launch stays below the 26.7 KB that six workgroups per CU had
+        // (launch_render_t's static_assert).
         const int n = a.scene.n_tri;
         float4* li = reinterpret_cast<float4*>(mf_base + 4 * wf);
-        for (int i = threadIdx.x; i < n * kIsectF4; i += 256) li[i] = a.scene.isect[i];
-        ms.isect = li;
-        if (!CT) {
-            float4* ls = li + (size_t)n * kIsectF4;
-            for (int i = threadIdx.x; i < n * kShadeF4; i += 256) ls[i] = a.scene.shade[i];
+        float4* ls = li + (size_t)n * kIsectF4;
+        if constexpr (ps_pooled(MF, CT)) {
+            // waves 0 and 1 move the hit-test records, waves 2 and 3 the frames, every load of a
+            // thread issued ahead of its first wait (a workgroup lives a few trips: a second
+            // round trip in front of the barrier shows in the frame)
+            if (threadIdx.x < 128) {
+                for (int i = threadIdx.x; i < n * kIsectF4; i += 128) li[i] = a.scene.isect[i];
+            } else {
+                for (int i = threadIdx.x - 128; i < n * kPsFrameF4; i += 128) {
+                    const int tri = i / kPsFrameF4, r = i - tri * kPsFrameF4;
+                    const float4 row = a.scene.shade[tri * kShadeF4 + r];
+                    const float4* col = a.scene.shade + tri * kShadeF4 + ((SAMPLER == 0 || tri >= a.scene.n_surf) ? 3 : 4);
+                    ls[i] = make_float4(row.x, row.y, row.z, reinterpret_cast<const float*>(col)[r]);
+                }
+            }
             ms.shade = ls;
+        } else {
+            for (int i = threadIdx.x; i < n * kIsectF4; i += 256) li[i] = a.scene.isect[i];
+            if (!CT) {
+                for (int i = threadIdx.x; i < n * kShadeF4; i += 256) ls[i] = a.scene.shade[i];
+                ms.shade = ls;
+            }
         }
+        ms.isect = li;
         __syncthreads();
     }
     // (a wave without pixels does nothing until the casts barrier below, the kernel's only one
     // after the staging)
     unsigned n_casts = 0;
-    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT>(a, cf, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
+    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT, NARROW>(a, cf, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
     if (a.casts != nullptr) {
         // the wave's sum bit-sliced through ballots (a lane's count is at most 3 per_chunk: a few
         // bits), no cross-lane permutes
@@ -1523,7 +1584,8 @@ template <int PRESET, int SAMPLER, int RULE>
 static void launch_render_t(const RenderLaunch& a, hipStream_t stream, const CullLaunch& cf) {
     if (PRESET == 0 && a.use_filter && a.scene.n_tri <= 64 * kRenderCullWords &&
         a.scene.bvh_nodes == nullptr) {
-        const size_t ps_lds = (size_t)4 * ps_wave_floats(a.per_chunk) * sizeof(float);
+        // (the routing predicate is on the wide layout, whichever the launch then takes)
+        size_t ps_lds = (size_t)4 * ps_wave_floats(a.per_chunk, false) * sizeof(float);
         if (ps_lds <= (size_t)RT_PS_MAX_LDS) {
             // the bounce casts from the scene's candidate table (rt_ctab.cpp) when it serves this
             // launch: one mask word, this build's bins, t_scale >= its ts_min
@@ -1532,16 +1594,27 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream, const Cul
                             T.bins == kCtabBins && T.graze_n == kCtabGraze && a.t_scale >= T.ts_min && T.words == 1;
             // The kernel's dynamic LDS, in its order: ps_lds, the four waves' slots, codes and
             // queue (ps_wave_floats); then, with the matrix-core image, the four waves' exact-phase
-            // blocks (the table route's hold the shorter pair list), the scene's isect records and,
-            // when not CT, its shading records
+            // blocks (the table route's hold the shorter pair list), the scene's isect records and
+            // its shading records (the table route's: kPsFrameF4 rows, and its wave blocks are
+            // the narrow ones up to kPsNarrowChunk samples per lane)
             size_t mf_lds = 0;
             if (a.scene.mf_frag != nullptr) {
                 mf_lds = (size_t)4 * (ct ? mf_wave_floats(kCtPairCap, RULE) : kMfWaveFloats) * sizeof(float);
-                mf_lds += (size_t)a.scene.n_tri * (kIsectF4 + (ct ? 0 : kShadeF4)) * sizeof(float4);
+                mf_lds += (size_t)a.scene.n_tri * (kIsectF4 + (ct ? kPsFrameF4 : kShadeF4)) * sizeof(float4);
             }
+            const bool narrow = ps_narrow(ct, a.per_chunk);
+            if (narrow) ps_lds = (size_t)4 * ps_wave_floats(a.per_chunk, true) * sizeof(float);
+            // the bench launch (4 samples per lane, Cornell's 38 triangles): no more than the
+            // 26,656 B of the int16 layout without the frames, six workgroups per CU
+            static_assert((4 * ps_wave_floats(4, true) + 4 * mf_wave_floats(kCtPairCap, 0)) * sizeof(float) +
+                                  38 * (kIsectF4 + kPsFrameF4) * sizeof(float4) <= 26656,
+                          "the table route's bench launch outgrew its LDS");
             const dim3 grid((unsigned)(a.n_blocks * a.split));
             KernelTimer kt(KT_RENDER_PS, stream);
-            if (ct)
+            if (narrow)
+                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1, true, true>), grid, dim3(256), ps_lds + mf_lds, stream, a,
+                                   cf);
+            else if (ct)
                 hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1, true>), grid, dim3(256), ps_lds + mf_lds, stream, a, cf);
             else if (mf_lds > 0 && a.scene.n_tri <= 64)
                 hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1>), grid, dim3(256), ps_lds + mf_lds, stream, a, cf);
