@@ -767,10 +767,21 @@ int rt_probe_radiance_device(rt_ctx* ctx, const rt_scene* scene, const rt_params
  *   vs IEEE 1.0f / x over all 2^32 floats;
  * RT_SELFTEST_DIV12: the grid-coordinate x / 12 (Chiu map) vs IEEE over its domain,
  *   +0 and |x| in [2^-100, 2^100];
- * RT_SELFTEST_DIVRHO: the estimator's x / RHO vs IEEE over all 2^32 floats. */
+ * RT_SELFTEST_DIVRHO: the estimator's x / RHO vs IEEE over all 2^32 floats;
+ * RT_SELFTEST_SQRT_POS: the sampling's square root without range guards vs sqrtf over its
+ *   domain, +0 and [2^-96, FLT_MAX];
+ * RT_SELFTEST_RCP_IN: the reciprocal without its range guard vs IEEE 1.0f / x over its domain,
+ *   |x| in [2^-125, 2^125];
+ * RT_SELFTEST_PHILOX_PX: the Philox block split into its pixel, event and sample parts vs the
+ *   whole block, all four words, 2^24 counters (pixel, sample, event, 0) for each of two keys, with
+ *   the pixel's words wave-uniform and per lane; result[1] = form << 25 | key << 24 |
+ *   pixel index << 12 | sample << 2 | event of the lowest mismatch. */
 #define RT_SELFTEST_RCP 1
 #define RT_SELFTEST_DIV12 2
 #define RT_SELFTEST_DIVRHO 3
+#define RT_SELFTEST_SQRT_POS 4
+#define RT_SELFTEST_RCP_IN 5
+#define RT_SELFTEST_PHILOX_PX 6
 int rt_selftest(rt_ctx* ctx, int which, uint64_t* result /* 2 */);
 
 /* Host-side checks of the CPU-preset primary-ray cull (k_cull_ps; no GPU needed).

@@ -1371,7 +1371,7 @@ int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* 
 
 int rt_selftest(rt_ctx* ctx, int which, uint64_t* result) {
     if (!ctx || !result) return fail(RT_E_INVALID, "NULL argument");
-    if (which != RT_SELFTEST_RCP && which != RT_SELFTEST_DIV12 && which != RT_SELFTEST_DIVRHO)
+    if (which < RT_SELFTEST_RCP || which > RT_SELFTEST_PHILOX_PX)
         return fail(RT_E_INVALID, "unknown self-test %d", which);
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;

@@ -603,6 +603,9 @@ constexpr int kPsSplitLights = 8;  // the light pre-test runs when the scene has
 // round 12).
 constexpr int kPsNarrowChunk = 4;
 __host__ __device__ constexpr bool ps_narrow(bool ct, int pc) { return ct && pc <= kPsNarrowChunk; }
+// one pixel per wave (k_render_ps's ONEPX instances, of the narrow layout): the 64 lanes of a wave
+// are the 64 chunks of one pixel
+__host__ __device__ constexpr bool ps_onepx(bool narrow, int split) { return narrow && split == 64; }
 __host__ __device__ constexpr int ps_wave_floats(int pc, bool narrow) {
     return narrow ? (pc * kPsFields * 64 + pc * 16 + pc * 16 + 63) & ~63 : pc * kPsFields * 64 + pc * 32 + pc * 32;
 }
@@ -683,19 +686,24 @@ __device__ __forceinline__ float readlane_f(float v, int l) {
 // path's Philox draw
 // (ps_shade_dir: with the surface's shading frame N, T, B in hand -- a caller that loads the
 // records ahead of time, the pipelined loop)
+// lpx: the Philox words of the sample's pixel (philox_pix).  The square roots and the normalize
+// are the forms without range guards (sqrt_rn_pos, normalize_unit: rt_math.hpp), the same bits
+// on the ranges the sampling has.
 template <int SAMPLER>
 __device__ __forceinline__ void ps_shade_dir(const RenderLaunch& a, const float4& N, const float4& T, const float4& B,
-                                             uint32_t lpix, int cur, int dep, const f3& pos, float* cos_out, f3* o_out,
-                                             f3* d_out) {
+                                             const PhiloxPix& lpx, int cur, int dep, const f3& pos, float* cos_out,
+                                             f3* o_out, f3* d_out) {
     float r1, r2;
-    draw2(lpix, (uint32_t)cur, 1u + (uint32_t)dep, a.seed_lo, a.seed_hi, &r1, &r2);
+    draw2_px(lpx, (uint32_t)cur, 1u + (uint32_t)dep, a.seed_lo, a.seed_hi, &r1, &r2);
+    // r1 = k 2^-24, k < 2^24: r1 r1 <= 1 - 2^-23, so 1 - r1 r1 lies in [2^-23, 1]; r1 is +0 or in
+    // [2^-24, 1), 1 - r1 in [2^-24, 1]
     float cos_theta, sin_theta;
     if (SAMPLER == 0) {
         cos_theta = r1;
-        sin_theta = sqrtf(1.0f - r1 * r1);
+        sin_theta = sqrt_rn_pos(1.0f - r1 * r1);
     } else {
-        cos_theta = sqrtf(r1);
-        sin_theta = sqrtf(1.0f - r1);
+        cos_theta = sqrt_rn_pos(r1);
+        sin_theta = sqrt_rn_pos(1.0f - r1);
     }
     float sphi, cphi;
     sincos_turn(r2, &sphi, &cphi);
@@ -705,18 +713,20 @@ __device__ __forceinline__ void ps_shade_dir(const RenderLaunch& a, const float4
                         (sx * B.z + cos_theta * N.z) + sz * T.z);
     *cos_out = cos_theta;
     *o_out = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
-    *d_out = normalize(sd);
+    // sd = (sin cphi) B + cos N + (sin sphi) T on an orthonormal frame with sin^2 + cos^2 and
+    // sphi^2 + cphi^2 within a few ulp of 1: dot(sd, sd) is 1 +- a few ulp
+    *d_out = normalize_unit(sd);
 }
 // (LF: shade is the table-route variant's LDS copy, kPsFrameF4 rows per triangle)
 template <int SAMPLER, bool LF = false>
-__device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4* __restrict__ shade, uint32_t lpix,
-                                             int cur, int dep, const f3& pos, int hit_tri, float* cos_out, f3* o_out,
-                                             f3* d_out) {
+__device__ __forceinline__ void ps_shade_hit(const RenderLaunch& a, const float4* __restrict__ shade,
+                                             const PhiloxPix& lpx, int cur, int dep, const f3& pos, int hit_tri,
+                                             float* cos_out, f3* o_out, f3* d_out) {
     constexpr int rows = LF ? kPsFrameF4 : kShadeF4;
     const float4 N = shade[hit_tri * rows + 0];
     const float4 T = shade[hit_tri * rows + 1];
     const float4 B = shade[hit_tri * rows + 2];
-    ps_shade_dir<SAMPLER>(a, N, T, B, lpix, cur, dep, pos, cos_out, o_out, d_out);
+    ps_shade_dir<SAMPLER>(a, N, T, B, lpx, cur, dep, pos, cos_out, o_out, d_out);
 }
 // the colour in the w lanes of triangle tri's rows of the LDS copy (kPsFrameF4)
 __device__ __forceinline__ float4 ps_frame_colour(const float4* __restrict__ frames, int tri) {
@@ -836,7 +846,9 @@ __device__ __forceinline__ void ps_finish(const RenderLaunch& a, const BlockDesc
 // CT: the bounce casts from the scene's candidate table (the launcher checked it serves this
 // launch) -- the matrix-core path is not compiled in, so the kernel's registers allow more waves.
 // NARROW: the launch's wave blocks are the narrow ones (ps_wave_floats; the launcher: ps_narrow).
-template <int SAMPLER, int RULE, int MF, bool CT = false, bool NARROW = false>
+// ONEPX: every lane of a wave holds the same pixel (split 64; the launcher: ps_onepx), so the pixel's
+// Philox words are wave-uniform and the scalar unit computes them, once per wave.
+template <int SAMPLER, int RULE, int MF, bool CT = false, bool NARROW = false, bool ONEPX = false>
 __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLaunch& cf, const DeviceScene& ms,
                                             float* wl, const BlockDesc& blk, int q, int chunk, int lane, int lx, int ly, int px,
                                             int py, bool valid) {
@@ -849,6 +861,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     // codes are bytes, and so are its queue's entries in the narrow layout (ps_wave_floats)
     constexpr bool LF = ps_pooled(MF, CT);
     static_assert(LF || !NARROW, "only the table-route variant has the narrow layout");
+    static_assert(NARROW || !ONEPX, "one pixel per wave is an instance of the narrow layout only");
     constexpr bool narrow = NARROW;
     float* const wslots = s_ps + (size_t)(threadIdx.x >> 6) * ps_wave_floats(pc, narrow);
     float* const slots = wslots + lane;
@@ -858,6 +871,22 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     auto code_at = [&](int kk, int ln) -> int { return (int)wcodes[kk * 64 + ln]; };
     auto set_code_at = [&](int kk, int ln, int c) { wcodes[kk * 64 + ln] = (code_t)c; };
     const f3 cam = make3(a.cam_x, a.cam_y, a.cam_z);
+    // The Philox words of the lane's pixel (philox_pix: the two products of a block that see only
+    // the pixel and the key), the same for all its samples.  ONEPX: the wave's pixel -- every lane
+    // of a wave that gets here is valid and holds it -- so the words are scalars.
+    PhiloxPix ppx;
+    if constexpr (ONEPX) {
+        ppx = philox_pix((uint32_t)__builtin_amdgcn_readfirstlane((int)pix), a.seed_lo, a.seed_hi);
+    } else {
+        ppx = philox_pix(pix, a.seed_lo, a.seed_hi);
+    }
+    // the words of pixel p, the owner of a queued sample (ONEPX: the wave's)
+    auto px_of = [&](uint32_t p) -> PhiloxPix {
+        if constexpr (ONEPX)
+            return ppx;
+        else
+            return philox_pix(p, a.seed_lo, a.seed_hi);
+    };
 
     // ---- candidate triangles of the wave's pixel rectangle (rect_cull, rt_cull.hpp) ----
     // (from the launch's precomputed forms; a launch without them runs the whole cull here)
@@ -916,8 +945,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
         for (int j = 0; j < PB; ++j) {
             const int s = chunk * pc + min(k0 + j, pc - 1);
             float r1, r2;
-            draw2(pix, (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
-            camera_ray<0>(a, px, py, r1, r2, &dd[j]);
+            draw2_px(ppx, (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
+            camera_ray<0, true>(a, px, py, r1, r2, &dd[j]);
             nx[j] = -(dd[j].x * nts);
             ny[j] = -(dd[j].y * nts);
             nz[j] = -(dd[j].z * nts);
@@ -1026,7 +1055,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     // the next direction from the surface hit (pos, hit_tri) at bounce depth dep: cos theta
     // and the ray (o = pos + eps sd, d = normalize(sd)), sampled with the path's Philox draw
     auto shade_hit = [&](int dep, float* cos_out, f3* o_out, f3* d_out) {
-        ps_shade_hit<SAMPLER, LF>(a, shade, lpix, cur, dep, pos, hit_tri, cos_out, o_out, d_out);
+        ps_shade_hit<SAMPLER, LF>(a, shade, px_of(lpix), cur, dep, pos, hit_tri, cos_out, o_out, d_out);
     };
     // Light pre-test.  The terminal cast of a path (the one at depth
     // max_bounces) adds light only if its closest hit is a light triangle; a surface or a miss
@@ -1099,8 +1128,9 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 f3 lo = cam, ld = make3(0.0f, 0.0f, 1.0f);
                 if (pend) {
                     key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), e);
-                    ps_shade_hit<SAMPLER, LF>(a, shade, key.pix, key.cur, a.max_bounces - 1, p_pos, p_pack & 63, &c, &lo,
-                                              &ld);
+                    // (a sample is pending only at max_bounces 2, launch_render's limit for this
+                    // preset: its pre-test's depth is 1, the event a constant)
+                    ps_shade_hit<SAMPLER, LF>(a, shade, px_of(key.pix), key.cur, 1, p_pos, p_pack & 63, &c, &lo, &ld);
                     pass = ps_light_pass<RULE>(a, ms, lo, ld);
                 }
                 // The passes are settled here, one ray at a time by the whole wave: lane j tests
@@ -1153,7 +1183,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                         float f_c0 = c;
                         if (SAMPLER == 0 && dep >= 1) {
                             float r1, r2;
-                            draw2(key.pix, (uint32_t)key.cur, 1u, a.seed_lo, a.seed_hi, &r1, &r2);
+                            draw2_px(px_of(key.pix), (uint32_t)key.cur, 1u, a.seed_lo, a.seed_hi, &r1, &r2);
                             f_c0 = r1;
                         }
                         ps_fold<SAMPLER, LF>(shade, v, (p_pack >> 6) & 63, f_c0);
@@ -1192,7 +1222,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                     // ahead of the Philox block; its shading frame is in LDS
                     const CtabFrame R = ctab_frame(tab, s_tri);
                     const PsKeys key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), s_e);  // the owner's
-                    ps_shade_hit<SAMPLER, LF>(a, shade, key.pix, key.cur, 0, spos, s_tri, &s_cos, &so, &sd);
+                    ps_shade_hit<SAMPLER, LF>(a, shade, px_of(key.pix), key.cur, 0, spos, s_tri, &s_cos, &so, &sd);
                     look = closest_hit_ctab_begin<1>(tab, R, so, sd, true);
                 }
 #if RT_PROF
@@ -1344,7 +1374,8 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
 #endif
 // NARROW: the wave blocks of this launch are the narrow ones (ps_wave_floats); the table-route
 // variant only, chosen by the launcher (ps_narrow)
-template <int SAMPLER, int RULE, int MF, bool CT = false, bool NARROW = false>
+// ONEPX: this launch has one pixel per wave (split 64: ps_onepx); an instance of the narrow layout
+template <int SAMPLER, int RULE, int MF, bool CT = false, bool NARROW = false, bool ONEPX = false>
 __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_render_ps(const RenderLaunch a,
                                                                                                 const CullLaunch cf) {
     const int lg = a.split_log2;
@@ -1415,7 +1446,7 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
     // (a wave without pixels does nothing until the casts barrier below, the kernel's only one
     // after the staging)
     unsigned n_casts = 0;
-    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT, NARROW>(a, cf, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
+    if (vmask != 0ull) n_casts = ps_body<SAMPLER, RULE, MF, CT, NARROW, ONEPX>(a, cf, ms, wl, blk, q, chunk, lane, lx, ly, px, py, valid);
     if (a.casts != nullptr) {
         // the wave's sum bit-sliced through ballots (a lane's count is at most 3 per_chunk: a few
         // bits), no cross-lane permutes
@@ -1435,8 +1466,11 @@ __global__ __launch_bounds__(256, CT ? RT_PS_CT_WAVES : RT_PS_MIN_WAVES) void k_
 // WHICH = RT_SELFTEST_RCP: rcp_rn(x) vs IEEE 1.0f / x over all 2^32 floats;
 // RT_SELFTEST_DIV12: div12(x) vs x / 12.0f over its domain (+0, |x| in [2^-100, 2^100]);
 // RT_SELFTEST_DIVRHO: div_rho(x) vs x / RHO over all 2^32 floats (its fallback included).
+// RT_SELFTEST_SQRT_POS: sqrt_rn_pos(x) vs sqrtf(x) over its domain (+0, x in [2^-96, FLT_MAX]);
+// RT_SELFTEST_RCP_IN: rcp_rn_in(x) vs IEEE 1.0f / x over its domain (|x| in [2^-125, 2^125]).
 // NaNs compare equal to NaNs.
 constexpr int kSelfRcp = 1, kSelfDiv12 = 2, kSelfDivRho = 3;  // RT_SELFTEST_* (rtmi.h)
+constexpr int kSelfSqrtPos = 4, kSelfRcpIn = 5, kSelfPhiloxPx = 6;
 
 template <int WHICH>
 __global__ __launch_bounds__(256) void k_selftest(unsigned long long* mism, unsigned* first) {
@@ -1454,6 +1488,15 @@ __global__ __launch_bounds__(256) void k_selftest(unsigned long long* mism, unsi
             if (!(bits == 0u || (ax >= 0x1p-100f && ax <= 0x1p100f))) continue;
             a = div12(x);
             b = x / 12.0f;
+        } else if constexpr (WHICH == kSelfSqrtPos) {
+            if (!(bits == 0u || (x >= 0x1p-96f && x <= FLT_MAX))) continue;
+            a = sqrt_rn_pos(x);
+            b = sqrtf(x);
+        } else if constexpr (WHICH == kSelfRcpIn) {
+            const float ax = fabsf(x);
+            if (!(ax >= 0x1p-125f && ax <= 0x1p125f)) continue;
+            a = rcp_rn_in(x);
+            b = 1.0f / x;
         } else {
             constexpr float rho = 1.0f / (2.0f * 3.14159265358979323846f);
             a = div_rho(x);
@@ -1468,6 +1511,46 @@ __global__ __launch_bounds__(256) void k_selftest(unsigned long long* mism, unsi
     if (bad) atomicAdd(mism, (unsigned long long)bad);
 }
 
+// RT_SELFTEST_PHILOX_PX: the split block (philox_pix, philox_ev, philox_finish) against
+// philox4x32_10, all four words, over 2^24 counters (pixel, sample, event, 0) per key and form:
+// 4096 pixels (0, 1, 2^16 - 1, 2^16, 2^31, 2^32 - 1 and a hashed spread) x samples 0..1023 x events
+// 0..3, for the key (1984, 0) and one with a high word.  Form 0: the pixel is the workgroup's, its
+// words go through readfirstlane (the scalar unit's products, ps_body's ONEPX); form 1: a pixel
+// per lane (thread t of block b takes pixel index (b + t) mod 4096, so every pair is met once).
+// Same grid as k_selftest.  first: the lowest form << 25 | key << 24 | pixel index << 12 |
+// sample << 2 | event that mismatched.
+__device__ __forceinline__ uint32_t selftest_pixel(uint32_t i) {
+    const uint32_t special[6] = {0u, 1u, 0xFFFFu, 0x10000u, 0x80000000u, 0xFFFFFFFFu};
+    return i < 6u ? special[i] : i * 0x9E3779B1u + 0x7F4A7C15u;
+}
+__global__ __launch_bounds__(256) void k_selftest_philox(unsigned long long* mism, unsigned* first) {
+    unsigned bad = 0;
+    for (uint32_t form = 0; form < 2u; ++form) {
+        const uint32_t pi = form == 0u ? blockIdx.x : ((blockIdx.x + threadIdx.x) & 4095u);
+        const uint32_t pixel = selftest_pixel(pi);
+        for (uint32_t key = 0; key < 2u; ++key) {
+            const uint32_t k0 = key == 0u ? 1984u : 0x89ABCDEFu, k1 = key == 0u ? 0u : 0x01234567u;
+            PhiloxPix px;
+            if (form == 0u)
+                px = philox_pix((uint32_t)__builtin_amdgcn_readfirstlane((int)pixel), k0, k1);
+            else
+                px = philox_pix(pixel, k0, k1);
+            for (uint32_t smp = threadIdx.x; smp < 1024u; smp += 256u) {
+                for (uint32_t ev = 0; ev < 4u; ++ev) {
+                    uint32_t want[4], got[4];
+                    philox4x32_10(pixel, smp, ev, 0u, k0, k1, want);
+                    philox_finish(px, philox_ev(ev), smp, k0, k1, got);
+                    if (want[0] != got[0] || want[1] != got[1] || want[2] != got[2] || want[3] != got[3]) {
+                        ++bad;
+                        atomicMin(first, form << 25 | key << 24 | pi << 12 | smp << 2 | ev);
+                    }
+                }
+            }
+        }
+    }
+    if (bad) atomicAdd(mism, (unsigned long long)bad);
+}
+
 }  // namespace
 
 hipError_t launch_selftest(int which, unsigned long long* mism, unsigned* first, hipStream_t stream) {
@@ -1477,6 +1560,12 @@ hipError_t launch_selftest(int which, unsigned long long* mism, unsigned* first,
         hipLaunchKernelGGL(k_selftest<kSelfDiv12>, dim3(4096), dim3(256), 0, stream, mism, first);
     else if (which == kSelfDivRho)
         hipLaunchKernelGGL(k_selftest<kSelfDivRho>, dim3(4096), dim3(256), 0, stream, mism, first);
+    else if (which == kSelfSqrtPos)
+        hipLaunchKernelGGL(k_selftest<kSelfSqrtPos>, dim3(4096), dim3(256), 0, stream, mism, first);
+    else if (which == kSelfRcpIn)
+        hipLaunchKernelGGL(k_selftest<kSelfRcpIn>, dim3(4096), dim3(256), 0, stream, mism, first);
+    else if (which == kSelfPhiloxPx)
+        hipLaunchKernelGGL(k_selftest_philox, dim3(4096), dim3(256), 0, stream, mism, first);
     else
         return hipErrorInvalidValue;
     return hipGetLastError();
@@ -1611,7 +1700,10 @@ static void launch_render_t(const RenderLaunch& a, hipStream_t stream, const Cul
                           "the table route's bench launch outgrew its LDS");
             const dim3 grid((unsigned)(a.n_blocks * a.split));
             KernelTimer kt(KT_RENDER_PS, stream);
-            if (narrow)
+            if (ps_onepx(narrow, a.split))
+                hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1, true, true, true>), grid, dim3(256), ps_lds + mf_lds,
+                                   stream, a, cf);
+            else if (narrow)
                 hipLaunchKernelGGL((k_render_ps<SAMPLER, RULE, 1, true, true>), grid, dim3(256), ps_lds + mf_lds, stream, a,
                                    cf);
             else if (ct)

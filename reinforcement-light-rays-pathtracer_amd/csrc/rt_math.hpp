@@ -55,6 +55,31 @@ __device__ __forceinline__ float rcp_rn_from(float x, float r0) {
 }
 __device__ __forceinline__ float rcp_rn(float x) { return rcp_rn_from(x, __builtin_amdgcn_rcpf(x)); }
 
+// rcp_rn for a caller that knows |x| in [2^-125, 2^125]: v_rcp_f32 and the Newton step alone, no
+// range test and no division behind it.  Equal to IEEE 1.0f / x over that whole domain, both
+// signs (rt_selftest(RT_SELFTEST_RCP_IN), a GPU test).
+__device__ __forceinline__ float rcp_rn_in(float x) {
+    const float r0 = __builtin_amdgcn_rcpf(x);
+    const float e = fmaf(-x, r0, 1.0f);
+    return fmaf(e, r0, r0);
+}
+
+// Correctly rounded sqrt for a caller that knows x = +0 or x in [2^-96, FLT_MAX]: v_sqrt_f32
+// (<= 1 ulp) and the neighbour correction of the compiler's own sqrtf sequence -- s - 1 ulp and
+// s + 1 ulp, their residuals x - n s in FMA, two selects -- without that sequence's scaling of
+// inputs below 2^-96 and without its select for +-0, inf and NaN.  Equal to sqrtf(x) bit for
+// bit over that whole domain, +0 included (rt_selftest(RT_SELFTEST_SQRT_POS), a GPU test).
+__device__ __forceinline__ float sqrt_rn_pos(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float dn = __uint_as_float(__float_as_uint(s) - 1u);
+    const float up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float vp = fmaf(-dn, s, x);
+    const float vs = fmaf(-up, s, x);
+    float r = (vp <= 0.0f) ? dn : s;
+    r = (vs > 0.0f) ? up : r;
+    return r;
+}
+
 // x / 12 for x = +0 or |x| in [2^-100, 2^100]: q = RN(x c), c = RN(1/12), corrected
 // by one FMA residual step; equal to IEEE x / 12.0f over that whole range (checked
 // exhaustively over every float on the host, tools/check_div12.c; -0 gives +0).
@@ -99,6 +124,16 @@ RT_HD f3 normalize(f3 v) {
 #endif
     return make3(v.x * inv, v.y * inv, v.z * inv);
 }
+
+#if defined(__HIPCC__)
+// normalize for a caller that knows dot(v, v) in [2^-96, FLT_MAX] -- its square root then lies
+// in [2^-48, 2^64], inside rcp_rn_in's domain: the same bits as normalize(v), without the
+// sqrt's scaling and class select and without the reciprocal's range test (k_render_ps)
+__device__ __forceinline__ f3 normalize_unit(f3 v) {
+    const float inv = rcp_rn_in(sqrt_rn_pos(dot(v, v)));
+    return make3(v.x * inv, v.y * inv, v.z * inv);
+}
+#endif
 
 // glm compute_cross
 RT_HD f3 cross(f3 x, f3 y) {
@@ -183,6 +218,68 @@ RT_HD void philox_from(const PhiloxShared& s, uint32_t c3, uint32_t out[4]) {
     out[1] = c1;
     out[2] = c2;
     out[3] = c3w;
+}
+
+// Philox4x32-10 blocks of the counter (pixel, sample, event, 0), split by what each product
+// depends on.  Round 1 multiplies the pixel and the event; round 2's second product takes
+// hi(M0 pixel) ^ k1.  So three words belong to the pixel and the key alone (philox_pix), two to the
+// event alone (philox_ev), and only round 2's first product and rounds 3 to 10 see the sample
+// (philox_finish): 17 of the block's 20 products when both halves are in hand.  The same words
+// as philox4x32_10(c0, c1, c2, 0, k0, k1), bit for bit.
+struct PhiloxPix {
+    uint32_t lo0;         // lo(M0 c0): round 2's c3
+    uint32_t q_hi, q_lo;  // M1 (hi(M0 c0) ^ k1): round 2's second product
+};
+struct PhiloxEv {
+    uint32_t hi, lo;  // M1 c2: round 1's second product
+};
+RT_HD PhiloxPix philox_pix(uint32_t c0, uint32_t k0, uint32_t k1) {
+    (void)k0;  // (no pixel word takes the key's low half: round 1 xors it with the sample)
+    PhiloxPix p;
+    const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0;
+    p.lo0 = (uint32_t)p0;
+    const uint64_t q = (uint64_t)0xCD9E8D57u * (uint64_t)((uint32_t)(p0 >> 32) ^ k1);
+    p.q_hi = (uint32_t)(q >> 32);
+    p.q_lo = (uint32_t)q;
+    return p;
+}
+RT_HD PhiloxEv philox_ev(uint32_t c2) {
+    PhiloxEv e;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
+    e.hi = (uint32_t)(p1 >> 32);
+    e.lo = (uint32_t)p1;
+    return e;
+}
+RT_HD void philox_finish(const PhiloxPix& px, const PhiloxEv& ev, uint32_t c1, uint32_t k0, uint32_t k1,
+                         uint32_t out[4]) {
+    const uint32_t n0 = RT_XOR3F(ev.hi, c1, k0);  // round 1's first word
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+    // round 2: (n0, ev.lo, hi(M0 c0) ^ k1, px.lo0)
+    const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)n0;
+    uint32_t c0 = RT_XOR3F(px.q_hi, ev.lo, k0);
+    c1 = px.q_lo;
+    uint32_t c2 = RT_XOR3F((uint32_t)(p0 >> 32), px.lo0, k1);
+    uint32_t c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+#pragma unroll
+    for (int r = 2; r < 10; ++r) {
+        const uint64_t q0 = (uint64_t)0xD2511F53u * (uint64_t)c0;
+        const uint64_t q1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
+        const uint32_t m0 = RT_XOR3F((uint32_t)(q1 >> 32), c1, k0);
+        const uint32_t m2 = RT_XOR3F((uint32_t)(q0 >> 32), c3, k1);
+        c0 = m0;
+        c1 = (uint32_t)q1;
+        c2 = m2;
+        c3 = (uint32_t)q0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0;
+    out[1] = c1;
+    out[2] = c2;
+    out[3] = c3;
 }
 
 // 24-bit uniform in [0, 1)

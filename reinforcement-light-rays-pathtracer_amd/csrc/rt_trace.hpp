@@ -1257,16 +1257,36 @@ __device__ __forceinline__ void draw2(uint32_t pix, uint32_t smp, uint32_t ev, u
     *b = u01(o[1]);
 }
 
+// draw2 with the pixel's Philox words in hand (philox_pix of the pixel and the key: the same for
+// every sample and event of the pixel, and wave-uniform when the wave holds one pixel); the same
+// two uniforms as draw2(pix, smp, ev, k0, k1)
+__device__ __forceinline__ void draw2_px(const PhiloxPix& px, uint32_t smp, uint32_t ev, uint32_t k0, uint32_t k1,
+                                         float* a, float* b) {
+#ifdef RT_TIMING_CHEAP_RNG
+    // timing-only build (wrong images), as draw2's: px.lo0 stands for the pixel
+    const uint32_t h = px.lo0 ^ (smp * 0x85EBCA6Bu) ^ (ev * 0xC2B2AE35u) ^ k0;
+    *a = u01(h * 0x27D4EB2Fu);
+    *b = u01((h ^ (h >> 15)) * 0x165667B1u);
+    return;
+#endif
+    uint32_t o[4];
+    philox_finish(px, philox_ev(ev), smp, k0, k1, o);
+    *a = u01(o[0]);
+    *b = u01(o[1]);
+}
+
 // Camera ray through (px+r1, py+r2): default_path_tracing.cpp:25-34, Ray::Ray
 // (ray.cpp:7-11), rotate_ray (ray.cpp:47-52; GPU/rays/ray.cu:161-172), with
 // glm's mat4*vec4 order (m0*v0 + m1*v1) + (m2*v2 + m3*v3).
-template <int PRESET>
+// UNIT: the normalize without its range guards (normalize_unit, rt_math.hpp; ps_body alone
+// selects it).  dot(dir, dir) >= height^2 >= 1, and with |x|, |y| < 2^24 it is below 2^50.
+template <int PRESET, bool UNIT = false>
 __device__ __forceinline__ void camera_ray(const RenderLaunch& a, int px, int py, float r1, float r2,
                                            f3* d_out) {
     const float x = (float)px + r1;
     const float y = (float)py + r2;
     f3 dir = make3(x - (float)a.width / 2.0f, y - (float)a.height / 2.0f, (float)a.height);
-    dir = normalize(dir);
+    dir = UNIT ? normalize_unit(dir) : normalize(dir);
     const float w = 1.0f;
     f3 r;
     r.x = (a.cos_y * dir.x + 0.0f * dir.y) + (-a.sin_y * dir.z + 0.0f * w);
