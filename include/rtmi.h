@@ -343,6 +343,13 @@ int rt_dqn_train_step_device(rt_ctx* ctx, rt_dqn_trainer* trainer, const float* 
 int rt_dqn_td_targets_device(rt_ctx* ctx, uint64_t seed, const float* d_next_q, const int32_t* d_terminal,
                              const float* d_reward, const float* d_discount, const uint32_t* d_pix, int sample,
                              int bounce, int n, float* d_target, void* stream);
+/* Q of n positions from the trainer's current parameters: the forward pass that
+ * rt_dqn_train_step_device and rt_neuralq_render_frame run (fp32, not the bf16 inference
+ * network of rt_dqn_forward), its output copied to d_q (device, n x n_out row-major).
+ * d_loc: device, n x 3.  Read-only for the trainer: parameters, Adam moments and the update
+ * count are untouched (the workspace may grow).  Asynchronous on `stream`. */
+int rt_dqn_trainer_forward_device(rt_ctx* ctx, rt_dqn_trainer* trainer, const float* d_loc, int n, float* d_q,
+                                  void* stream);
 
 /* ---- Q-network fit to a radiance map (the reference's NN_Q_Value_Trainer) ----
  * The supervised stage between rt_sarsa_save_q and rt_render_dqn
@@ -429,7 +436,7 @@ int rt_dqn_fit_epoch(rt_ctx* ctx, rt_dqn_fit* fit, double* loss_out, double* err
  * Reference settings: batch 4096, epsilon 0.05 / 0.05 / 0.01 (deep_learning_settings.h).
  * stats (optional, spp x 3 floats): per sample the nn_training_stats.txt values (:553-583):
  * average path length (sum of termination bounces / pixels), loss (summed over batches),
- * zero-contribution paths ((r + g + b) / 3 < THROUGHPUT_THRESHOLD).  out_rgb: W x H x 3 or
+ * zero-contribution paths (every channel < THROUGHPUT_THRESHOLD).  out_rgb: W x H x 3 or
  * NULL.  Pixel ids key the RNG (Philox; seed = params->seed); successive frames continue
  * the sample sequence. */
 typedef struct rt_neuralq rt_neuralq;
@@ -439,6 +446,15 @@ int rt_neuralq_destroy(rt_neuralq* nq);
 int rt_neuralq_epsilon(const rt_neuralq* nq, float* epsilon);
 int rt_neuralq_render_frame(rt_ctx* ctx, rt_neuralq* nq, const rt_camera* cam, const rt_params* params,
                             float* out_rgb, float* stats, uint64_t* out_ray_casts);
+/* The per-ray arrays as the last frame left them (host copies, one ray per pixel, id =
+ * y * width + x; for checks): position, throughput, throughput summed over the frame's samples
+ * (n x 3 each), surface of the position, state (0 contributing, 1 terminal, 2 restarted),
+ * bounce of termination, sampled action, reward, discount, terminal flag (n each).  NULL
+ * outputs are skipped; n_rays (optional) receives n, so a first call with only n_rays sizes
+ * the buffers.  RT_E_INVALID before the first frame.  A blocking copy. */
+int rt_neuralq_read_rays(const rt_neuralq* nq, float* loc, float* throughput, float* total, int32_t* tri,
+                         uint32_t* state, uint32_t* bounces, int32_t* action, float* reward, float* discount,
+                         int32_t* terminal, int32_t* n_rays);
 
 /* ---- Expected-SARSA radiance volumes (BASELINE config 3) ------------------ */
 typedef struct rt_sarsa rt_sarsa;

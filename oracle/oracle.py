@@ -506,6 +506,104 @@ def td_targets(seed, next_q, terminal, reward, discount, pix, sample, bounce):
     return out
 
 
+ORC_STEP_FN = ctypes.CFUNCTYPE(ctypes.c_float, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32),
+                               ctypes.POINTER(ctypes.c_float), ctypes.c_int, ctypes.c_void_p)
+
+# orc_neuralq_frame's branch counters, in its order
+NQ_COUNTERS = ("greedy", "explore", "no_cell", "miss", "light", "restart", "second_restart", "live_at_cap")
+# its per-ray arrays: (name, dtype, components)
+NQ_RAYS = (("loc", np.float32, 3), ("tp", np.float32, 3), ("total", np.float32, 3), ("tri", np.int32, 1),
+           ("state", np.uint32, 1), ("bounces", np.uint32, 1), ("action", np.int32, 1), ("reward", np.float32, 1),
+           ("discount", np.float32, 1), ("terminal", np.int32, 1))
+# the negative controls (orc_neuralq_frame's variant argument)
+NQ_VARIANTS = {"none": 0, "target_event": 1, "restart_no_swap": 2, "tp_state2": 3, "q_before_step": 4,
+               "prev_surface_only": 5}
+
+
+class NeuralQ:
+    """The Neural-Q training frame restated (rt_oracle.c orc_neuralq_frame) around a network the
+    caller owns: q_fn(loc (n, 3) float32) -> (n, 144) float32 and step_fn(prev (n, 3), action (n,)
+    int32, target (n,) float32) -> loss are called exactly where the renderer evaluates and updates
+    its network (q_fn over all rays before sampling; per batch q_fn on the batch's new positions,
+    then step_fn).  Epsilon and the frame count carry over from frame to frame."""
+
+    def __init__(self, geom, q_fn, step_fn, batch_size=4096, epsilon_start=0.05, epsilon_min=0.05,
+                 epsilon_decay=0.01, variant="none"):
+        get = (lambda k: geom[k]) if isinstance(geom, dict) else (lambda k: getattr(geom, k))
+        self._tri = np.ascontiguousarray(np.concatenate([get("tri"), get("light")], 0), np.float32)
+        self._alb = np.ascontiguousarray(get("albedo"), np.float32)
+        self._em = np.ascontiguousarray(get("emission"), np.float32)
+        self._grp = np.ascontiguousarray(get("light_group"), np.int32)
+        self._ns, self._nl = get("tri").shape[0], get("light").shape[0]
+        self.q_fn, self.step_fn = q_fn, step_fn
+        self.batch = int(batch_size)
+        self.epsilon = float(np.float32(epsilon_start))
+        self.eps_min, self.eps_decay = float(epsilon_min), float(epsilon_decay)
+        self.variant = NQ_VARIANTS[variant]
+        self.frames = 0
+        self.calls = []  # ("q", n) / ("step", n) in call order, all frames
+
+    def render_frame(self, cam: OrcCamera, params: OrcParams) -> dict:
+        """{"img" (H, W, 3), "stats" (spp, 3), "casts", "epsilon", "rays": {name: array},
+        "counters": {name: count}} of the next frame."""
+        L = lib()
+        U32, U64 = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64)
+        L.orc_neuralq_frame.argtypes = [_FP, _FP, ctypes.c_int, _FP, _IP, ctypes.c_int, ctypes.POINTER(OrcCamera),
+                                        ctypes.POINTER(OrcParams), ctypes.c_int, ctypes.c_int, _FP, ctypes.c_float,
+                                        ctypes.c_float, ORC_Q_FN, ORC_STEP_FN, ctypes.c_void_p, ctypes.c_int,
+                                        _FP, _FP, U64, _FP, _FP, _FP, _IP, U32, U32, _IP, _FP, _FP, _IP, U64]
+        L.orc_neuralq_frame.restype = ctypes.c_int
+        n = params.width * params.height
+        img = np.zeros((params.height, params.width, 3), np.float32)
+        stats = np.zeros((params.spp, 3), np.float32)
+        casts = ctypes.c_uint64(0)
+        eps = ctypes.c_float(self.epsilon)
+        rays = {name: np.zeros((n, c) if c > 1 else n, dt) for name, dt, c in NQ_RAYS}
+        counters = np.zeros(len(NQ_COUNTERS), np.uint64)
+        failure = []
+
+        def q_cb(loc_p, m, q_p, _user):
+            try:
+                loc = np.ctypeslib.as_array(loc_p, shape=(m, 3)).copy()
+                q = np.ascontiguousarray(self.q_fn(loc), np.float32)
+                assert q.shape == (m, 144), q.shape
+                ctypes.memmove(q_p, q.ctypes.data, q.nbytes)
+                self.calls.append(("q", m))
+            except BaseException as e:  # (an exception cannot cross the C frame: kept for after it)
+                failure.append(e)
+                ctypes.memset(q_p, 0, 4 * 144 * m)
+
+        def step_cb(prev_p, act_p, tgt_p, m, _user):
+            try:
+                prev = np.ctypeslib.as_array(prev_p, shape=(m, 3)).copy()
+                act = np.ctypeslib.as_array(act_p, shape=(m,)).copy()
+                tgt = np.ctypeslib.as_array(tgt_p, shape=(m,)).copy()
+                self.calls.append(("step", m))
+                return float(self.step_fn(prev, act, tgt))
+            except BaseException as e:
+                failure.append(e)
+                return 0.0
+
+        def ptr(a):
+            return a.ctypes.data_as({np.dtype(np.float32): _FP, np.dtype(np.int32): _IP,
+                                     np.dtype(np.uint32): U32}[a.dtype])
+
+        rc = L.orc_neuralq_frame(_f(self._tri), _f(self._alb), self._ns, _f(self._em), _i(self._grp), self._nl,
+                                 ctypes.byref(cam), ctypes.byref(params), self.batch, self.frames, ctypes.byref(eps),
+                                 self.eps_min, self.eps_decay, ORC_Q_FN(q_cb), ORC_STEP_FN(step_cb), None,
+                                 self.variant, _f(img), _f(stats), ctypes.byref(casts),
+                                 *[ptr(rays[name]) for name, _, _ in NQ_RAYS],
+                                 counters.ctypes.data_as(U64))
+        if failure:
+            raise failure[0]
+        if rc != 0:
+            raise ValueError("orc_neuralq_frame: bad batch / image size / spp / max_bounces, or no surfaces")
+        self.epsilon = float(eps.value)
+        self.frames += 1
+        return {"img": img, "stats": stats, "casts": int(casts.value), "epsilon": self.epsilon, "rays": rays,
+                "counters": {k: int(v) for k, v in zip(NQ_COUNTERS, counters)}}
+
+
 class AdamRef:
     """fp64 restatement of one Neural-Q learning step (neural_q_pathtracer.cu:478-513):
     DQNetwork forward (b + W x, rectify x 4; NN_Builders/fc_layer.cu:40-72), pick, loss =

@@ -1882,16 +1882,16 @@ ORC_API int orc_render_sarsa_rect(orc_sarsa *m, const orc_camera *cam, const orc
  * at the raw Q of action 0 and weights actions 1.. by the cosine of a jittered direction in
  * their cell (here the Chiu map's cos with the sampler's Philox jitters: counter
  * (pix, sample, 1 + bounce, 1 + a/2)), as rt_dqn_td_targets_device. */
-ORC_API void orc_td_targets(uint64_t seed, const float *next_q, const int32_t *terminal, const float *reward,
-                            const float *discount, const uint32_t *pix, int sample, int bounce, int n,
-                            float *target) {
+static void td_targets_ev(uint64_t seed, const float *next_q, const int32_t *terminal, const float *reward,
+                          const float *discount, const uint32_t *pix, uint32_t sample, uint32_t ev, int n,
+                          float *target) {
     uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
     for (int b = 0; b < n; b++) {
         if (terminal[b] == 1) { target[b] = reward[b]; continue; }
         const float *q = next_q + (size_t)b * 144;
         float best = q[0];
         for (int a2 = 0; a2 < 144; a2 += 2) {
-            uint32_t ctr[4] = {pix[b], (uint32_t)sample, 1u + (uint32_t)bounce, 1u + (uint32_t)(a2 >> 1)};
+            uint32_t ctr[4] = {pix[b], sample, ev, 1u + (uint32_t)(a2 >> 1)};
             uint32_t o[4];
             orc_philox4x32_10(ctr, key, o);
             for (int h = 0; h < 2; h++) {
@@ -1905,4 +1905,272 @@ ORC_API void orc_td_targets(uint64_t seed, const float *next_q, const int32_t *t
         }
         target[b] = reward[b] + best * discount[b];
     }
+}
+
+ORC_API void orc_td_targets(uint64_t seed, const float *next_q, const int32_t *terminal, const float *reward,
+                            const float *discount, const uint32_t *pix, int sample, int bounce, int n,
+                            float *target) {
+    td_targets_ev(seed, next_q, terminal, reward, discount, pix, (uint32_t)sample, 1u + (uint32_t)bounce, n, target);
+}
+
+/* ================================================================== */
+/* Neural-Q training frame                                             */
+/* ================================================================== */
+/* NeuralQPathtracer::render_frame (GPU/deep_learning/neural_q_pathtracer.cu:226-600) in the
+ * reference's per-ray arrays, one ray per pixel (id = y * width + x), in its order:
+ *   per sample: initialise_ray (:604-643);
+ *     per bounce b: (b > 0) Q of every ray's position, then sample_batch_ray_directions_epsilon_greedy
+ *       (nn_rendering_helpers.cu:330-389): greedy rows importance_sample_direction (dqn_sample; a
+ *       row whose Q admits no cell keeps its direction and takes action 0), explore rows a
+ *       uniformly chosen jittered cell; trace_ray (:646-745; GPU hit rule; throughput, path length
+ *       and the rays_finished flag only for paths still contributing, state 0); (b > 0) per batch
+ *       of `batch` rays the learning rule (:420-513): Q at the new positions, compute_td_targets,
+ *       trainer.update on the positions before the trace and the sampled actions;
+ *       sample_random_scene_pos_for_terminated_rays (nn_rendering_helpers.cu:241-277: the new
+ *       position stored with y and z exchanged, state 2); leave the loop once no path bounced;
+ *     update_total_throughput, sum_path_lengths, sum_zero_contribution_light_paths; epsilon decays;
+ *   update_device_buffer: total / spp.
+ * The network is not evaluated here.  q_fn(loc, n, q) returns Q [n][144] of n positions and
+ * step_fn(prev, action, target, n) runs one update and returns its loss; they are called exactly
+ * where the reference evaluates and updates its network: q_fn once over all rays before
+ * sampling, then per batch q_fn on the batch's new positions followed by step_fn.
+ * The state the update trains on.  The reference is built with TRAIN_ON_POSITION false
+ * (constants/deep_learning_settings.h:10): the network's input is the scene's vertices in the
+ * ray's coordinate system, ray_vertices = vertices - ray_locations
+ * (convert_vertices_to_point_coord_system, nn_rendering_helpers.cu:281-298), which is also this
+ * project's network input (nn_vertices - loc).  ray_vertices is converted at the top of the
+ * bounce (:292), from every ray's position before the trace, and copied to prev_ray_vertices after
+ * the trace (:405-408); trainer.update reads prev_ray_vertices (:487-489).  So S_t is the position
+ * before the trace for every ray, whether the trace ends on a surface, a light or nothing:
+ * `prev` below, set for every ray.  prev_ray_locations, which trace_ray writes on surface hits
+ * only (:714-716), is read only under TRAIN_ON_POSITION true (:482-485), a build the reference
+ * does not ship and whose 3-input network this project does not have; variant 5 restates that
+ * array instead, as a control that the comparison tells the two apart.
+ * Conventions of this project that the restatement adopts where the reference's own cannot be
+ * reproduced or differ without effect on the algorithm: the ray id is
+ * y * width + x (the reference: SCREEN_HEIGHT * x + y, its pixel-to-thread map); a sample's loss
+ * is summed over the batches in double and rounded to float once (the reference adds floats,
+ * :276, :508); a restart's rejection loop stops after 64 attempts and then mirrors the point
+ * into the triangle (Triangle::sample_position_on_plane loops without a bound; 2^-64); the random
+ * numbers are Philox draws keyed as follows, not cuRAND's.
+ * Philox events (pixel, frame * spp + sample, event, counter): 0 the camera jitter, 1 + b the
+ * greedy sampler, 0x1000 + b the epsilon draw (word 0, (0, 1]) and the exploration cell (word 1)
+ * and its jitters (words 2, 3), 0x2000 + b a restart's surface, 0x3000 + b (counter = attempt) its
+ * point, 0x4000 + b the targets' cell jitters.
+ * variant (negative controls of the tests; 0 = the algorithm): 1 the targets draw from event
+ * 1 + b; 2 the restart position without the y/z exchange; 3 throughput also updated for
+ * restarted rays (state 2); 4 next-state Q of every batch taken before the bounce's first update;
+ * 5 the update's state taken from prev_ray_locations (written on surface hits only).
+ * counters [8]: greedy rows, explore rows, greedy rows with no selectable cell, misses, light
+ * hits, restarts, second restarts of a ray within a sample, rays still live after the last
+ * bounce of a sample. */
+typedef float (*orc_step_fn)(const float *prev, const int32_t *action, const float *target, int n, void *user);
+
+ORC_API int orc_neuralq_frame(const float *tri, const float *albedo, int n_surf, const float *emission,
+                              const int32_t *light_group, int n_light, const orc_camera *cam,
+                              const orc_params *p, int batch, int frame, float *eps_io, float eps_min,
+                              float eps_decay, orc_q_fn q_fn, orc_step_fn step_fn, void *user, int variant,
+                              float *out_rgb, float *stats, uint64_t *out_casts, float *o_loc, float *o_tp,
+                              float *o_total, int32_t *o_tri, uint32_t *o_state, uint32_t *o_bounces,
+                              int32_t *o_action, float *o_reward, float *o_discount, int32_t *o_terminal,
+                              uint64_t *counters) {
+    if (batch <= 0 || p->width <= 0 || p->height <= 0 || p->spp <= 0 || p->max_bounces < 1 || n_surf <= 0) return -1;
+    orc_scene sc;
+    scene_init(&sc, tri, albedo, n_surf, emission, light_group, n_light);
+    const float cy = (float)cos((double)cam->yaw_y), sy = (float)sin((double)cam->yaw_y);
+    const float cx = (float)cos((double)cam->yaw_x), sx = (float)sin((double)cam->yaw_x);
+    const int n = p->width * p->height;
+    const uint32_t key[2] = {(uint32_t)p->seed, (uint32_t)(p->seed >> 32)};
+    const float RHO = 1.0f / (2.0f * 3.1415926535f);
+    float *lum = (float *)malloc(sizeof(float) * (size_t)(n_surf + n_light));
+    for (int j = 0; j < n_surf; j++) lum[j] = lum3(albedo + 3 * (size_t)j);
+    for (int j = 0; j < n_light; j++) lum[n_surf + j] = lum3(emission + 3 * (size_t)j);
+    float *prev = (float *)malloc(sizeof(float) * 3 * (size_t)n), *dir = (float *)malloc(sizeof(float) * 3 * (size_t)n);
+    float *q = (float *)malloc(sizeof(float) * 144 * (size_t)n), *target = (float *)malloc(sizeof(float) * (size_t)n);
+    uint32_t *pix = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n);
+    int *restarts = (int *)malloc(sizeof(int) * (size_t)n);
+    float *loc = o_loc, *tp = o_tp, *total = o_total, *reward = o_reward, *discount = o_discount;
+    int32_t *rtri = o_tri, *action = o_action, *terminal = o_terminal;
+    uint32_t *state = o_state, *bounces = o_bounces;
+    uint64_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, casts = 0;
+    float eps = *eps_io;
+    for (int i = 0; i < 3 * n; i++) total[i] = 0.0f;
+    for (int i = 0; i < n; i++) terminal[i] = 0;
+    const uint32_t base = (uint32_t)frame * (uint32_t)p->spp;
+    for (int s = 0; s < p->spp; s++) {
+        const uint32_t smp = base + (uint32_t)s;
+        double loss = 0.0;
+        for (int i = 0; i < n; i++) {
+            float r1, r2;
+            draw2(p->seed, (uint32_t)i, smp, 0u, &r1, &r2);
+            v3 o, d;
+            orc_params pg = *p;
+            pg.preset = 1;
+            camera_ray(cam, &pg, cy, sy, cx, sx, i % p->width, i / p->width, r1, r2, &o, &d);
+            loc[3 * i] = prev[3 * i] = o.x; loc[3 * i + 1] = prev[3 * i + 1] = o.y; loc[3 * i + 2] = prev[3 * i + 2] = o.z;
+            dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
+            tp[3 * i] = tp[3 * i + 1] = tp[3 * i + 2] = 1.0f;
+            rtri[i] = -1;
+            state[i] = 0u;
+            reward[i] = 0.0f;
+            discount[i] = 1.0f;
+            bounces[i] = (uint32_t)p->max_bounces;
+            action[i] = 0;
+            pix[i] = (uint32_t)i;
+            restarts[i] = 0;
+        }
+        for (int b = 0; b < p->max_bounces; b++) {
+            if (b > 0) {
+                q_fn(loc, n, q, user);
+                for (int i = 0; i < n; i++) {
+                    const float *nn = sc.normal + (size_t)rtri[i] * 3;
+                    const v3 N = mk(nn[0], nn[1], nn[2]);
+                    const v3 pos = mk(loc[3 * i], loc[3 * i + 1], loc[3 * i + 2]);
+                    v3 t = mk(tp[3 * i], tp[3 * i + 1], tp[3 * i + 2]);
+                    const int upd = state[i] == 0u || (variant == 3 && state[i] == 2u);
+                    uint32_t ctr[4] = {pix[i], smp, 0x1000u + (uint32_t)b, 0u}, o[4];
+                    orc_philox4x32_10(ctr, key, o);
+                    if (u01_oc(o[0]) > eps) {
+                        v3 tn = t, d;
+                        const int act = dqn_sample(q + (size_t)i * 144, N, pos, p->seed, pix[i], smp, 1u + (uint32_t)b,
+                                                   &tn, &d);
+                        cnt[0]++;
+                        if (act >= 0) {
+                            dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
+                            action[i] = act;
+                            if (upd) t = tn;
+                        } else {
+                            action[i] = 0;
+                            cnt[2]++;
+                        }
+                    } else {
+                        const float u = u01_oc(o[1]) - 0.0001f;
+                        int idx = (int)(u * 144.0f);
+                        idx = idx < 0 ? 0 : (idx > 143 ? 143 : idx);
+                        const int gx = idx / 12, gy = idx - gx * 12;
+                        v3 T, B;
+                        normal_frame(N, &T, &B);
+                        const v3 d = grid_dir((float)gx + u01(o[2]), (float)gy + u01(o[3]), N, T, B, pos);
+                        if (upd) {
+                            const float c = dot3(N, d);
+                            t = mk((t.x * c) / RHO, (t.y * c) / RHO, (t.z * c) / RHO);
+                        }
+                        dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z;
+                        action[i] = idx;
+                        cnt[1]++;
+                    }
+                    tp[3 * i] = t.x; tp[3 * i + 1] = t.y; tp[3 * i + 2] = t.z;
+                }
+            }
+            int finished = 1;
+            for (int i = 0; i < n; i++) {
+                const v3 pos = mk(loc[3 * i], loc[3 * i + 1], loc[3 * i + 2]);
+                const v3 dr = mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
+                const v3 o = mk(pos.x + dr.x * 1e-5f, pos.y + dr.y * 1e-5f, pos.z + dr.z * 1e-5f);
+                const v3 d = normalize3(dr);
+                const hit_t h = closest_hit(&sc, o, d, p->t_scale, 1);
+                casts++;
+                /* S_t of the update: the position the ray's vertices were converted at (see above) */
+                if (variant != 5 || (h.tri >= 0 && h.tri < n_surf)) {
+                    prev[3 * i] = pos.x; prev[3 * i + 1] = pos.y; prev[3 * i + 2] = pos.z;
+                }
+                const uint32_t st = state[i];
+                const int upd = st == 0u || (variant == 3 && st == 2u);
+                v3 t = mk(tp[3 * i], tp[3 * i + 1], tp[3 * i + 2]);
+                if (h.tri < 0 || h.tri >= n_surf) {
+                    const int light = h.tri >= 0;
+                    cnt[light ? 4 : 3]++;
+                    reward[i] = light ? lum[h.tri] * 200.0f : 0.0f;
+                    discount[i] = 0.0f;
+                    if (upd) {
+                        if (light) {
+                            const float *e = emission + (size_t)(h.tri - n_surf) * 3;
+                            t = mk(t.x * e[0], t.y * e[1], t.z * e[2]);
+                        } else {
+                            t = mk(t.x * p->env_light, t.y * p->env_light, t.z * p->env_light);
+                        }
+                    }
+                    if (st == 0u) bounces[i] = (uint32_t)b;
+                    state[i] = 1u;
+                    terminal[i] = 1;
+                } else {
+                    const v3 D = mk(d.x * p->t_scale, d.y * p->t_scale, d.z * p->t_scale);
+                    loc[3 * i] = o.x + h.t * D.x; loc[3 * i + 1] = o.y + h.t * D.y; loc[3 * i + 2] = o.z + h.t * D.z;
+                    rtri[i] = h.tri;
+                    if (upd) {
+                        const float *al = albedo + (size_t)h.tri * 3;
+                        t = mk(t.x * (al[0] / PI_F), t.y * (al[1] / PI_F), t.z * (al[2] / PI_F));
+                    }
+                    if (st == 0u) finished = 0;
+                    reward[i] = 0.0f;
+                    discount[i] = lum[h.tri];
+                    terminal[i] = 0;
+                }
+                tp[3 * i] = t.x; tp[3 * i + 1] = t.y; tp[3 * i + 2] = t.z;
+            }
+            if (b > 0) {
+                const uint32_t ev = variant == 1 ? 1u + (uint32_t)b : 0x4000u + (uint32_t)b;
+                if (variant == 4) q_fn(loc, n, q, user);
+                for (int b0 = 0; b0 < n; b0 += batch) {
+                    const int nb = batch < n - b0 ? batch : n - b0;
+                    float *qb = q + (size_t)b0 * 144;
+                    if (variant != 4) q_fn(loc + 3 * (size_t)b0, nb, qb, user);
+                    td_targets_ev(p->seed, qb, terminal + b0, reward + b0, discount + b0, pix + b0, smp, ev, nb,
+                                  target + b0);
+                    loss += (double)step_fn(prev + 3 * (size_t)b0, action + b0, target + b0, nb, user);
+                }
+            }
+            for (int i = 0; i < n; i++) {
+                if (state[i] != 1u) continue;
+                uint32_t ctr[4] = {pix[i], smp, 0x2000u + (uint32_t)b, 0u}, o[4];
+                orc_philox4x32_10(ctr, key, o);
+                int sf = (int)((float)n_surf * u01_oc(o[0]));
+                sf = sf < n_surf ? sf : n_surf - 1;
+                const float *v = tri + (size_t)sf * 9;
+                float a1, a2;
+                uint32_t attempt = 0;
+                ctr[2] = 0x3000u + (uint32_t)b;
+                do {
+                    ctr[3] = attempt++;
+                    orc_philox4x32_10(ctr, key, o);
+                    a1 = u01_oc(o[0]);
+                    a2 = u01_oc(o[1]);
+                } while (a1 + a2 > 1.0f && attempt < 64u);
+                if (a1 + a2 > 1.0f) { a1 = 1.0f - a1; a2 = 1.0f - a2; }
+                float pt[3];
+                for (int c = 0; c < 3; c++) pt[c] = (v[c] + a1 * (v[3 + c] - v[c])) + a2 * (v[6 + c] - v[c]);
+                loc[3 * i] = pt[0];
+                loc[3 * i + 1] = variant == 2 ? pt[1] : pt[2];
+                loc[3 * i + 2] = variant == 2 ? pt[2] : pt[1];
+                rtri[i] = sf;
+                state[i] = 2u;
+                cnt[5]++;
+                if (++restarts[i] == 2) cnt[6]++;
+            }
+            if (finished) break;
+        }
+        uint64_t sum_b = 0, zero = 0;
+        for (int i = 0; i < n; i++) {
+            for (int c = 0; c < 3; c++) total[3 * i + c] = total[3 * i + c] + tp[3 * i + c];
+            sum_b += bounces[i];
+            if (tp[3 * i] < 0.0001f && tp[3 * i + 1] < 0.0001f && tp[3 * i + 2] < 0.0001f) zero++;
+            if (state[i] == 0u) cnt[7]++;
+        }
+        const float dec = eps - eps_decay;
+        eps = dec > eps_min ? dec : eps_min;
+        if (stats) {
+            stats[3 * s + 0] = (float)sum_b / ((float)p->height * (float)p->width);
+            stats[3 * s + 1] = (float)loss;
+            stats[3 * s + 2] = (float)zero;
+        }
+    }
+    const float fs = (float)p->spp;
+    if (out_rgb)
+        for (int i = 0; i < 3 * n; i++) out_rgb[i] = total[i] / fs;
+    *eps_io = eps;
+    if (out_casts) *out_casts = casts;
+    if (counters) memcpy(counters, cnt, sizeof(cnt));
+    free(lum); free(prev); free(dir); free(q); free(target); free(pix); free(restarts);
+    free(sc.normal);
+    return 0;
 }

@@ -1155,7 +1155,12 @@ __global__ __launch_bounds__(256) void k_nq_sample(const DqnLaunch a, const NqRa
 // miss: reward 0, terminal; light: reward = its luminance x 200, terminal; surface: the
 // new state, discount = the material's luminance.  Throughputs and path lengths change
 // only for paths still contributing (state 0).  The position before the trace is the
-// learning rule's S_t.  BVH: the scene's exact BVH (large scenes), a stack column per lane.
+// learning rule's S_t for every ray, terminating or not: the reference (TRAIN_ON_POSITION
+// false, deep_learning_settings.h:10) updates on prev_ray_vertices, the copy (:405-408) of the
+// vertices converted at the top of the bounce from every ray's position (:292), and `prev`
+// is that position (the network's input is nn_vertices - prev).  prev_ray_locations, which
+// trace_ray writes on surface hits only (:714-716), is read only in the TRAIN_ON_POSITION
+// build (:482-485).  BVH: the scene's exact BVH (large scenes), a stack column per lane.
 template <bool BVH>
 __global__ __launch_bounds__(256) void k_nq_trace(const DqnLaunch a, const NqRays r, int bounce) {
     __shared__ int s_stk[BVH ? kBvhMaxDepth * 256 : 1];

@@ -931,6 +931,21 @@ int rt_dqn_td_targets_device(rt_ctx* ctx, uint64_t seed, const float* d_next_q, 
     return RT_OK;
 }
 
+int rt_dqn_trainer_forward_device(rt_ctx* ctx, rt_dqn_trainer* t, const float* d_loc, int n, float* d_q,
+                                  void* stream) {
+    if (!ctx || !t || !d_loc || !d_q) return err(RT_E_INVALID, "NULL argument");
+    if (n <= 0) return err(RT_E_INVALID, "empty batch");
+    if (t->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "trainer belongs to another device");
+    RT_HIPE(hipSetDevice(t->device));
+    int rc = ensure_ws(t, n);
+    if (rc != RT_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    rc = trainer_forward(t, d_loc, n, st);
+    if (rc != RT_OK) return rc;
+    RT_HIPE(hipMemcpyAsync(d_q, t->H[3], sizeof(float) * (size_t)n * t->dims[4], hipMemcpyDeviceToDevice, st));
+    return RT_OK;
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------
@@ -1165,6 +1180,31 @@ int rt_neuralq_render_frame(rt_ctx* ctx, rt_neuralq* q, const rt_camera* cam, co
     RT_HIPE(hipMemcpyAsync(&casts, r.stats + 2, sizeof(casts), hipMemcpyDeviceToHost, st));
     RT_HIPE(hipStreamSynchronize(st));
     if (out_ray_casts) *out_ray_casts = casts;
+    return RT_OK;
+}
+
+int rt_neuralq_read_rays(const rt_neuralq* q, float* loc, float* throughput, float* total, int32_t* tri,
+                         uint32_t* state, uint32_t* bounces, int32_t* action, float* reward, float* discount,
+                         int32_t* terminal, int32_t* n_rays) {
+    if (!q) return err(RT_E_INVALID, "NULL argument");
+    if (q->frames == 0 || q->r.n <= 0) return err(RT_E_INVALID, "no frame has been rendered");
+    RT_HIPE(hipSetDevice(q->device));
+    const rt::NqRays& r = q->r;
+    const size_t n = (size_t)r.n;
+    if (n_rays) *n_rays = (int32_t)r.n;
+    const struct {
+        void* dst;
+        const void* src;
+        size_t bytes;
+    } copies[] = {
+        {loc, r.loc, sizeof(float) * 3 * n},      {throughput, r.tp, sizeof(float) * 3 * n},
+        {total, r.total, sizeof(float) * 3 * n},  {tri, r.tri, sizeof(int32_t) * n},
+        {state, r.state, sizeof(uint32_t) * n},   {bounces, r.bounces, sizeof(uint32_t) * n},
+        {action, r.action, sizeof(int32_t) * n},  {reward, r.reward, sizeof(float) * n},
+        {discount, r.discount, sizeof(float) * n}, {terminal, r.terminal, sizeof(int32_t) * n},
+    };
+    for (const auto& c : copies)
+        if (c.dst) RT_HIPE(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

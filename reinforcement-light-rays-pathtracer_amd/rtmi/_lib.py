@@ -64,10 +64,11 @@ EXPORTS = (
     "rt_sarsa_nearest", "rt_render_sarsa", "rt_render_sarsa_tiles_device", "rt_sarsa_td_device",
     "rt_sarsa_apply", "rt_sarsa_set_search", "rt_sarsa_search_stats", "rt_sarsa_save_q",
     "rt_neuralq_create", "rt_neuralq_destroy", "rt_neuralq_epsilon", "rt_neuralq_render_frame",
+    "rt_neuralq_read_rays",
     "rt_sarsa_save_selected", "rt_sarsa_load_q", "rt_sarsa_set_sampling", "rt_sarsa_set_td_mode", "rt_sarsa_get_td_mode", "rt_sarsa_set_inframe_lanes", "rt_sarsa_frame_stats",
     "rt_dqn_save_selected",
     "rt_dqn_trainer_create", "rt_dqn_trainer_destroy", "rt_dqn_trainer_params", "rt_dqn_trainer_gradients",
-    "rt_dqn_train_step_device",
+    "rt_dqn_train_step_device", "rt_dqn_trainer_forward_device",
     "rt_dqn_td_targets_device",
     "rt_scene_set_accel", "rt_scene_accel_info", "rt_scene_ctab_info", "rt_bvh_check",
     "rt_ktime_enable", "rt_ktime_read", "rt_ktime_name",
@@ -170,6 +171,7 @@ def _declare(lib):
         "rt_dqn_trainer_params": (i, [_P, ctypes.POINTER(_FP), ctypes.POINTER(_FP)]),
         "rt_dqn_trainer_gradients": (i, [_P, ctypes.POINTER(_FP), ctypes.POINTER(_FP)]),
         "rt_dqn_train_step_device": (i, [_P, _P, _P, _P, _P, i, _FP, _FP, _P]),
+        "rt_dqn_trainer_forward_device": (i, [_P, _P, _P, i, _P, _P]),
         "rt_dqn_td_targets_device": (i, [_P, ctypes.c_uint64, _P, _P, _P, _P, _P, i, i, i, _P, _P]),
         "rt_dqn_forward": (i, [_P, _P, _FP, i, _FP]),
         "rt_dqn_forward_device": (i, [_P, _P, _P, i, _P, _P]),
@@ -192,6 +194,7 @@ def _declare(lib):
         "rt_neuralq_destroy": (i, [_P]),
         "rt_neuralq_epsilon": (i, [_P, _FP]),
         "rt_neuralq_render_frame": (i, [_P, _P, _P, _P, _FP, _FP, _U64P]),
+        "rt_neuralq_read_rays": (i, [_P, _FP, _FP, _FP, _IP, _UP, _UP, _IP, _FP, _FP, _IP, _IP]),
         "rt_sarsa_load_q": (i, [_P, ctypes.c_char_p]),
         "rt_sarsa_frame_stats": (i, [_P, _U64P, _U64P]),
         "rt_sarsa_save_q": (i, [_P, ctypes.c_char_p]),

@@ -10,7 +10,10 @@
   Dqn(ctx, nn_vertices, weights)   device network (rt_dqn_create)
   forward / sample / render / render_tiles_device
   DqnTrainer(ctx, nn_vertices, weights)   Neural-Q training (rt_dqn_trainer_*): TD targets,
-                          one Adam step per batch, parameters out for a new Dqn
+                          one Adam step per batch, parameters out for a new Dqn; forward_device
+                          its own fp32 forward (read-only)
+  NeuralQ(ctx, scene, trainer)    the renderer that trains while it renders (rt_neuralq_*);
+                          read_rays() the per-ray arrays of the last frame
   QFit(ctx, trainer, pos, q) / QFit.from_map / QFit.from_file   the reference's NN_Q_Value_Trainer:
                           the network fitted to a radiance map's Q-table (rt_dqn_fit_*), epoch()
                           -> (loss, test error); fit_order(seed, n) its split and shuffle;
@@ -339,6 +342,13 @@ class DqnTrainer:
                                              ctypes.byref(gn) if sync else None, ctypes.c_void_p(stream)))
         return (float(loss.value), float(gn.value)) if sync else None
 
+    def forward_device(self, loc_ptr: int, n: int, q_ptr: int, stream: int = 0) -> None:
+        """Q (n x n_out, device) of n device positions from the current parameters: the fp32
+        forward of the training step and of NeuralQ's frame (rt_dqn_trainer_forward_device);
+        changes nothing in the trainer; asynchronous on `stream`."""
+        check(lib().rt_dqn_trainer_forward_device(self.ctx.handle, self._h, ctypes.c_void_p(loc_ptr), n,
+                                                  ctypes.c_void_p(q_ptr), ctypes.c_void_p(stream)))
+
     def fit_step_device(self, loc_ptr: int, target_ptr: int, n: int, stream: int = 0,
                         sync: bool = True) -> Optional[Tuple[float, float]]:
         """One Adam step of the supervised fit (rt_dqn_fit_step_device): targets n x n_out, the
@@ -417,6 +427,23 @@ class NeuralQ:
         check(lib().rt_neuralq_render_frame(self.ctx.handle, self._h, ctypes.byref(cam), ctypes.byref(params),
                                             _fp(img), _fp(stats), ctypes.byref(casts)))
         return img, stats, int(casts.value)
+
+    RAY_ARRAYS = (("loc", np.float32, 3), ("tp", np.float32, 3), ("total", np.float32, 3), ("tri", np.int32, 1),
+                  ("state", np.uint32, 1), ("bounces", np.uint32, 1), ("action", np.int32, 1),
+                  ("reward", np.float32, 1), ("discount", np.float32, 1), ("terminal", np.int32, 1))
+
+    def read_rays(self) -> dict:
+        """The per-ray arrays as the last frame left them (rt_neuralq_read_rays), by name:
+        loc, tp, total (n, 3); tri, state, bounces, action, reward, discount, terminal (n,).
+        Raises before the first frame."""
+        n = ctypes.c_int32(0)
+        none = [None] * len(self.RAY_ARRAYS)
+        check(lib().rt_neuralq_read_rays(self._h, *none, ctypes.byref(n)))
+        out = {name: np.zeros((n.value, c) if c > 1 else n.value, dt) for name, dt, c in self.RAY_ARRAYS}
+        ptr = {np.float32: ctypes.c_float, np.int32: ctypes.c_int32, np.uint32: ctypes.c_uint32}
+        args = [out[name].ctypes.data_as(ctypes.POINTER(ptr[dt])) for name, dt, _ in self.RAY_ARRAYS]
+        check(lib().rt_neuralq_read_rays(self._h, *args, None))
+        return out
 
     @staticmethod
     def stats_lines(stats) -> str:

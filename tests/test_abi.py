@@ -25,6 +25,20 @@ def test_exports_every_declared_symbol(rtmi_mod):
     assert sorted(rtmi_mod._lib.EXPORTS) == syms
 
 
+def test_read_only_training_entry_points_are_declared_and_refuse_null(rtmi_mod):
+    """rt_dqn_trainer_forward_device and rt_neuralq_read_rays: in the header, in EXPORTS, with
+    argument types, and RT_E_INVALID on NULL handles before anything touches a device."""
+    L = rtmi_mod.lib()
+    for name, n_args in (("rt_dqn_trainer_forward_device", 6), ("rt_neuralq_read_rays", 12)):
+        assert name in header_symbols() and name in rtmi_mod._lib.EXPORTS
+        assert len(getattr(L, name).argtypes) == n_args
+    assert L.rt_dqn_trainer_forward_device(None, None, None, 1, None, None) == -1
+    assert b"NULL" in L.rt_last_error()
+    n = ctypes.c_int32(-7)
+    assert L.rt_neuralq_read_rays(None, *([None] * 10), ctypes.byref(n)) == -1
+    assert b"NULL" in L.rt_last_error() and n.value == -7
+
+
 def test_params_defaults(rtmi_mod):
     p = rtmi_mod.default_params(rtmi_mod.RT_PRESET_CPU)
     assert (p.width, p.height, p.spp, p.max_bounces, p.hit_rule, p.seed) == (512, 512, 16, 2, 0, 1984)
