@@ -307,6 +307,63 @@ int rt_render_dqn_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn*
                                int n_tiles, int tile_size, float* d_out, uint64_t* d_casts,
                                void* stream);
 
+/* The Q-network view: the network's irradiance estimate at every camera hit, the network's
+ * side of the thesis's comparison (Images/neural_q_visualisation.png beside
+ * expected_sarsa_visualisation.png, 4_critical_evaluation.tex); it replaces no reference
+ * interface.  The map's side is rt_render_irradiance.
+ *
+ * Per sample s in [first_sample, first_sample + spp) of every pixel: the camera ray
+ * rt_render_dqn casts for sample index s (k_dqn_camera: jitter draw2(pix, s, 0, seed), pixel
+ * key y * W + x), its closest hit under the GPU hit rule and t_scale, the hit point p being the
+ * one the renderer hands the network at bounce 1.  At a hit on surface `tri`:
+ *   Q[0..143]  the fp32 forward at p, rt_dqn_forward's value bit for bit (not the bf16 copy the
+ *              renderer keeps between forward and sampler);
+ *   c_k = chiu_cos(gx + 0.5f, gy + 0.5f), k = gx * 12 + gy: the cell-centre cosine, in float32
+ *              1 - xx * xx with xx = max(|2 (g / 12) - 1|) over the two coordinates;
+ *   t_k = Q_k * c_k (one rounded multiply, never contracted into the sum);
+ *   B_w = (t_36w + t_36w+1) + .. + t_36w+35, added one after another in k order, w = 0..3;
+ *   S = ((B_0 + B_1) + B_2) + B_3 (sample_from_q's blocking);
+ *   L = (S * brdf[tri]) * ((2 pi) / 144), brdf[tri] the luminance / pi a radiance volume on that
+ *              surface carries, the constant rt_render_irradiance's;
+ *   the sample is (L, L, L), or with tint != 0 albedo * (L / luminance), 0 where the luminance is 0;
+ *   action = the first k of largest t_k: a scan from k = 0 that replaces on >, from -inf, so a
+ *              NaN never wins (0 if no t_k exceeds -inf).
+ * A light gives its emission, a miss params->env_light.  The pixel is
+ * (((v_s0 + v_s0+1) + ..) / (float)spp, folded in sample order whatever number of sample slots
+ * a pass holds.  spp_split, max_bounces and sampler are ignored.
+ *
+ * How to read the number: for a volume whose Q row is q, rt_sarsa_write makes the map's
+ * estimate initial_irradiance(c, q, luminance) * (2 pi / 144); a network that returns q at that
+ * point gives the same value up to the rounding of a 144-term fp32 sum against a double one.
+ * So this view and rt_render_irradiance with k = 1 are on one scale, and their difference
+ * shows where the network departs from the map it was fitted to.
+ *
+ * out_tri / out_pos / out_q / out_action (each may be NULL) describe sample first_sample:
+ * out_tri -1 for a miss and >= n_surf for a light; out_pos and out_q zeros and out_action -1
+ * unless a surface was hit.  The network, the scene and its tables are read only; the call
+ * uses the context's DQN workspace as rt_render_dqn does.  A pixel does not depend on the tile
+ * list, RTMI_DQN_RAYS_IN_FLIGHT, the forward kernel (rt_dqn_set_mlp), the cast route, or the
+ * route of the reduction: inside the streaming forward's epilogue on its LDS tile, or (out_q
+ * requested, RT_DQN_MLP_STATIONARY networks, RTMI_DQN_VIEW_FUSED=0 in the environment, read
+ * per call) k_dqn_view_reduce on the Q the forward wrote.
+ * Refused before any device work: NULL required pointers, an unknown mode, size or spp <= 0
+ * (RT_E_INVALID); another preset or hit rule than the GPU engine's (RT_E_UNSUPPORTED).
+ * n_tiles == 0 is RT_OK. */
+#define RT_DQN_VIEW_IRRADIANCE 0
+typedef struct {
+    int32_t mode; /* RT_DQN_VIEW_IRRADIANCE */
+    int32_t tint; /* != 0: times the surface's albedo / luminance, as rt_irr_opts.tint */
+} rt_dqn_view_opts;
+int rt_render_dqn_view(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam,
+                       const rt_params* params, const rt_dqn_view_opts* opts, uint32_t first_sample,
+                       float* out_rgb /* W x H x 3 */, int32_t* out_tri, float* out_pos /* W x H x 3 */,
+                       float* out_q /* W x H x 144 */, int32_t* out_action /* W x H */);
+int rt_render_dqn_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn,
+                                    const rt_camera* cam, const rt_params* params,
+                                    const rt_dqn_view_opts* opts, uint32_t first_sample,
+                                    const int32_t* tiles, int n_tiles, int tile_size, float* d_out,
+                                    void* stream);
+
 /* ---- Neural-Q training ---------------------------
  * The learning rule of NeuralQPathtracer::render_frame
  * (GPU/deep_learning/neural_q_pathtracer.cu:420-513), which the reference runs through
@@ -851,7 +908,7 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 #define RT_KT_SARSA_RENDER 2  /* k_sarsa_render (config 3) */
 #define RT_KT_SARSA_APPLY 3   /* k_sarsa_apply */
 #define RT_KT_DQN_MLP 4       /* k_dqn_mlp: the Q-network forward (config 4) */
-#define RT_KT_DQN_BOUNCE 5    /* k_dqn_bounce: Q.cos sampling + trace */
+#define RT_KT_DQN_BOUNCE 5    /* k_dqn_bounce: Q.cos sampling + trace; in rt_render_dqn_view, k_dqn_view_reduce */
 #define RT_KT_DQN_CAMERA 6    /* k_dqn_camera */
 #define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view) */
 #define RT_KT_SARSA_NEAREST 8 /* k_sarsa_nearest: rt_sarsa_nearest's queries (without its copies) */

@@ -432,7 +432,61 @@ __device__ __forceinline__ float chiu_cos_cell_w(int a, uint32_t w) {
     return chiu_cos(fmaf((float)(w & 0xffffu), 0x1p-16f, (float)gxi), fmaf((float)(w >> 16), 0x1p-16f, (float)gyi));
 }
 
+// ---------------------------------------------------------------------------
+// The Q-network view's reduction (rt_render_dqn_view, rtmi.h): a ray's 144 Q values to the
+// network's irradiance estimate, in sample_from_q's blocking -- one thread per (ray, block w
+// of kSampCells cells):
+//   t_k = Q_k * c_k, c_k = chiu_cos(gx + 0.5, gy + 0.5) (k = gx * 12 + gy: the cell-centre
+//   cosine), B_w = (t_{36w} + t_{36w+1}) + .. in cell order, and the block's first cell of
+//   largest t_k (replace on >, from -inf: a NaN never wins);
+// view_merge: S = ((B_0 + B_1) + B_2) + B_3 and the first cell of largest t_k over the
+// blocks in order (0 if no t_k exceeds -inf).  ld(k) returns Q_k.
+// ---------------------------------------------------------------------------
+template <class LoadQ>
+__device__ __forceinline__ void view_block(int w, LoadQ ld, float* bsum, float* best, int* act) {
+    float b = 0.0f, bt = -INFINITY;
+    int ba = w * kSampCells;
+#pragma unroll
+    for (int j = 0; j < kSampCells; ++j) {
+        const int k = w * kSampCells + j;
+        const float c = chiu_cos((float)(w * (kSampCells / kDqnGrid) + j / kDqnGrid) + 0.5f,
+                                 (float)(j % kDqnGrid) + 0.5f);
+        const float t = ld(k) * c;
+        b = j == 0 ? t : b + t;
+        if (t > bt) {
+            bt = t;
+            ba = k;
+        }
+    }
+    *bsum = b;
+    *best = bt;
+    *act = ba;
+}
+static_assert(kSampCells % kDqnGrid == 0, "a block is whole grid rows");
+
+// bsum / best / act: the ray's kSampBlocks block results, `stride` apart
+__device__ __forceinline__ void view_merge(const float* bsum, const float* best, const int* act, int stride, float* S,
+                                           int* action) {
+    float s = bsum[0], bt = -INFINITY;
+    int a = 0;
+#pragma unroll
+    for (int w = 0; w < kSampBlocks; ++w) {
+        if (w > 0) s = s + bsum[w * stride];
+        if (best[w * stride] > bt) {
+            bt = best[w * stride];
+            a = act[w * stride];
+        }
+    }
+    *S = s;
+    *action = a;
+}
+
 // One workgroup = MT*16 rays (LDS: MT = 6 in place -> 66 KB, two workgroups per CU).
+// VIEW: instead of writing Q out, the workgroup runs the Q-network view's reduction
+// (view_block / view_merge) on its staged fp32 tile and writes the ray's S and action,
+// q[i] = S, q[ldq + i] = action bits (i the list row): 8 B instead of 576 B per ray.  The
+// block results live in bufA's slack behind the stage; consecutive lanes read consecutive
+// rows at the odd kStageStride, so a 32-lane group's ds_read_b32 hits 32 distinct banks.
 // FUSED: instead of writing Q out, the workgroup runs importance_sample_direction's
 // selection (nn_rendering_helpers.cu:391-489) on its LDS tile in sample_from_q's blocked
 // order, one thread per (ray, block of 36 cells): Q*cos and the block sums, then the total,
@@ -440,7 +494,7 @@ __device__ __forceinline__ float chiu_cos_cell_w(int a, uint32_t w) {
 // writes the chosen cell and its normalised Q*cos per ray (q[i] = action bits,
 // q[ldq + i] = qd), 8 B instead of 576 B of Q per ray; k_dqn_bounce<MF, true> finishes the
 // direction.  Q never leaves the chip.
-template <int MT, bool FUSED = false, bool QB = false>
+template <int MT, bool FUSED = false, bool QB = false, bool VIEW = false>
 #ifndef RT_MLP_MIN_WAVES
 #define RT_MLP_MIN_WAVES 2  // waves per SIMD: the workgroups per CU that its LDS admits (3: MT = 4 in place)
 #endif
@@ -522,6 +576,32 @@ __global__ __launch_bounds__(kMlpThreads, RT_MLP_MIN_WAVES) void k_dqn_mlp(const
     }
 #endif
     __syncthreads();
+    if constexpr (VIEW) {
+        static_assert(!FUSED && !QB, "the view reduces the fp32 stage");
+        // [block][row] behind the stage (no LDS of its own)
+        static_assert(kRows * kStageStride * 4 + 3 * kSampBlocks * kRows * 4 <= kRows * kStrideA * 2,
+                      "the view's block results fit bufA's slack");
+        const float* const stage = reinterpret_cast<const float*>(bufA);
+        float* const bsum = reinterpret_cast<float*>(bufA) + kRows * kStageStride;
+        float* const best = bsum + kSampBlocks * kRows;
+        int* const bact = reinterpret_cast<int*>(best + kSampBlocks * kRows);
+        for (int u = threadIdx.x; u < kSampBlocks * kRows; u += kMlpThreads) {
+            const int w = u / kRows, r = u - w * kRows;  // 32-lane groups share w (kRows = 96)
+            if (r >= rows_valid) continue;
+            const float* const srow = stage + r * kStageStride;
+            view_block(w, [&](int k) { return srow[k]; }, bsum + u, best + u, bact + u);
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < rows_valid) {
+            const int r = threadIdx.x;
+            float S;
+            int action;
+            view_merge(bsum + r, best + r, bact + r, kRows, &S, &action);
+            q[row0 + r] = S;
+            q[(size_t)ldq + row0 + r] = __int_as_float(action);
+        }
+        return;
+    }
     if constexpr (FUSED && kFusedFits) {
         static_assert(kRows == 64 && kMlpThreads == 64 * kSampBlocks, "the fused sampler maps a thread to a block");
         float* const stage = reinterpret_cast<float*>(bufA);  // [row][kStageStride]: Q -> Q*cos
@@ -819,7 +899,7 @@ __device__ __forceinline__ SampleOut sample_from_q(float* __restrict__ q, size_t
 #endif
 template <int MF, bool BOUNCE = false, bool CT = false>
 __device__ __forceinline__ bool dqn_trace(const DqnLaunch& a, f3 pos, f3 dir, bool active, float* wl, f3* loc_out,
-                                          int* tri_out, f3* tp, int surf = -1) {
+                                          int* tri_out, f3* tp, int surf = -1, int* hit_out = nullptr) {
     const f3 o = make3(pos.x + dir.x * kEps, pos.y + dir.y * kEps, pos.z + dir.z * kEps);
     const f3 d = normalize(dir);
     Hit h;
@@ -839,6 +919,7 @@ __device__ __forceinline__ bool dqn_trace(const DqnLaunch& a, f3 pos, f3 dir, bo
         if (!active) return false;
         h = closest_hit_sel<1>(a.scene, a.use_filter, o, d, a.t_scale);
     }
+    if (hit_out != nullptr) *hit_out = h.tri;  // (the view's camera: -1 a miss, >= n_surf a light)
     if (h.tri < 0) {
         *tp = make3(tp->x * a.env_light, tp->y * a.env_light, tp->z * a.env_light);
         return false;
@@ -922,10 +1003,12 @@ __device__ __forceinline__ float* dqn_lane_ws(float* s) {
 }
 
 // initialise_ray + the first trace_ray (bounce 0: no Q evaluation)
+// VIEW (rt_render_dqn_view): every ray's hit is recorded in rays.tri, -1 for a miss and the
+// light's index for a light, not only the surface hits'
 #ifndef RT_MF_DQN_WAVES
 #define RT_MF_DQN_WAVES 4  // occupancy floor of the MF variants
 #endif
-template <int MF>
+template <int MF, bool VIEW = false>
 __global__ __launch_bounds__(256, MF > 0 ? RT_MF_DQN_WAVES : 1) void k_dqn_camera(const DqnLaunch a) {
     __shared__ float s_mfw[dqn_lds_floats(MF)];
     const int rid = blockIdx.x * 256 + threadIdx.x;
@@ -948,13 +1031,15 @@ __global__ __launch_bounds__(256, MF > 0 ? RT_MF_DQN_WAVES : 1) void k_dqn_camer
         }
     }
     f3 loc;
-    int tri = 0;
+    int tri = 0, hit = -1;
     keep = dqn_trace<MF>(a, make3(a.cam_x, a.cam_y, a.cam_z), d, valid, dqn_lane_ws<MF>(s_mfw),
-                         &loc, &tri, &tp);
+                         &loc, &tri, &tp, -1, VIEW ? &hit : nullptr);
     if (rid < a.rays.n) {
         if (keep) {
             st3(a.rays.loc, rid, loc);
             a.rays.tri[rid] = tri;
+        } else if (VIEW) {
+            a.rays.tri[rid] = hit;
         }
         st3(a.rays.tp, rid, tp);
     }
@@ -1051,6 +1136,89 @@ __global__ __launch_bounds__(256) void k_dqn_finish(const DqnLaunch a) {
     dst[0] = t.x / fs;
     dst[1] = t.y / fs;
     dst[2] = t.z / fs;
+}
+
+// ---------------------------------------------------------------------------
+// The Q-network view (rt_render_dqn_view): per pass k_dqn_camera<MF, true>, the forward over
+// list[0], the reduction to (S, action) per list row -- k_dqn_mlp<MT, .., VIEW> on its LDS
+// tile, or k_dqn_view_reduce on the Q the forward wrote -- and k_dqn_view_shade, which turns
+// S into the sample's value in rays.tp (lights and misses already hold theirs: the camera's
+// throughput is 1 * emission and 1 * env_light).  va: rays.dir, free in this driver:
+// va[i] = S, va[rays.n + i] = action bits.
+// ---------------------------------------------------------------------------
+constexpr float kViewIrrScale = (2.f * kPi) / ((float)(kGridRes * kGridRes));  // rt_render_irradiance's kIrrScale
+constexpr int kViewRays = 256 / kSampBlocks;  // rays per k_dqn_view_reduce workgroup
+
+// the unfused route: one thread per (list row, block of 36 cells) on the action-major fp32 Q
+__global__ __launch_bounds__(256) void k_dqn_view_reduce(const DqnLaunch a) {
+    __shared__ float s_sum[kSampBlocks * kViewRays], s_best[kSampBlocks * kViewRays];
+    __shared__ int s_act[kSampBlocks * kViewRays];
+    const int n_act = a.rays.count[0];
+    if ((int)(blockIdx.x * kViewRays) >= n_act) return;  // uniform
+    const int r = threadIdx.x & (kViewRays - 1), w = threadIdx.x / kViewRays;
+    const int i = blockIdx.x * kViewRays + r;
+    if (i < n_act) {
+        const float* const qi = a.rays.q + i;
+        const size_t ldq = (size_t)a.rays.ldq;
+        view_block(w, [&](int k) { return qi[(size_t)k * ldq]; }, s_sum + threadIdx.x, s_best + threadIdx.x,
+                   s_act + threadIdx.x);
+    }
+    __syncthreads();
+    if (w == 0 && i < n_act) {
+        float S;
+        int action;
+        view_merge(s_sum + r, s_best + r, s_act + r, kViewRays, &S, &action);
+        a.rays.dir[i] = S;
+        a.rays.dir[(size_t)a.rays.n + i] = __int_as_float(action);
+    }
+}
+
+// L = (S * brdf[tri]) * kIrrScale into rays.tp, grey or tinted as k_sarsa_irr; on the pass that
+// holds the view's first sample (v.first), slot 0's action and Q row into the pixel AOVs
+__global__ __launch_bounds__(256) void k_dqn_view_shade(const DqnLaunch a, const DqnView v) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.rays.count[0]) return;
+    const int rid = a.rays.list[0][i];
+    const int tri = a.rays.tri[rid];
+    const float S = a.rays.dir[i];
+    const int action = __float_as_int(a.rays.dir[(size_t)a.rays.n + i]);
+    const float2 sf = v.surf[tri];  // {luminance / pi, luminance}
+    const float L = (S * sf.x) * kViewIrrScale;
+    f3 c = make3(L, L, L);
+    if (v.tint) {
+        const float4 alb = a.scene.shade[tri * kShadeF4 + 4];
+        const float g = L / sf.y;
+        c = sf.y == 0.0f ? make3(0.f, 0.f, 0.f) : make3(alb.x * g, alb.y * g, alb.z * g);
+    }
+    st3(a.rays.tp, rid, c);
+    if (v.first && rid < a.rays.n_pix && (v.out_action != nullptr || v.out_q != nullptr)) {
+        const BlockDesc blk = a.blocks[rid >> 8];  // (a listed ray's pixel is inside the image)
+        const int q = rid & 255;
+        const size_t op = (size_t)(blk.oy0 + (q >> 4)) * (size_t)a.out_pitch + (size_t)(blk.ox0 + (q & 15));
+        if (v.out_action != nullptr) v.out_action[op] = action;
+        if (v.out_q != nullptr)
+            for (int k = 0; k < kDqnActions; ++k) v.out_q[op * kDqnActions + k] = a.rays.q[(size_t)k * a.rays.ldq + i];
+    }
+}
+
+// slot 0's hit into the pixel AOVs (the pass that holds the view's first sample)
+__global__ __launch_bounds__(256) void k_dqn_view_aov(const DqnLaunch a, const DqnView v) {
+    const int rid = blockIdx.x * 256 + threadIdx.x;  // pixel slot
+    if (rid >= a.rays.n_pix) return;
+    int px, py;
+    if (!ray_pixel(a, rid, &px, &py)) return;
+    const BlockDesc blk = a.blocks[rid >> 8];
+    const int q = rid & 255;
+    const size_t op = (size_t)(blk.oy0 + (q >> 4)) * (size_t)a.out_pitch + (size_t)(blk.ox0 + (q & 15));
+    const int tri = a.rays.tri[rid];
+    const bool surf = tri >= 0 && tri < a.scene.n_surf;
+    if (v.out_tri != nullptr) v.out_tri[op] = tri;
+    if (v.out_pos != nullptr) {
+        const f3 p = surf ? ld3(a.rays.loc, rid) : make3(0.f, 0.f, 0.f);
+        v.out_pos[3 * op + 0] = p.x;
+        v.out_pos[3 * op + 1] = p.y;
+        v.out_pos[3 * op + 2] = p.z;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_dqn_sample_only(const DeviceScene s, float* q, const float* loc,
@@ -1421,6 +1589,53 @@ hipError_t launch_dqn_accumulate(const DqnLaunch& a, hipStream_t stream) {
 hipError_t launch_dqn_finish(const DqnLaunch& a, hipStream_t stream) {
     hipLaunchKernelGGL(k_dqn_finish, dim3(pix_blocks(a)), dim3(256), 0, stream, a);
     return hipGetLastError();
+}
+
+hipError_t launch_dqn_view_camera(const DqnLaunch& a, hipStream_t stream) {
+    KernelTimer kt(KT_DQN_CAMERA, stream);
+    switch (dqn_mf(a)) {
+        case 1: hipLaunchKernelGGL((k_dqn_camera<1, true>), dim3(ray_blocks(a)), dim3(256), 0, stream, a); break;
+        case 4: hipLaunchKernelGGL((k_dqn_camera<4, true>), dim3(ray_blocks(a)), dim3(256), 0, stream, a); break;
+        case -1: hipLaunchKernelGGL((k_dqn_camera<-1, true>), dim3(ray_blocks(a)), dim3(256), 0, stream, a); break;
+        default: hipLaunchKernelGGL((k_dqn_camera<0, true>), dim3(ray_blocks(a)), dim3(256), 0, stream, a); break;
+    }
+    return hipGetLastError();
+}
+
+// the fused reduction lives in this file's streaming kernel (the weight-stationary one writes Q)
+bool dqn_view_can_fuse(const DqnNet& net) { return !(net.mlp_mode == kMlpStationary && dqn_mlp_ws_fits(net)); }
+
+// the reduction is timed as KT_DQN_BOUNCE, the family of the kernel that consumes Q (the view
+// runs no bounce); the fused route's is inside KT_DQN_MLP
+hipError_t launch_dqn_view_pass(const DqnLaunch& a, const DqnView& v, bool fused, hipStream_t stream) {
+    if (a.rays.n <= 0) return hipSuccess;
+    if (v.surf == nullptr || a.net.N[3] != kDqnActions) return hipErrorInvalidValue;
+    if (fused) {
+        if (!dqn_view_can_fuse(a.net) || v.out_q != nullptr) return hipErrorInvalidValue;
+        KernelTimer kt(KT_DQN_MLP, stream);
+        const int blocks = (a.rays.n + kTileM - 1) / kTileM;
+        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, false, false, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0,
+                           stream, a.net, a.rays.loc, a.rays.list[0], a.rays.count + 0, a.rays.n, a.rays.dir, a.rays.n,
+                           MlpSample());
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else {
+        hipError_t e = launch_dqn_mlp(a.net, a.rays.loc, a.rays.list[0], a.rays.count + 0, a.rays.n, a.rays.q,
+                                      a.rays.ldq, stream);
+        if (e != hipSuccess) return e;
+        KernelTimer kt(KT_DQN_BOUNCE, stream);
+        hipLaunchKernelGGL(k_dqn_view_reduce, dim3((unsigned)((a.rays.n + kViewRays - 1) / kViewRays)), dim3(256), 0,
+                           stream, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_dqn_view_shade, dim3(ray_blocks(a)), dim3(256), 0, stream, a, v);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && v.first && (v.out_tri != nullptr || v.out_pos != nullptr)) {
+        hipLaunchKernelGGL(k_dqn_view_aov, dim3(pix_blocks(a)), dim3(256), 0, stream, a, v);
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 hipError_t launch_dqn_sample_only(const DeviceScene& s, const float* q, const float* loc, const int32_t* tri,

@@ -28,6 +28,7 @@ int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wante
 bool ctab_wanted(const rt_scene* sc, const rt_camera* cam, const rt_params* p, int user);
 int ctx_blocks(rt_ctx* ctx, const int32_t* tiles, int n_tiles, int tile_size, int width, int height,
                const BlockDesc** d_blocks, int* n_blocks);
+void surface_brdf_table(const rt_scene* scene, std::vector<float>* out);  // rt_sarsa_host.cpp
 }  // namespace rt
 
 namespace {
@@ -373,12 +374,19 @@ struct Workspace {
     std::vector<void*> allocs;
     int cap = 0;
     int device = 0;
+    // the Q-network view's per-surface table {luminance / pi, luminance} (uploaded per call)
+    std::vector<float> surf_host;
+    float2* surf = nullptr;
+    int surf_cap = 0;
     void release() {
         for (void* p : allocs) (void)hipFree(p);
         allocs.clear();
         cap = 0;
     }
-    ~Workspace() { release(); }
+    ~Workspace() {
+        release();
+        if (surf) (void)hipFree(surf);
+    }
     int ensure(int n) {
         if (n <= cap) {
             r.n = n;
@@ -491,9 +499,170 @@ int check_dqn_params(const rt_params* p) {
     return RT_OK;
 }
 
+// rt_render_dqn_view's parameters: check_dqn_params without the max_bounces check (camera rays only)
+int check_dqn_view_params(const rt_params* p, const rt_dqn_view_opts* o) {
+    if (!p || !o) return err(RT_E_INVALID, "NULL argument");
+    if (o->mode != RT_DQN_VIEW_IRRADIANCE) return err(RT_E_INVALID, "bad view mode");
+    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return err(RT_E_INVALID, "bad image size / spp");
+    if (p->preset != RT_PRESET_GPU || p->hit_rule != RT_HIT_RULE_GPU)
+        return err(RT_E_UNSUPPORTED, "the Q-network view implements the GPU-engine preset (hit rule GPU)");
+    return RT_OK;
+}
+
+#ifndef RT_DQN_VIEW_FUSED
+// the view's default route: 1 = the reduction inside k_dqn_mlp (DESIGN.md section 7 holds the A/B)
+#define RT_DQN_VIEW_FUSED 1
+#endif
+
+// The Q-network view: run_dqn's workspace, frame begin and passes over sample slots; a pass is
+// the camera, the forward over list[0], the reduction and the accumulation -- no bounce loop,
+// no host synchronisation.  aov: the per-pixel outputs of sample first_sample (each optional).
+int run_dqn_view(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam, const rt_params* p,
+                 const rt_dqn_view_opts* opts, uint32_t first_sample, const rt::BlockDesc* d_blocks, int n_blocks,
+                 int clip_x1, int clip_y1, int out_pitch, float* d_out, const rt::DqnView& aov, hipStream_t stream) {
+    Workspace* ws = g_ws_for(ctx);
+    const int n_pix = n_blocks * 256;
+    int rays_in_flight = kRaysInFlight;
+    if (const char* env = getenv("RTMI_DQN_RAYS_IN_FLIGHT")) rays_in_flight = std::max(1, atoi(env));  // tests
+    const int in_flight = std::max(1, std::min(p->spp, rays_in_flight / n_pix));
+    int rc = ws->ensure(n_pix * in_flight);
+    if (rc != RT_OK) return rc;
+    rt::DqnLaunch a;
+    memset(&a, 0, sizeof(a));
+    a.scene = rt::scene_launch_view(scene);
+    a.net = dqn->net;
+    a.rays = ws->r;
+    RT_HIPE(hipMemsetAsync(a.rays.casts, 0, sizeof(unsigned long long), stream));
+    a.width = p->width;
+    a.height = p->height;
+    a.spp = p->spp;
+    a.max_bounces = 1;
+    a.seed_lo = (uint32_t)p->seed;
+    a.seed_hi = (uint32_t)(p->seed >> 32);
+    a.t_scale = p->t_scale;
+    a.env_light = p->env_light;
+    a.cam_x = cam->pos[0];
+    a.cam_y = cam->pos[1];
+    a.cam_z = cam->pos[2];
+    a.cos_y = (float)cos((double)cam->yaw_y);
+    a.sin_y = (float)sin((double)cam->yaw_y);
+    a.cos_x = (float)cos((double)cam->yaw_x);
+    a.sin_x = (float)sin((double)cam->yaw_x);
+    a.blocks = d_blocks;
+    a.n_blocks = n_blocks;
+    a.clip_x1 = clip_x1;
+    a.clip_y1 = clip_y1;
+    a.out_pitch = out_pitch;
+    a.out = d_out;
+    a.use_filter = rt::filter_usable(a.scene, a.cam_x, a.cam_y, a.cam_z, a.t_scale);
+    // the per-surface table, by the host code of a radiance volume's vol_brdf
+    rt::surface_brdf_table(scene, &ws->surf_host);
+    const int n_surf = (int)(ws->surf_host.size() / 2);
+    if (n_surf > ws->surf_cap) {
+        if (ws->surf) (void)hipFree(ws->surf);
+        ws->surf = nullptr;
+        ws->surf_cap = 0;
+        RT_HIPE(hipMalloc((void**)&ws->surf, sizeof(float2) * (size_t)n_surf));
+        ws->surf_cap = n_surf;
+    }
+    if (n_surf > 0)
+        RT_HIPE(hipMemcpyAsync(ws->surf, ws->surf_host.data(), sizeof(float2) * (size_t)n_surf, hipMemcpyHostToDevice,
+                               stream));
+    rt::DqnView v = aov;
+    v.surf = ws->surf;
+    v.tint = opts->tint != 0;
+    // the route: the fused reduction unless asked otherwise (RTMI_DQN_VIEW_FUSED, read per call:
+    // tests and the A/B), the Q rows are wanted, or the network is pinned to the stationary kernel
+    bool fused = RT_DQN_VIEW_FUSED != 0;
+    if (const char* env = getenv("RTMI_DQN_VIEW_FUSED")) fused = atoi(env) != 0;
+    fused = fused && v.out_q == nullptr && rt::dqn_view_can_fuse(a.net);
+    a.rays.n_pix = n_pix;
+    a.rays.n = n_pix;
+    hipError_t e = rt::launch_dqn_frame_begin(a, stream);
+    for (int s = 0; e == hipSuccess && s < p->spp; s += in_flight) {
+        a.rays.s0 = (int)(first_sample + (uint32_t)s);
+        a.rays.n = n_pix * std::min(in_flight, p->spp - s);
+        v.first = s == 0;
+        e = hipMemsetAsync(a.rays.count, 0, sizeof(int32_t) * 2, stream);
+        if (e == hipSuccess) e = rt::launch_dqn_view_camera(a, stream);
+        if (e == hipSuccess) e = rt::launch_dqn_view_pass(a, v, fused, stream);
+        if (e == hipSuccess) e = rt::launch_dqn_accumulate(a, stream);
+    }
+    if (e == hipSuccess) e = rt::launch_dqn_finish(a, stream);
+    if (e != hipSuccess) return err(RT_E_HIP, std::string("DQN view: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rt_render_dqn_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam,
+                                    const rt_params* params, const rt_dqn_view_opts* opts, uint32_t first_sample,
+                                    const int32_t* tiles, int n_tiles, int tile_size, float* d_out, void* stream) {
+    if (!ctx || !scene || !dqn || !cam) return err(RT_E_INVALID, "NULL argument");
+    int rc = check_dqn_view_params(params, opts);
+    if (rc != RT_OK) return rc;
+    if (n_tiles == 0) return RT_OK;
+    if (!tiles || !d_out || n_tiles < 0) return err(RT_E_INVALID, "bad tiles/out");
+    RT_HIPE(hipSetDevice(rt::ctx_device(ctx)));
+    const rt::BlockDesc* d_blocks = nullptr;
+    int n_blocks = 0;
+    rc = rt::ctx_blocks(ctx, tiles, n_tiles, tile_size, params->width, params->height, &d_blocks, &n_blocks);
+    if (rc != RT_OK) return rc;
+    return run_dqn_view(ctx, scene, dqn, cam, params, opts, first_sample, d_blocks, n_blocks, params->width,
+                        params->height, tile_size, d_out, rt::DqnView(), (hipStream_t)stream);
+}
+
+int rt_render_dqn_view(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam,
+                       const rt_params* params, const rt_dqn_view_opts* opts, uint32_t first_sample, float* out_rgb,
+                       int32_t* out_tri, float* out_pos, float* out_q, int32_t* out_action) {
+    if (!ctx || !scene || !dqn || !cam || !out_rgb) return err(RT_E_INVALID, "NULL argument");
+    int rc = check_dqn_view_params(params, opts);
+    if (rc != RT_OK) return rc;
+    RT_HIPE(hipSetDevice(rt::ctx_device(ctx)));
+    const int w = params->width, h = params->height;
+    std::vector<rt::BlockDesc> blocks;
+    for (int by = 0; by < h; by += 16)
+        for (int bx = 0; bx < w; bx += 16) blocks.push_back({bx, by, bx, by});
+    const size_t np = (size_t)w * h;
+    rt::BlockDesc* d_blocks = nullptr;
+    float* d_out = nullptr;
+    rt::DqnView aov;
+    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
+    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
+    if (e == hipSuccess && out_tri) e = hipMalloc(&aov.out_tri, sizeof(int32_t) * np);
+    if (e == hipSuccess && out_pos) e = hipMalloc(&aov.out_pos, sizeof(float) * 3 * np);
+    if (e == hipSuccess && out_q) e = hipMalloc(&aov.out_q, sizeof(float) * rt::kDqnActions * np);
+    if (e == hipSuccess && out_action) e = hipMalloc(&aov.out_action, sizeof(int32_t) * np);
+    // pixels without a surface hit: Q zeros, action -1 (the kernels write the surface pixels)
+    if (e == hipSuccess && out_q) e = hipMemset(aov.out_q, 0, sizeof(float) * rt::kDqnActions * np);
+    if (e == hipSuccess && out_action) e = hipMemset(aov.out_action, 0xff, sizeof(int32_t) * np);
+    if (e == hipSuccess)
+        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = run_dqn_view(ctx, scene, dqn, cam, params, opts, first_sample, d_blocks, (int)blocks.size(), w, h, w,
+                          d_out, aov, 0);
+        if (rc == RT_OK) e = hipDeviceSynchronize();
+    }
+    const bool ok = rc == RT_OK;
+    if (ok && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
+    if (ok && e == hipSuccess && out_tri) e = hipMemcpy(out_tri, aov.out_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
+    if (ok && e == hipSuccess && out_pos) e = hipMemcpy(out_pos, aov.out_pos, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
+    if (ok && e == hipSuccess && out_q)
+        e = hipMemcpy(out_q, aov.out_q, sizeof(float) * rt::kDqnActions * np, hipMemcpyDeviceToHost);
+    if (ok && e == hipSuccess && out_action)
+        e = hipMemcpy(out_action, aov.out_action, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
+    (void)hipFree(d_blocks);
+    (void)hipFree(d_out);
+    (void)hipFree(aov.out_tri);
+    (void)hipFree(aov.out_pos);
+    (void)hipFree(aov.out_q);
+    (void)hipFree(aov.out_action);
+    if (rc != RT_OK) return rc;
+    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_dqn_view: ") + hipGetErrorString(e));
+    return RT_OK;
+}
 
 int rt_render_dqn_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam,
                                const rt_params* params, const int32_t* tiles, int n_tiles, int tile_size,

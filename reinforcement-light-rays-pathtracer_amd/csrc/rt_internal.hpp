@@ -327,6 +327,23 @@ struct DqnLaunch {
     int use_filter;  // as RenderLaunch::use_filter
 };
 
+// The Q-network view (rt_render_dqn_view): what its kernels need beside a DqnLaunch
+struct DqnView {
+    const float2* surf = nullptr;   // [n_surf] {luminance / pi (a volume's vol_brdf), luminance}
+    int tint = 0;
+    int first = 0;                  // the pass holds the view's first sample in slot 0: the AOVs are written
+    int32_t* out_tri = nullptr;     // per-pixel AOVs in DqnLaunch::out's layout, each optional
+    float* out_pos = nullptr;
+    float* out_q = nullptr;         // (the unfused route only: the Q rows are in rays.q)
+    int32_t* out_action = nullptr;
+};
+// k_dqn_camera<MF, true>: as launch_dqn_camera, every ray's hit recorded in rays.tri
+hipError_t launch_dqn_view_camera(const DqnLaunch& a, hipStream_t stream);
+// forward over list[0], reduction (fused: in k_dqn_mlp's epilogue; else k_dqn_view_reduce on rays.q), shading
+// into rays.tp, and on v.first the AOVs; dqn_view_can_fuse: the network takes the streaming kernel
+bool dqn_view_can_fuse(const DqnNet& net);
+hipError_t launch_dqn_view_pass(const DqnLaunch& a, const DqnView& v, bool fused, hipStream_t stream);
+
 // Neural-Q training renderer (GPU/deep_learning/neural_q_pathtracer.cu:226-600): one ray
 // per pixel (id = y * width + x) through all bounces of a sample, in the reference's
 // per-ray arrays (SoA, device).

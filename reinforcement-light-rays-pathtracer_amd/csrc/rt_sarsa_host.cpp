@@ -99,6 +99,26 @@ float luminance(const float* rgb) {
     return 0.5f * (mx + mn);
 }
 
+}  // namespace
+
+namespace rt {
+// {luminance / pi, luminance} per surface: the vol_brdf a radiance volume on that surface
+// carries (rt_sarsa_create below) and its luminance, for the Q-network view (rt_dqn_host.cpp)
+void surface_brdf_table(const rt_scene* scene, std::vector<float>* out) {
+    const float *tri, *normals, *albedo, *emission;
+    int n_surf = 0, n_light = 0;
+    scene_host(scene, &tri, &normals, &albedo, &emission, &n_surf, &n_light);
+    out->resize((size_t)2 * n_surf);
+    for (int j = 0; j < n_surf; ++j) {
+        const float lum = luminance(albedo + 3 * j);
+        (*out)[2 * j] = lum / kPi;
+        (*out)[2 * j + 1] = lum;
+    }
+}
+}  // namespace rt
+
+namespace {
+
 struct Tree {
     const std::vector<float>* pos;  // [n][4]
     std::vector<rt::KdNode> nodes;

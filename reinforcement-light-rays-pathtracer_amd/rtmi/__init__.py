@@ -8,7 +8,8 @@ from ._lib import (LIB_PATH, RT_HIT_NONE, RT_HIT_RULE_CPU, RT_HIT_RULE_GPU, RT_H
                    RT_HIT_TYPE_SURFACE, RT_PRESET_CPU, RT_PRESET_GPU, RT_SAMPLER_COSINE,
                    RT_SAMPLER_UNIFORM, RT_KT_RENDER_PS, RT_KT_RENDER, RT_KT_SARSA_RENDER, RT_KT_SARSA_APPLY,
                    RT_KT_DQN_MLP, RT_KT_DQN_BOUNCE, RT_KT_DQN_CAMERA, RT_KT_SARSA_VIEW, RT_KT_SARSA_NEAREST, RT_KT_PROBE, RT_KT_BAKE, RT_KT_COUNT, RtCamera, RtError,
-                   RtParams, RtIrrOpts, RT_SARSA_KNN_MAX, RT_IRR_MEAN, RT_IRR_CONE, check, lib)
+                   RtParams, RtIrrOpts, RT_SARSA_KNN_MAX, RT_IRR_MEAN, RT_IRR_CONE, RtDqnViewOpts,
+                   RT_DQN_VIEW_IRRADIANCE, check, lib)
 from .api import (CAMERAS, OBJ_KINDS, Context, Geometry, Scene, camera, cornell_geometry,
                   default_params, filter_records, intersect, intersect_device, intersect_method, intersect_cand,
                   CAND_TABLE, CAND_GIVEN, CAND_CAP_TABLE, CAND_CAP_SHARED, ISECT_SCAN,
@@ -27,6 +28,6 @@ __all__ = [
     "dist", "dqn", "metrics", "probe", "sarsa", "tiles", "check", "ktime_enable", "ktime_read", "ktime_name",
     "RT_KT_RENDER_PS", "RT_KT_RENDER", "RT_KT_SARSA_RENDER", "RT_KT_SARSA_APPLY", "RT_KT_DQN_MLP",
     "RT_KT_DQN_BOUNCE", "RT_KT_DQN_CAMERA", "RT_KT_SARSA_VIEW", "RT_KT_SARSA_NEAREST", "RT_KT_PROBE", "RT_KT_BAKE", "RT_KT_COUNT",
-    "RtIrrOpts", "RT_SARSA_KNN_MAX", "RT_IRR_MEAN", "RT_IRR_CONE",
+    "RtIrrOpts", "RT_SARSA_KNN_MAX", "RT_IRR_MEAN", "RT_IRR_CONE", "RtDqnViewOpts", "RT_DQN_VIEW_IRRADIANCE",
     "intersect_cand", "CAND_TABLE", "CAND_GIVEN", "CAND_CAP_TABLE", "CAND_CAP_SHARED",
 ]

@@ -48,6 +48,7 @@ RT_KT_COUNT = 11
 RT_SARSA_KNN_MAX = 8
 RT_IRR_MEAN = 0
 RT_IRR_CONE = 1
+RT_DQN_VIEW_IRRADIANCE = 0
 
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -59,7 +60,7 @@ EXPORTS = (
     "rt_ctab_candidates",
     "rt_dynet_read", "rt_dynet_write", "rt_dqn_create", "rt_dqn_destroy", "rt_dqn_set_mlp", "rt_dqn_mlp_rows", "rt_dqn_forward", "rt_dqn_forward_device",
     "rt_dqn_sample",
-    "rt_render_dqn", "rt_render_dqn_tiles_device",
+    "rt_render_dqn", "rt_render_dqn_tiles_device", "rt_render_dqn_view", "rt_render_dqn_view_tiles_device",
     "rt_sarsa_create", "rt_sarsa_create_density", "rt_sarsa_destroy", "rt_sarsa_info", "rt_sarsa_volumes", "rt_sarsa_read",
     "rt_sarsa_nearest", "rt_render_sarsa", "rt_render_sarsa_tiles_device", "rt_sarsa_td_device",
     "rt_sarsa_apply", "rt_sarsa_set_search", "rt_sarsa_search_stats", "rt_sarsa_save_q",
@@ -102,6 +103,10 @@ class RtParams(ctypes.Structure):
 class RtIrrOpts(ctypes.Structure):
     _fields_ = [("k", ctypes.c_int32), ("radius", ctypes.c_float), ("weight", ctypes.c_int32),
                 ("tint", ctypes.c_int32)]
+
+
+class RtDqnViewOpts(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int32), ("tint", ctypes.c_int32)]
 
 
 class RtError(RuntimeError):
@@ -180,6 +185,10 @@ def _declare(lib):
                               i, i, _FP, _U64P]),
         "rt_render_dqn_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera),
                                            ctypes.POINTER(RtParams), _IP, i, i, _P, _P, _P]),
+        "rt_render_dqn_view": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                   ctypes.POINTER(RtDqnViewOpts), ctypes.c_uint32, _FP, _IP, _FP, _FP, _IP]),
+        "rt_render_dqn_view_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                                ctypes.POINTER(RtDqnViewOpts), ctypes.c_uint32, _IP, i, i, _P, _P]),
         "rt_sarsa_create": (i, [_P, _P, ctypes.c_uint64, ctypes.POINTER(_P)]),
         "rt_sarsa_create_density": (i, [_P, _P, ctypes.c_uint64, ctypes.c_float, ctypes.POINTER(_P)]),
         "rt_sarsa_destroy": (i, [_P]),

@@ -9,6 +9,8 @@
                           forward is exact, so the device's Q can be pinned bit for bit
   Dqn(ctx, nn_vertices, weights)   device network (rt_dqn_create)
   forward / sample / render / render_tiles_device
+  render_view / render_view_tiles_device   the Q-network view (rt_render_dqn_view): the network's
+                          irradiance estimate at every camera hit, on rt_render_irradiance's scale
   DqnTrainer(ctx, nn_vertices, weights)   Neural-Q training (rt_dqn_trainer_*): TD targets,
                           one Adam step per batch, parameters out for a new Dqn; forward_device
                           its own fp32 forward (read-only)
@@ -27,7 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import RT_DQN_VIEW_IRRADIANCE, RtDqnViewOpts, check, lib
 from .api import Context, Scene, _fp, _ip
 
 HIDDEN = (200, 300, 200)  # NN_Builders/dq_network.cu:14-17
@@ -292,6 +294,49 @@ def render_tiles_device(ctx: Context, scene: Scene, dqn: Dqn, cam, params, tiles
                                            ctypes.byref(params), _ip(t), t.shape[0], tile_size,
                                            ctypes.c_void_p(out_ptr), ctypes.c_void_p(casts_ptr),
                                            ctypes.c_void_p(stream)))
+
+
+VIEW_OUTPUTS = ("tri", "pos", "q", "action")
+
+
+def render_view(ctx: Context, scene: Scene, dqn: Dqn, cam, params, tint: bool = False, first_sample: int = 0,
+                outputs: Sequence[str] = (), mode: int = RT_DQN_VIEW_IRRADIANCE):
+    """The Q-network view (rt_render_dqn_view): per camera hit the network's irradiance estimate
+    L = (sum_k Q_k c_k) * luminance / pi * (2 pi / 144) on the cell-centre cosines c_k -- the scale
+    of RadianceMap.irradiance_view(k=1) -- grey, or (tint) times albedo / luminance; a light gives
+    its emission, a miss env_light.  Returns the image (H, W, 3), or (image, aov) when `outputs`
+    names any of VIEW_OUTPUTS: aov["tri"] (H, W) -1 miss / >= n_surf light, aov["pos"] (H, W, 3),
+    aov["q"] (H, W, 144) the fp32 forward at the hit point, aov["action"] (H, W) the first cell of
+    largest Q_k c_k (-1 without a surface hit), all of sample first_sample."""
+    unknown = set(outputs) - set(VIEW_OUTPUTS)
+    if unknown:
+        raise ValueError(f"unknown view outputs {sorted(unknown)}; choose from {VIEW_OUTPUTS}")
+    h, w = params.height, params.width
+    out = np.zeros((h, w, 3), np.float32)
+    shapes = {"tri": ((h, w), np.int32), "pos": ((h, w, 3), np.float32), "q": ((h, w, ACTIONS), np.float32),
+              "action": ((h, w), np.int32)}
+    aov = {k: np.zeros(*shapes[k]) for k in VIEW_OUTPUTS if k in outputs}
+    opts = RtDqnViewOpts(int(mode), int(bool(tint)))
+    check(lib().rt_render_dqn_view(ctx.handle, scene.handle, dqn.handle, ctypes.byref(cam), ctypes.byref(params),
+                                   ctypes.byref(opts), int(first_sample), _fp(out),
+                                   _ip(aov["tri"]) if "tri" in aov else None,
+                                   _fp(aov["pos"]) if "pos" in aov else None,
+                                   _fp(aov["q"]) if "q" in aov else None,
+                                   _ip(aov["action"]) if "action" in aov else None))
+    return (out, aov) if outputs else out
+
+
+def render_view_tiles_device(ctx: Context, scene: Scene, dqn: Dqn, cam, params, tiles: np.ndarray, tile_size: int,
+                             out_ptr: int, stream: int, tint: bool = False, first_sample: int = 0,
+                             mode: int = RT_DQN_VIEW_IRRADIANCE) -> None:
+    """render_view over a tile list into device memory, stream-ordered; tiles and output layout
+    as render_tiles_device (rt_render_dqn_view_tiles_device)."""
+    t = np.ascontiguousarray(tiles, np.int32).reshape(-1, 2)
+    opts = RtDqnViewOpts(int(mode), int(bool(tint)))
+    check(lib().rt_render_dqn_view_tiles_device(ctx.handle, scene.handle, dqn.handle, ctypes.byref(cam),
+                                                ctypes.byref(params), ctypes.byref(opts), int(first_sample),
+                                                _ip(t), t.shape[0], tile_size, ctypes.c_void_p(out_ptr),
+                                                ctypes.c_void_p(stream)))
 
 
 class DqnTrainer:
