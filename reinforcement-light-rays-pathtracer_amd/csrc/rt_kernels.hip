@@ -613,6 +613,14 @@ __host__ __device__ constexpr int ps_wave_floats(int pc, bool narrow) {
 // [N.xyz, F.x] [T.xyz, F.y] [B.xyz, F.z] -- the frame, and in the w lanes the one colour a fold
 // reads there: a surface's fold row for the kernel's sampler, a light's emission
 constexpr int kPsFrameF4 = 3;
+#ifndef RT_PS_PASS_MIN
+// pending samples at which a trip of the table-route variant's pipelined loop runs a pre-test
+// pass (ps_body; 1: in every trip that has any)
+#define RT_PS_PASS_MIN 64
+#endif
+constexpr int kPsPassMin = RT_PS_PASS_MIN;
+// (a trip adds at most 64 samples to fewer than kPsPassMin left pending: under 128, two registers)
+static_assert(kPsPassMin >= 1 && kPsPassMin <= 64, "the pending list holds what a trip can leave pending");
 static_assert(ps_wave_floats(4, true) == 896, "the narrow wave block at 4 samples per lane");
 static_assert(ps_wave_floats(3, true) % 64 == 0 && ps_wave_floats(1, true) % 64 == 0, "wave blocks are 256-byte multiples");
 
@@ -1086,6 +1094,10 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     };
 #if RT_PROF
     uint64_t t_pre = 0;  // wave cycles inside the light pre-test
+    // wave-uniform: the pipelined loop's pre-test passes run inside the loop and after it, and the
+    // pending lanes over those passes
+    unsigned pp_loop = 0, pp_drain = 0, pp_lanes = 0;
+    bool pp_in_loop = true;
 #endif
     bool piped = false;  // the pipelined loop has done the bounces: the loop after it does not run
     // The pipelined loop (the table-route variant with the pre-test on: every live lane ends its
@@ -1094,32 +1106,48 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
     // after it runs only with the pre-test off.  The cast's table lookup opens with two dependent
     // global loads that nothing in the lane's own chain covers, and the pre-test that follows a
     // surface hit shares no data with the lane's next sample.  So a sample whose cast hit a surface does not run its pre-test on
-    // the spot: the lane keeps it as pending (the hit point, and the slot's entry packed with
-    // the two triangles) and goes free.  Next trip: claim, shade the new sample, issue its lookup
-    // (closest_hit_ctab_begin), then run the pending sample's pre-test -- its keys re-derived
-    // from the entry as claim() derives them -- settle the passes, store its value, and only then
-    // use the lookup's words (closest_hit_ctab_finish).  Loads return in the order of their
+    // the spot: the lane parks it as pending and goes free.  The hit point goes into the sample's
+    // own slot (its three floats are dead between the claim and the final value), and the sample
+    // (its entry packed with the two triangles) joins the wave's pending list at a position from
+    // one ballot, as the queue is built.  The list lives in two registers of the wave, entry j of
+    // its up to 127 in lane j % 64 of list_a (j < 64) or list_b: one cross-lane permute appends a
+    // trip's samples, a pass takes list_a as it stands, lane l entry l, and list_b moves down.  (In
+    // LDS the list would need 128 bytes per wave beside the queue's dead prefix, which the bench
+    // launch does not have below six workgroups per CU.)
+    // A pre-test pass costs the wave the same whatever the number of pending lanes, so it runs
+    // only on a full wave of them: a trip claims, shades the new
+    // samples, issues their lookups (closest_hit_ctab_begin), then, with kPsPassMin samples
+    // pending, runs a pass on the oldest -- keys re-derived from the entry as claim() derives
+    // them -- settles what passes, stores the values, and only then uses the lookup's words
+    // (closest_hit_ctab_finish).  Loads return in the order of their
     // issue, so a wait inside the pre-test for a global load would wait for the lookup's words as
-    // well: the pre-test issues none.  Its surface's shading frame, the hit-test records and
-    // the rows a settled ray that ends on a light folds with all come from the workgroup's LDS
-    // (the frame by the hit triangle packed in the entry).  Every sample runs
+    // well: the pre-test issues none.  Its sample, its surface's shading frame, the hit-test
+    // records and the rows a settled ray that ends on a light folds with all come from LDS.
+    // Every sample runs
     // the same float operations on the same operands as in the loop below, and the casts are
-    // counted at the same events: the image and the ray casts are unchanged.  When the queue has
-    // drained, the pre-tests still pending run after the loop.  Nothing but the pending sample
-    // and wave-uniform counters is carried from trip to trip.
+    // counted at the same events, in whichever lane: the image and the ray casts are unchanged.
+    // When the queue has drained, passes run after the loop until the list is empty, the last one
+    // partial.  Nothing but the list and wave-uniform counters is carried from trip to trip.
     if constexpr (ps_pooled(MF, CT)) piped = split;
     if constexpr (ps_pooled(MF, CT)) {
         if (piped) {
             const CtabDev& tab = ms.ctab[RULE];
-            bool pend = false;
-            f3 p_pos = make3(0.0f, 0.0f, 0.0f);
-            int p_pack = 0;  // the entry << 12 | f_tri0 << 6 | hit_tri
-            // the pending samples' pre-tests, the passes settled on the spot (wave-level)
+            int list_a = 0, list_b = 0;  // an entry: the sample's queue entry << 12 | f_tri0 << 6 | hit_tri
+            int l_cnt = 0;               // wave-uniform: pending samples
+            // one pre-test pass over the (up to 64) oldest pending samples, what passes settled on
+            // the spot (wave-level)
             auto pretest_pending = [&]() {
+                const bool pend = lane < l_cnt;
+                const int p_pack = list_a;
+                list_a = list_b;
+                l_cnt = max(0, l_cnt - 64);
 #if RT_PROF
                 const uint64_t tp = __builtin_amdgcn_s_memtime();
+                pp_loop += pp_in_loop ? 1u : 0u;
+                pp_drain += pp_in_loop ? 0u : 1u;
+                pp_lanes += (unsigned)__builtin_popcountll(__ballot(pend));
 #endif
-                const int e = p_pack >> 12, ol = e & 63, kk = e >> 6;
+                const int e = p_pack >> 12, p_tri = p_pack & 63;  // the sample's entry, the triangle its cast hit
                 bool pass = false;
                 PsKeys key;
                 key.pix = 0u;
@@ -1127,10 +1155,12 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 float c = 0.0f;
                 f3 lo = cam, ld = make3(0.0f, 0.0f, 1.0f);
                 if (pend) {
+                    const float* own = wslots + (e >> 6) * kPsFields * 64 + (e & 63);
+                    const f3 p_pos = make3(own[0 * 64], own[1 * 64], own[2 * 64]);
                     key = ps_owner_keys(a, blk, q - (lane >> a.split_log2), e);
                     // (a sample is pending only at max_bounces 2, launch_render's limit for this
                     // preset: its pre-test's depth is 1, the event a constant)
-                    ps_shade_hit<SAMPLER, LF>(a, shade, px_of(key.pix), key.cur, 1, p_pos, p_pack & 63, &c, &lo, &ld);
+                    ps_shade_hit<SAMPLER, LF>(a, shade, px_of(key.pix), key.cur, 1, p_pos, p_tri, &c, &lo, &ld);
                     pass = ps_light_pass<RULE>(a, ms, lo, ld);
                 }
                 // The passes are settled here, one ray at a time by the whole wave: lane j tests
@@ -1179,7 +1209,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                         const int dep = a.max_bounces - 1;
                         const float4 em = ps_emission<LF>(shade, tri);
                         v = make3(em.x, em.y, em.z);
-                        if (dep >= 1) ps_fold<SAMPLER, LF>(shade, v, p_pack & 63, c);
+                        if (dep >= 1) ps_fold<SAMPLER, LF>(shade, v, p_tri, c);
                         float f_c0 = c;
                         if (SAMPLER == 0 && dep >= 1) {
                             float r1, r2;
@@ -1188,11 +1218,10 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                         }
                         ps_fold<SAMPLER, LF>(shade, v, (p_pack >> 6) & 63, f_c0);
                     }
-                    float* own = wslots + kk * kPsFields * 64 + ol;
+                    float* own = wslots + (e >> 6) * kPsFields * 64 + (e & 63);
                     own[0 * 64] = v.x;
                     own[1 * 64] = v.y;
                     own[2 * 64] = v.z;
-                    pend = false;
                 }
 #if RT_PROF
                 t_pre += __builtin_amdgcn_s_memtime() - tp;
@@ -1229,35 +1258,62 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 const uint64_t tb = __builtin_amdgcn_s_memtime();
                 const uint64_t tp0 = t_pre;
 #endif
-                if (__ballot(pend) != 0ull) pretest_pending();
+                if (l_cnt >= kPsPassMin) pretest_pending();
                 const Hit h = closest_hit_ctab_finish<RULE, 1, kCtPairCap>(ms, tab, s_tri, look, so, sd, a.t_scale, has,
                                                                            wl);
 #if RT_PROF
                 pt[1] += tb - ta;  // (with the claim and the lookup's begin half)
                 pt[3] += (__builtin_amdgcn_s_memtime() - tb) - (t_pre - tp0);
 #endif
-                if (!has) continue;
-                ++n_casts;
-                if (h.tri >= 0 && h.tri < n_surf && 1 < a.max_bounces) {
-                    // a surface with one bounce left: pending
-                    p_pos = make3(so.x + h.t * (sd.x * a.t_scale), so.y + h.t * (sd.y * a.t_scale),
-                                  so.z + h.t * (sd.z * a.t_scale));
-                    p_pack = (s_e << 12) | (s_tri << 6) | h.tri;
-                    pend = true;
-                    continue;
-                }
+                n_casts += has ? 1u : 0u;
+                // a surface with one bounce left: pending
+                const bool park_it = has && h.tri >= 0 && h.tri < n_surf && 1 < a.max_bounces;
                 f3 L = make3(0.0f, 0.0f, 0.0f);  // a miss, or a surface at max_bounces
-                if (h.tri >= n_surf) {
+                if (park_it) {
+                    L = make3(so.x + h.t * (sd.x * a.t_scale), so.y + h.t * (sd.y * a.t_scale),
+                              so.z + h.t * (sd.z * a.t_scale));
+                } else if (h.tri >= n_surf) {
                     const float4 e = ps_emission<LF>(shade, h.tri);
                     L = make3(e.x, e.y, e.z);
                     ps_fold<SAMPLER, LF>(shade, L, s_tri, s_cos);  // (depth 1: the path's first bounce)
                 }
-                float* own = wslots + (s_e >> 6) * kPsFields * 64 + (s_e & 63);
-                own[0 * 64] = L.x;
-                own[1 * 64] = L.y;
-                own[2 * 64] = L.z;
+                // The list grows by this trip's n pending samples (wave-level): the k-th of them, in
+                // lane order, becomes entry l_cnt + k.  One permute of the whole wave carries it to
+                // that entry's lane; the other lanes send to the lanes past those, so that no two
+                // lanes send to the same one.
+                {
+                    const uint64_t pm = __ballot(park_it);
+                    const int n = __builtin_popcountll(pm);
+                    const uint64_t om = ~pm;
+                    // (the counts start from the wave-uniform offsets: l_cnt + k, and l_cnt + n + the
+                    // lane's rank among the others)
+                    const int kp = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32),
+                                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)pm, (uint32_t)l_cnt));
+                    const int ko = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(om >> 32),
+                                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)om, (uint32_t)(l_cnt + n)));
+                    const int to = (park_it ? kp : ko) & 63;
+                    // (h.tri of a pending sample is a surface, below 64; what the other lanes send is never read)
+                    const int got = __builtin_amdgcn_ds_permute(to << 2, (s_e << 12) | (s_tri << 6) | h.tri);
+                    const int k = (lane - l_cnt) & 63;  // this lane holds entry l_cnt + k, new if k < n
+                    if (k < n) {
+                        if (l_cnt + k < 64)
+                            list_a = got;
+                        else
+                            list_b = got;
+                    }
+                    l_cnt += n;
+                }
+                if (has) {  // the hit point of a pending sample, or the sample's value
+                    float* own = wslots + (s_e >> 6) * kPsFields * 64 + (s_e & 63);
+                    own[0 * 64] = L.x;
+                    own[1 * 64] = L.y;
+                    own[2 * 64] = L.z;
+                }
             }
-            if (__ballot(pend) != 0ull) pretest_pending();
+#if RT_PROF
+            pp_in_loop = false;
+#endif
+            while (l_cnt > 0) pretest_pending();
         }
     }
     for (; !piped;) {
@@ -1356,6 +1412,14 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
         for (int i = 0; i < 8; ++i) atomicAdd(a.prof + i, (unsigned long long)pt[i]);
         atomicAdd(a.prof + 9, (unsigned long long)t_pre);
         atomicMax(a.prof + 8, (unsigned long long)max_settle);
+        // the passes a wave would run on 64 pending samples each, and the waves that would run fewer
+        const unsigned pp_dense = (pp_lanes + 63u) >> 6;
+        atomicAdd(a.prof + 10, (unsigned long long)pp_loop);
+        atomicAdd(a.prof + 11, (unsigned long long)pp_drain);
+        atomicAdd(a.prof + 12, (unsigned long long)pp_lanes);
+        atomicAdd(a.prof + 13, (unsigned long long)pp_dense);
+        atomicAdd(a.prof + 14, (unsigned long long)(pp_dense < pp_loop + pp_drain ? 1u : 0u));
+        atomicAdd(a.prof + 15, 1ull);
     }
 #endif
     ps_finish(a, blk, wslots, chunk, lane, lx, ly, valid, acc);
