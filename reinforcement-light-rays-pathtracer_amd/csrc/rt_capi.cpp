@@ -1351,21 +1351,24 @@ int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* 
     if (rc != RT_OK) return rc;
     // RT_PS_PROF (with an RT_PROF=1 kernel build): k_render_ps's per-phase cycle sums to stderr
     static const bool prof = getenv("RT_PS_PROF") != nullptr;
-    if (prof) RT_HIP(hipMalloc(&a.prof, 16 * sizeof(unsigned long long)));
-    if (prof) RT_HIP(hipMemsetAsync(a.prof, 0, 16 * sizeof(unsigned long long), (hipStream_t)stream));
+    if (prof) RT_HIP(hipMalloc(&a.prof, 22 * sizeof(unsigned long long)));
+    if (prof) RT_HIP(hipMemsetAsync(a.prof, 0, 22 * sizeof(unsigned long long), (hipStream_t)stream));
     rt::CullLaunch cf;
     rt::ctx_cull_forms(ctx, scene, a, (hipStream_t)stream, &cf);
     RT_HIP(rt::launch_render(a, (hipStream_t)stream, &cf));
     if (prof) {
-        unsigned long long v[16];
+        unsigned long long v[22];
         RT_HIP(hipStreamSynchronize((hipStream_t)stream));
         RT_HIP(hipMemcpy(v, a.prof, sizeof(v), hipMemcpyDeviceToHost));
         RT_HIP(hipFree(a.prof));
         fprintf(stderr, "{\"ps_prof\": {\"primary\": %llu, \"shade\": %llu, \"masks\": %llu, \"exact\": %llu, "
                         "\"bounce_total\": %llu, \"trips\": %llu, \"light_passes\": %llu, \"sparse_trips\": %llu, "
                         "\"max_settle\": %llu, \"pretest\": %llu, \"pretest_passes_loop\": %llu, \"pretest_passes_drain\": %llu, "
-                        "\"pending_lanes\": %llu, \"dense_passes\": %llu, \"waves_saving\": %llu, \"waves\": %llu}}\n",
-                v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12], v[13], v[14], v[15]);
+                        "\"pending_lanes\": %llu, \"dense_passes\": %llu, \"waves_saving\": %llu, \"waves\": %llu, "
+                        "\"exact_list_iters\": %llu, \"exact_fold_iters\": %llu, \"exact_pairs\": %llu, "
+                        "\"exact_rounds\": %llu, \"exact_passes\": %llu, \"exact_max_lane_passes\": %llu}}\n",
+                v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], v[12], v[13], v[14], v[15],
+                v[16], v[17], v[18], v[19], v[20], v[21]);
     }
     return RT_OK;
 }

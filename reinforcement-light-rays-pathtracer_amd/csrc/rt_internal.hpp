@@ -247,7 +247,7 @@ struct RenderLaunch {
     // k_cull_ps (diagnostic): kRenderCullWords 64-bit candidate masks per wave
     // (n_blocks * split * 4 waves); unused by the renders
     unsigned long long* cull;
-    // RT_PROF builds only: per-phase s_memtime cycle sums and counters of k_render_ps (16 words)
+    // RT_PROF builds only: per-phase s_memtime cycle sums and counters of k_render_ps (22 words)
     unsigned long long* prof;
     // GPU preset, persistent chunk queue (k_render_pq): the chunk sums [n_blocks * 256 *
     // split][3] and the work counter (zeroed by the launcher); null: the per-pixel kernels

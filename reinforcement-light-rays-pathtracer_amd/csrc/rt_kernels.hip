@@ -909,6 +909,7 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
 #if RT_PROF
     // P, shade, filter masks, exact, post, loops, light pre-test passes, loops with < 16 live lanes
     uint64_t pt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    ExactProf xprof = {0u, 0u, 0u, 0u, 0u, 0u};  // the bounce trips' shared exact phase
     uint64_t t0 = __builtin_amdgcn_s_memtime();
 #endif
     const float nts = a.t_scale;
@@ -1259,8 +1260,13 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
                 const uint64_t tp0 = t_pre;
 #endif
                 if (l_cnt >= kPsPassMin) pretest_pending();
+#if RT_PROF
+                const Hit h = closest_hit_ctab_finish<RULE, 1, kCtPairCap>(ms, tab, s_tri, look, so, sd, a.t_scale, has,
+                                                                           wl, &xprof);
+#else
                 const Hit h = closest_hit_ctab_finish<RULE, 1, kCtPairCap>(ms, tab, s_tri, look, so, sd, a.t_scale, has,
                                                                            wl);
+#endif
 #if RT_PROF
                 pt[1] += tb - ta;  // (with the claim and the lookup's begin half)
                 pt[3] += (__builtin_amdgcn_s_memtime() - tb) - (t_pre - tp0);
@@ -1420,6 +1426,12 @@ __device__ __forceinline__ unsigned ps_body(const RenderLaunch& a, const CullLau
         atomicAdd(a.prof + 13, (unsigned long long)pp_dense);
         atomicAdd(a.prof + 14, (unsigned long long)(pp_dense < pp_loop + pp_drain ? 1u : 0u));
         atomicAdd(a.prof + 15, 1ull);
+        atomicAdd(a.prof + 16, (unsigned long long)xprof.list_iters);
+        atomicAdd(a.prof + 17, (unsigned long long)xprof.fold_iters);
+        atomicAdd(a.prof + 18, (unsigned long long)xprof.pairs);
+        atomicAdd(a.prof + 19, (unsigned long long)xprof.rounds);
+        atomicAdd(a.prof + 20, (unsigned long long)xprof.passes);
+        atomicAdd(a.prof + 21, (unsigned long long)xprof.max_pass);
     }
 #endif
     ps_finish(a, blk, wslots, chunk, lane, lx, ly, valid, acc);

@@ -475,6 +475,18 @@ __host__ __device__ constexpr int mf_wave_floats(int cap, int rule) {
     return (rule == 1 && 6 * 64 + cap / 2 + cap < 11 * 64) ? 11 * 64 : 6 * 64 + cap / 2 + cap;
 }
 
+#if RT_PROF
+// counters of the shared exact phase, per wave (RT_PROF builds; k_render_ps sums them into
+// RenderLaunch::prof): iterations of the listing walk and of the fold loop, pairs listed, test
+// rounds of 64, pairs that pass exact_tv, and the sum over trips of the most passing pairs one
+// lane owned
+struct ExactProf {
+    unsigned list_iters, fold_iters, pairs, rounds, passes, max_pass;
+};
+#else
+struct ExactProf;
+#endif
+
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // The exact phase of one 64-triangle block (triangles tri0 + bit of F) shared by the
@@ -483,7 +495,8 @@ __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcn
 // trip count is (candidates of the wave) / 64 instead of the largest per-lane count.
 template <int RULE, int CAP = kMfPairCap>
 __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, int tri0, uint64_t F, f3 o,
-                                              float nDx, float nDy, float nDz, float* wl, int lane, Hit& h) {
+                                              float nDx, float nDy, float nDz, float* wl, int lane, Hit& h,
+                                              ExactProf* xp = nullptr) {
     const int cnt = __builtin_popcountll(F);  // 0..64: 7 bits
     // exclusive prefix sum over the lanes, bit-sliced through ballots (no LDS round trips,
     // unlike a shuffle scan: the cross-lane permutes were a dependent chain of 6)
@@ -497,7 +510,21 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
     if (total == 0) return;
     const float* ray = wl;  // (o, -D) of every lane: written by closest_hit_mf before its masks
     uint16_t* pr = reinterpret_cast<uint16_t*>(wl + 6 * 64);
+#if RT_PROF
+    unsigned my_pass = 0, walk = 0;
+    if (xp) {
+        for (int c = 64; c >= 1; --c)
+            if (walk == 0 && __ballot(cnt >= c) != 0ull) walk = (unsigned)c;  // the busiest lane's count
+        xp->pairs += total;
+    }
+#endif
     for (int cb = 0; cb < total; cb += CAP) {
+#if RT_PROF
+        if (xp) {
+            xp->list_iters += walk;
+            xp->fold_iters += walk;
+        }
+#endif
         {
             uint64_t G = F;
             int p = excl - cb;
@@ -517,6 +544,12 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
             const f3 ro = make3(ray[0 * 64 + rl], ray[1 * 64 + rl], ray[2 * 64 + rl]);
             tv[k] = exact_tv<RULE>(isect, tri0 + (int)(q & 63u), ro, ray[3 * 64 + rl], ray[4 * 64 + rl],
                                    ray[5 * 64 + rl]);
+#if RT_PROF
+            if (xp) {
+                xp->rounds += 1;
+                xp->passes += __builtin_popcountll(__ballot(tv[k] < __builtin_inff()));
+            }
+#endif
         }
         wave_lds_sync();
         {
@@ -527,6 +560,9 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
                 G &= G - 1ull;
                 if (p >= 0 && p < CAP) {
                     const float t = tv[p];
+#if RT_PROF
+                    my_pass += t < __builtin_inff() ? 1u : 0u;
+#endif
                     if ((RULE == 0) ? (t < h.t + kEps) : (t < h.t)) {
                         h.t = t;
                         h.tri = tri0 + b;
@@ -537,6 +573,15 @@ __device__ __forceinline__ void mf_exact_wave(const float4* __restrict__ isect, 
         }
         wave_lds_sync();  // the pair list is read before the next window overwrites it
     }
+#if RT_PROF
+    if (xp) {
+        for (int c = 61; c >= 1; --c)
+            if (__ballot(my_pass >= (unsigned)c) != 0ull) {
+                xp->max_pass += (unsigned)c;
+                break;
+            }
+    }
+#endif
 }
 
 // s.mf_frag may point to a workgroup's LDS copy of the image (k_render_ps);
@@ -830,6 +875,10 @@ __device__ __forceinline__ bool ctab_usable(const CtabDev& T, float t_scale) {
 // (mf_exact_wave, per 64-triangle block).  Wave-level like closest_hit_mf (a lane without a ray:
 // F = 0).  closest_hit_ctab: F from the table T for a bounce ray leaving surface `surf`.
 // RULE 1's shared exact phase folds by minimum (cand_exact_min) instead of per-lane list walks.
+#ifndef RT_CAND_DENSE
+#define RT_CAND_DENSE 1  // 0: the one-word table route's shared phase by mf_exact_wave's list walks, as every
+                         // other route (the A/B of profiles/r15_*)
+#endif
 #ifndef RT_CAND_OWN_MIN
 #define RT_CAND_OWN_MIN 0  // RT_CTAB_OWN of the min-fold phase (complex_light_room 512^2 x 64: 0 / 1 -> 50.9 / 66.8 ms)
 #endif
@@ -906,9 +955,110 @@ __device__ __forceinline__ void cand_exact_min(const float4* __restrict__ isect,
     wave_lds_sync();
 }
 
+// inclusive maximum scan of v >= 0 over the wave's lanes: shifts within the rows of 16, then each
+// row's last value broadcast to the rows after it (DPP: no LDS round trip; a lane without a
+// source keeps 0)
+__device__ __forceinline__ int wave_max_scan(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));  // row_shr:1
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));  // row_shr:2
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));  // row_shr:4
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));  // row_shr:8
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));  // row_bcast:15 -> rows 1, 3
+    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));  // row_bcast:31 -> rows 2, 3
+    return v;
+}
+
+// The shared exact phase of the one-word table route under RULE 0, at a cost per round of 64
+// pairs that does not depend on the lanes' counts.  The wave's (lane, candidate) pairs are
+// numbered lane-major as in mf_exact_wave; lane k of a round tests pair cb + k.
+//   listing: an owner with candidates writes lane + 1 at byte `excl - cb` of a zeroed row of 64
+//     (positions are distinct: owners' excl strictly increase).  The inclusive maximum scan of
+//     the row, with the previous round's last value carried in, gives every pair its owner; the
+//     owner's mask and first pair number come by ds_bpermute and the triangle is the
+//     (k - excl_owner)-th set bit of that mask.  No lane walks its list.
+//   fold: one ballot of the passes (t finite: +inf never passes the window); an owner cuts its
+//     range [excl, excl + cnt) of the round out of it and fetches t and the triangle of its set
+//     bits only, in ascending position = ascending triangle index, under the window
+//     t < best + eps.  A failing pair never changed mf_exact_wave's best either, so the hit is
+//     the same bit for bit; a range that straddles rounds carries best over in h.
+// LDS (wl): the rays' 6 x 64 floats as closest_hit_cand parks them, then the row's 64 bytes.
+__device__ __forceinline__ void cand_exact_dense(const float4* __restrict__ isect, uint64_t F, float* wl, int lane,
+                                                 Hit& h, ExactProf* xp = nullptr) {
+    const int cnt = __builtin_popcountll(F);
+    int excl = 0, total = 0;
+#pragma unroll
+    for (int b = 0; b < 7; ++b) {
+        const uint64_t bm = __ballot((cnt >> b) & 1);
+        excl += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u)) << b;
+        total += __builtin_popcountll(bm) << b;
+    }
+    if (total == 0) return;
+    const float* ray = wl;
+    uint8_t* row = reinterpret_cast<uint8_t*>(wl + 6 * 64);
+    const int f_lo = (int)(uint32_t)F, f_hi = (int)(uint32_t)(F >> 32);
+    int carry = 0;  // lane + 1 of the owner of the previous round's last pair
+#if RT_PROF
+    unsigned my_pass = 0;
+#endif
+    for (int cb = 0; cb < total; cb += 64) {
+        const int lo = excl - cb;  // the lane's pairs in this round: positions [lo, lo + cnt) of [0, 64)
+        row[lane] = 0;
+        if (cnt != 0 && lo >= 0 && lo < 64) row[lo] = (uint8_t)(lane + 1);
+        wave_lds_sync();
+        const int own = max(wave_max_scan((int)row[lane]), carry);
+        carry = __builtin_amdgcn_readlane(own, 63);
+        const int k = cb + lane;
+        const bool valid = k < total;
+        // (every lane takes part in the permutes: a lane reads its owner's registers)
+        const int ra = (valid ? (own - 1) & 63 : lane) << 2;
+        const uint32_t o_lo = (uint32_t)__builtin_amdgcn_ds_bpermute(ra, f_lo);
+        const uint32_t o_hi = (uint32_t)__builtin_amdgcn_ds_bpermute(ra, f_hi);
+        const int o_ex = __builtin_amdgcn_ds_bpermute(ra, excl);
+        float t = __builtin_inff();
+        int tri = 0;
+        if (valid) {
+            const int rl = ra >> 2;
+            tri = select_bit(((uint64_t)o_hi << 32) | o_lo, k - o_ex);
+            const f3 ro = make3(ray[0 * 64 + rl], ray[1 * 64 + rl], ray[2 * 64 + rl]);
+            t = exact_tv<0>(isect, tri, ro, ray[3 * 64 + rl], ray[4 * 64 + rl], ray[5 * 64 + rl]);
+        }
+        const uint64_t pass = __ballot(t < __builtin_inff());
+        // the lane's part [ra0, rb0) of the round (shift counts taken mod 64 where it is empty)
+        const int ra0 = max(lo, 0), rb0 = min(lo + cnt, 64);
+        uint64_t m = ra0 < rb0 ? pass & (~0ull << (ra0 & 63)) & (~0ull >> ((64 - rb0) & 63)) : 0ull;
+#if RT_PROF
+        if (xp) {
+            xp->rounds += 1;
+            xp->passes += __builtin_popcountll(pass);
+            my_pass += __builtin_popcountll(m);
+        }
+#endif
+        while (__ballot(m != 0ull) != 0ull) {
+            const bool mine = m != 0ull;
+            const int ja = (mine ? __builtin_ctzll(m) : lane) << 2;
+            const float tj = __int_as_float(__builtin_amdgcn_ds_bpermute(ja, __float_as_int(t)));
+            const int bj = __builtin_amdgcn_ds_bpermute(ja, tri);
+            if (mine && tj < h.t + kEps) {
+                h.t = tj;
+                h.tri = bj;
+            }
+            m &= m - 1ull;
+#if RT_PROF
+            if (xp) xp->fold_iters += 1;
+#endif
+        }
+    }
+#if RT_PROF
+    if (xp) {
+        xp->pairs += total;
+        xp->max_pass += __builtin_amdgcn_readlane(wave_max_scan((int)my_pass), 63);
+    }
+#endif
+}
+
 template <int RULE, int NW, int CAP = kMfPairCap>
 __device__ __forceinline__ Hit closest_hit_cand(const DeviceScene& s, uint64_t (&F)[NW], f3 o, f3 d, float t_scale,
-                                                float* wl) {
+                                                float* wl, ExactProf* xp = nullptr) {
     const float nDx = -(d.x * t_scale);
     const float nDy = -(d.y * t_scale);
     const float nDz = -(d.z * t_scale);
@@ -958,7 +1108,12 @@ __device__ __forceinline__ Hit closest_hit_cand(const DeviceScene& s, uint64_t (
     } else {
 #pragma unroll
         for (int w = 0; w < NW; ++w)
-            if (64 * w < s.n_tri) mf_exact_wave<RULE, CAP>(s.isect, 64 * w, F[w], o, nDx, nDy, nDz, wl, lane, h);
+            if (64 * w < s.n_tri) {
+                if constexpr (RT_CAND_DENSE && RULE == 0 && NW == 1 && CAP == kCtPairCap)
+                    cand_exact_dense(s.isect, F[w], wl, lane, h, xp);
+                else
+                    mf_exact_wave<RULE, CAP>(s.isect, 64 * w, F[w], o, nDx, nDy, nDz, wl, lane, h, xp);
+            }
     }
     return h;
 }
@@ -986,7 +1141,7 @@ __device__ __forceinline__ CtabLook<NW> closest_hit_ctab_begin(const CtabDev& T,
 template <int RULE, int NW, int CAP = kMfPairCap>
 __device__ __forceinline__ Hit closest_hit_ctab_finish(const DeviceScene& s, const CtabDev& T, int surf,
                                                        const CtabLook<NW>& L, f3 o, f3 d, float t_scale, bool active,
-                                                       float* wl) {
+                                                       float* wl, ExactProf* xp = nullptr) {
     uint64_t F[NW];
     if (active) {
         ctab_finish<NW>(T, s.n_tri, surf, L, F);
@@ -994,7 +1149,7 @@ __device__ __forceinline__ Hit closest_hit_ctab_finish(const DeviceScene& s, con
 #pragma unroll
         for (int k = 0; k < NW; ++k) F[k] = 0ull;
     }
-    return closest_hit_cand<RULE, NW, CAP>(s, F, o, d, t_scale, wl);
+    return closest_hit_cand<RULE, NW, CAP>(s, F, o, d, t_scale, wl, xp);
 }
 
 template <int RULE>
