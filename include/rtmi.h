@@ -833,6 +833,114 @@ int rt_probe_radiance_device(rt_ctx* ctx, const rt_scene* scene, const rt_params
                              const int32_t* d_tri, const uint32_t* d_ids, int n, uint32_t first_sample,
                              float* d_rad, float* d_irr, float* d_dir, uint64_t* d_casts, void* stream);
 
+/* ---- radiance-volume glyphs ------------------------------------------------------
+ * The picture the reference judges a radiance map or a Q-network with (thesis ch. 4,
+ * Images/expected_sarsa_visualisation.png, neural_q_visualisation.png, true_distribution.png):
+ * selected surface points, each drawn as a hemisphere of 12 x 12 coloured sectors inside the
+ * scene.  GPU engine: RENDER_SAVED_RADIANCE_VOLUMES (GPU/constants/image_settings.h:15) makes
+ * Scene::load_custom_scene (GPU/scenes/scene.cu:41-46) call
+ * RadianceVolume::read_radiance_volumes_to_surfaces = read_radiance_volumes_from_file +
+ * get_vertices + build_surfaces (GPU/radiance_volumes/radiance_volume.cu:375-515); CPU engine:
+ * build_radiance_volume_shapes / build_radiance_magnitude_volume_shapes
+ * (CPU/radiance_volumes/radiance_volume.cpp:100-174).  The inputs are the files of
+ * rt_sarsa_save_selected, rt_dqn_save_selected and tools/true_distribution.py.
+ *
+ * Unlike the reference, which appends 288 diffuse triangles per volume to the scene (with
+ * hand-written normals) and path traces everything, the glyphs here are an overlay view: the
+ * mesh never enters an rt_scene, is unlit, and is composited over any frame the library renders.
+ *
+ * rt_selected_read: read_radiance_volumes_from_file (radiance_volume.cu:377-440), host only.  One
+ *   row "x y z nx ny nz d0 .. d143" per line, every value strtof of its token, through the parser
+ *   of rt_qtable_read; lines of blanks are skipped.  Two passes like rt_qtable_read: with pos,
+ *   normal and values NULL the call sizes (*n out); with all three given, *n holds on entry the
+ *   row count the arrays were allocated for and the file must still have it.  A missing file, a
+ *   row with too few or too many tokens, or a token that is not a number returns RT_E_IO with the
+ *   line's number in the message.
+ * rt_glyph_mesh: get_vertices + build_surfaces (radiance_volume.cu:442-515), host only.  For a
+ *   glyph at P with normal N (used as given: the reference does not normalise what it reads) and
+ *   diameter D (the reference's DIAMETER, 0.15f, which acts as a radius): (T, B) = the frame of N
+ *   (create_normal_coordinate_system); for x, y in 0..12, (xh, yh, zh) = Chiu's map of
+ *   (x / 12.f, y / 12.f), each times D in one rounded multiply (xs, ys, zs), and
+ *     V[x][y].c = (T.c * xs + N.c * ys) + (B.c * zs + P.c)
+ *   Quad k = x * 12 + y (the sector of every other entry point) gives triangle 2k = (V[x][y],
+ *   V[x][y+1], V[x+1][y]) and 2k + 1 = (V[x+1][y], V[x][y+1], V[x+1][y+1]), the reference's
+ *   (v0, v2, v1) and (v1, v2, v3).  quad_normal[k] = normalize(mid - P), mid = (((v0 + v1) + v2)
+ *   + v3) / 4.f per component: what build_surfaces writes over the triangles' normals.
+ *   RT_E_INVALID: a non-finite input, a zero normal, D not > 0.
+ * rt_glyph_colours: the sector colours, host only.
+ *   RT_GLYPH_RATIO (the GPU engine, build_surfaces): m = 0; scanning k upward m = v[k] wherever
+ *     m < v[k]; ratio = v[k] / m (0 for a row whose m stays 0); colour (ratio, 1.f - ratio, 0).
+ *   RT_GLYPH_MAGNITUDE (the CPU engine, build_radiance_magnitude_volume_shapes): m starts at
+ *     0.0001f and takes |v[k]| where that is larger; colour grey 1.f - |v[k]| / m.
+ *   Non-finite values: RT_E_INVALID.
+ *
+ * rt_glyphs_create: a glyph set on the context's device, 0 <= n <= RT_GLYPH_MAX (n = 0 is a valid
+ *   empty set): rt_glyph_mesh's triangles as an intersection-record soup of its own, the exact BVH
+ *   of rt_bvh.cpp built over it at once, rt_glyph_colours(colour_mode)'s table and the quad
+ *   normals.  rt_glyphs_create_sized: the same with a diameter per glyph (diameters: n), for a
+ *   picture that mixes sizes.  rt_glyphs_set_colours replaces the table (rgb: n x 144 x 3, the
+ *   caller's own).
+ *   rt_glyphs_info: glyphs, triangles (288 n), nodes of the BVH (pointers may be NULL).
+ *
+ * rt_render_glyph_view (k_glyph_view, csrc/rt_glyph.hip): per sample s in [first_sample,
+ *   first_sample + spp) of every pixel, rt_render_volume_view's camera ray (jitter draw2(pix, s,
+ *   0, seed), camera_ray<1>); H_s its closest hit in the scene under the GPU hit rule and t_scale
+ *   (k_sarsa_view's route, or the scene's BVH where its accel mode turns it on: the same hits);
+ *   H_g its closest hit in the glyph soup under the same rule.  The winner is the hit of the scan
+ *   over the soup "scene surfaces, then glyph triangles, then lights": the glyph wins iff
+ *   t_g < t_s, or t_g == t_s and H_s is a light.
+ *   The sample's value: glyph triangle j gives glyph j / 288, sector (j % 288) / 2 and that
+ *   sector's colour, with opts->shade != 0 every channel times
+ *     0.25f + 0.75f * fmaxf(-((nq.x * d.x + nq.y * d.y) + nq.z * d.z), 0.f)
+ *   (nq the sector's quad normal, d the ray direction, every operation rounded once; the mesh is
+ *   two-sided, as the hit test is).  Otherwise base_rgb[pixel] where a base was given; without a
+ *   base a surface gives its albedo, a light its emission and a miss params->env_light.
+ *   The pixel is the sum of its spp_split chunk sums in order, divided by (float)spp
+ *   (k_sarsa_view's fold).  max_bounces and sampler are ignored.
+ *   base_rgb: host W x H x 3 or NULL; out_rgb: W x H x 3, required.  out_tri, out_glyph,
+ *   out_sector, out_t (W x H, each may be NULL) describe sample first_sample: out_tri the scene's
+ *   own hit, rt_render_volume_view's out_tri bit for bit, glyph in front or not; out_glyph and
+ *   out_sector -1 unless a glyph won; out_t the winner's t, +inf for a miss.
+ *   The scene, its tables and the glyph set are read only.  A pixel depends on neither the tile
+ *   list nor the glyph cast's route: the BVH, or with RTMI_GLYPH_BVH=0 in the environment (read
+ *   per call) the plain scan of the soup.
+ *   Refused before any device work, params by value first: size or spp <= 0, a bad spp_split
+ *   (RT_E_INVALID); another preset or hit rule than the GPU engine's (RT_E_UNSUPPORTED); then
+ *   NULL required pointers (RT_E_INVALID).  rt_glyphs_create checks n before its pointers.
+ *   The launches are timed under RT_KT_SARSA_VIEW.
+ * rt_render_glyph_view_tiles_device: the same over a tile list into device memory,
+ *   stream-ordered; tiles and output layout as rt_render_sarsa_tiles_device; d_base: the whole
+ *   W x H x 3 image on the device, or NULL.  n_tiles == 0 is RT_OK. */
+#define RT_GLYPH_MAX 256      /* glyphs per set: 73,728 triangles */
+#define RT_GLYPH_SECTORS 144
+#define RT_GLYPH_TRIS 288     /* triangles per glyph */
+#define RT_GLYPH_RATIO 0
+#define RT_GLYPH_MAGNITUDE 1
+typedef struct rt_glyphs rt_glyphs;
+typedef struct {
+    int32_t shade; /* != 0: the sector colour times 0.25 + 0.75 max(-nq.d, 0) */
+} rt_glyph_view_opts;
+int rt_selected_read(const char* path, int32_t* n, float* pos /* n x 3 */, float* normal /* n x 3 */,
+                     float* values /* n x 144 */);
+int rt_glyph_mesh(const float* pos, const float* normal, int32_t n, float diameter,
+                  float* tri_v /* n x 288 x 9 */, float* quad_normal /* n x 144 x 3, may be NULL */);
+int rt_glyph_colours(const float* values /* n x 144 */, int32_t n, int mode, float* rgb /* n x 144 x 3 */);
+int rt_glyphs_create(rt_ctx* ctx, const float* pos, const float* normal, const float* values, int32_t n,
+                     float diameter, int colour_mode, rt_glyphs** out);
+int rt_glyphs_create_sized(rt_ctx* ctx, const float* pos, const float* normal, const float* values,
+                           const float* diameters /* n */, int32_t n, int colour_mode, rt_glyphs** out);
+int rt_glyphs_destroy(rt_glyphs* glyphs);
+int rt_glyphs_set_colours(rt_glyphs* glyphs, const float* rgb /* n x 144 x 3 */);
+int rt_glyphs_info(const rt_glyphs* glyphs, int32_t* n_glyphs, int32_t* n_tri, int32_t* bvh_nodes);
+int rt_render_glyph_view(rt_ctx* ctx, const rt_scene* scene, const rt_glyphs* glyphs, const rt_camera* cam,
+                         const rt_params* params, const rt_glyph_view_opts* opts, uint32_t first_sample,
+                         const float* base_rgb, float* out_rgb, int32_t* out_tri, int32_t* out_glyph,
+                         int32_t* out_sector, float* out_t);
+int rt_render_glyph_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_glyphs* glyphs,
+                                      const rt_camera* cam, const rt_params* params,
+                                      const rt_glyph_view_opts* opts, uint32_t first_sample, const float* d_base,
+                                      const int32_t* tiles, int n_tiles, int tile_size, float* d_out, void* stream);
+
 /* Device self-tests of numeric building blocks (no reference counterpart): every
  * bit-exact claim against oracle/ rests on them.  result[0] = mismatches, result[1] = the
  * lowest mismatching input bits (0xffffffff: none).
@@ -910,7 +1018,7 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 #define RT_KT_DQN_MLP 4       /* k_dqn_mlp: the Q-network forward (config 4) */
 #define RT_KT_DQN_BOUNCE 5    /* k_dqn_bounce: Q.cos sampling + trace; in rt_render_dqn_view, k_dqn_view_reduce */
 #define RT_KT_DQN_CAMERA 6    /* k_dqn_camera */
-#define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view) */
+#define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view); k_glyph_view (rt_render_glyph_view) */
 #define RT_KT_SARSA_NEAREST 8 /* k_sarsa_nearest: rt_sarsa_nearest's queries (without its copies) */
 #define RT_KT_PROBE 9         /* k_probe: rt_probe_radiance's paths (without its fold) */
 #define RT_KT_BAKE 10         /* k_bake: rt_sarsa_bake's paths (without its finish) */

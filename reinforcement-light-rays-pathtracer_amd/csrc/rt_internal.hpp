@@ -22,7 +22,7 @@ enum KtimeKernel {
     KT_DQN_MLP = 4,
     KT_DQN_BOUNCE = 5,
     KT_DQN_CAMERA = 6,
-    KT_SARSA_VIEW = 7,  // k_sarsa_view (the radiance-map view)
+    KT_SARSA_VIEW = 7,  // k_sarsa_view (the radiance-map view), k_glyph_view (the glyph view)
     KT_SARSA_NEAREST = 8,  // k_sarsa_nearest (rt_sarsa_nearest's queries)
     KT_PROBE = 9,  // k_probe (rt_probe_radiance)
     KT_BAKE = 10,  // k_bake (rt_sarsa_bake's paths, without its finish)
@@ -501,6 +501,23 @@ hipError_t launch_sarsa_knn(const SarsaMap& m, const float* pos, const float* nr
 // the irradiance render (k_sarsa_irr): r as launch_sarsa_view's; out_vol / out_dist [pixel][k]
 hipError_t launch_sarsa_irr(const RenderLaunch& r, const SarsaMap& m, int k, float radius, int cone, int tint,
                             int32_t* out_tri, float* out_pos, int32_t* out_vol, float* out_dist, hipStream_t stream);
+
+// ---- radiance-volume glyphs (rt_glyph.hip, rt_glyph_host.cpp; rtmi.h "radiance-volume glyphs") ----
+constexpr int kGlyphSectors = 144;                // RT_GLYPH_SECTORS: quads of a glyph, k = x * 12 + y
+constexpr int kGlyphTris = 2 * kGlyphSectors;     // RT_GLYPH_TRIS: triangle j of the soup is quad j / 2
+// a glyph set as k_glyph_view reads it
+struct GlyphSet {
+    DeviceScene soup;                 // the mesh's hit-test records (n_tri = 288 n, 0 for an empty set); its bvh_*
+                                      // fields set: the glyph cast takes the exact BVH, null: the plain scan
+    const float4* colour = nullptr;   // [144 n] rgb of quad q (w unused)
+    const float4* qnormal = nullptr;  // [144 n] the quad's normal, normalize(mid - P) (w unused)
+    const float* base = nullptr;      // the whole width x height x 3 image the glyphs are drawn over, or null
+    int shade = 0;                    // rt_glyph_view_opts.shade
+};
+// the glyph view (k_glyph_view): r as launch_sarsa_view's (hit rule GPU); out_tri / out_glyph / out_sector / out_t:
+// optional per-pixel AOVs of sample r.sample_base, in r.out's pixel layout.  Timed under KT_SARSA_VIEW.
+hipError_t launch_glyph_view(const RenderLaunch& r, const GlyphSet& g, int32_t* out_tri, int32_t* out_glyph,
+                             int32_t* out_sector, float* out_t, hipStream_t stream);
 
 hipError_t launch_intersect(const DeviceScene& s, const float* orig, const float* dir, int n,
                             float t_scale, int hit_rule, int use_filter, float* out_t,

@@ -1120,31 +1120,6 @@ __global__ __launch_bounds__(256) void k_sarsa_nearest(const SarsaMap m, const f
     if (in) out[i] = v;
 }
 
-// closest_hit's answer from the wave's camera-ray candidates (wave_candidates: the triangles
-// the cull of the wave's pixel rectangle keeps; cm is wave-uniform): the exact test on the
-// kept triangles in index order, their records by scalar loads.  No wave-level operation:
-// lanes without a ray skip it.
-template <int RULE>
-__device__ __forceinline__ Hit view_hit_culled(const DeviceScene& sc, const uint64_t* cm, f3 o, f3 d, float t_scale) {
-    cfloat4* __restrict__ tri = as_const(sc.isect);
-    const float nDx = -(d.x * t_scale);
-    const float nDy = -(d.y * t_scale);
-    const float nDz = -(d.z * t_scale);
-    Hit h;
-    h.t = (RULE == 0) ? FLT_MAX : 999999.0f;
-    h.tri = -1;
-#pragma unroll
-    for (int g = 0; g < kRenderCullWords; ++g) {
-        uint64_t w = cm[g];
-        while (w != 0ull) {
-            const int i = 64 * g + __builtin_ctzll(w);
-            w &= w - 1ull;
-            exact_one_c<RULE>(tri, i, o, nDx, nDy, nDz, h);
-        }
-    }
-    return h;
-}
-
 // The radiance-map view (the reference's PATH_TRACING_METHOD 2: GPU/path_tracing/
 // voronoi_trace.cu:6-41, RadianceMap::get_voronoi_colour, radiance_map.cu:218-225): per
 // sample the camera ray of k_sarsa_render (sample index a.sample_base + s), its closest hit,

@@ -554,8 +554,10 @@ int view_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const 
 // action count, then "x y z Q0 .. Q(A-1)" per line, each value strtof of its whole token
 // (std::stof).  Lines of blanks are skipped.  pos (rows x 3) and q (rows x actions) may be
 // NULL: the rows are then only checked and counted.  RT_E_IO names the line.  The one parser
-// of this format: rt_sarsa_load_q and rt_qtable_read.
-int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<float>* pos, std::vector<float>* q) {
+// of this format: rt_sarsa_load_q and rt_qtable_read.  fixed > 0: a file without the header
+// line whose rows hold 3 + fixed values (rt_selected_read: the normal and the 144 sectors).
+int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<float>* pos, std::vector<float>* q,
+                  int fixed = 0) {
     std::ifstream in(path);
     if (!in.is_open()) return err(RT_E_IO, std::string("cannot open ") + path);
     auto bad = [&](int line, const std::string& what) {
@@ -563,8 +565,9 @@ int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<flo
     };
     const char* blanks = " \t\r\n\v\f";
     std::string line, tok;
-    int line_no = 0, actions = 0, rows = 0;
-    bool have_header = false;
+    int line_no = 0, actions = fixed, rows = 0;
+    bool have_header = fixed > 0;
+    bool header_line = false;
     while (std::getline(in, line)) {
         ++line_no;
         size_t at = line.find_first_not_of(blanks);
@@ -576,6 +579,7 @@ int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<flo
             at = end == std::string::npos ? end : line.find_first_not_of(blanks, end);
             char* stop = nullptr;
             if (!have_header) {
+                header_line = true;
                 const long a = strtol(tok.c_str(), &stop, 10);
                 if (stop == tok.c_str() || *stop != '\0' || at != std::string::npos)
                     return bad(line_no, "the first line must be the action count");
@@ -594,8 +598,9 @@ int parse_q_table(const char* path, int* n_rows, int* n_actions, std::vector<flo
             }
             ++count;
         }
-        if (!have_header) {
+        if (header_line) {
             have_header = true;
+            header_line = false;
             continue;
         }
         if (count != 3 + actions)
@@ -1097,6 +1102,33 @@ int rt_qtable_read(const char* path, int32_t* n_rows, int32_t* n_actions, float*
         return err(RT_E_IO, std::string(path) + ": the table's size differs from the sizing pass's");
     if (!fpos.empty()) memcpy(pos, fpos.data(), sizeof(float) * fpos.size());
     if (!fq.empty()) memcpy(q, fq.data(), sizeof(float) * fq.size());
+    return RT_OK;
+}
+
+// read_radiance_volumes_from_file (radiance_volume.cu:377-440): "x y z nx ny nz d0 .. d143" rows,
+// through parse_q_table in its headerless form (3 + 147 values per row)
+int rt_selected_read(const char* path, int32_t* n, float* pos, float* normal, float* values) {
+    if (!path || !n) return err(RT_E_INVALID, "NULL argument");
+    const int given = (pos != nullptr) + (normal != nullptr) + (values != nullptr);
+    if (given != 0 && given != 3)
+        return err(RT_E_INVALID, "pos, normal and values must all be given or all be NULL");
+    constexpr int kRest = 3 + rt::kSarsaSectors;
+    int rows = 0, cols = 0;
+    if (given == 0) {
+        const int rc = parse_q_table(path, &rows, &cols, nullptr, nullptr, kRest);
+        if (rc != RT_OK) return rc;
+        *n = rows;
+        return RT_OK;
+    }
+    std::vector<float> fpos, rest;
+    const int rc = parse_q_table(path, &rows, &cols, &fpos, &rest, kRest);
+    if (rc != RT_OK) return rc;
+    if (rows != *n) return err(RT_E_IO, std::string(path) + ": the file's row count differs from the sizing pass's");
+    if (!fpos.empty()) memcpy(pos, fpos.data(), sizeof(float) * fpos.size());
+    for (int r = 0; r < rows; ++r) {
+        memcpy(normal + (size_t)3 * r, &rest[(size_t)kRest * r], sizeof(float) * 3);
+        memcpy(values + (size_t)rt::kSarsaSectors * r, &rest[(size_t)kRest * r + 3], sizeof(float) * rt::kSarsaSectors);
+    }
     return RT_OK;
 }
 

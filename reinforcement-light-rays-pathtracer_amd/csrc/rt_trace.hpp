@@ -1502,6 +1502,32 @@ __device__ __forceinline__ void wave_candidates(const RenderLaunch& a, bool vali
     }
 }
 
+// closest_hit's answer from the wave's camera-ray candidates (wave_candidates: the triangles
+// the cull of the wave's pixel rectangle keeps; cm is wave-uniform): the exact test on the
+// kept triangles in index order, their records by scalar loads.  No wave-level operation:
+// lanes without a ray skip it.  The view kernels' camera cast (k_sarsa_view, k_sarsa_irr,
+// k_glyph_view).
+template <int RULE>
+__device__ __forceinline__ Hit view_hit_culled(const DeviceScene& sc, const uint64_t* cm, f3 o, f3 d, float t_scale) {
+    cfloat4* __restrict__ tri = as_const(sc.isect);
+    const float nDx = -(d.x * t_scale);
+    const float nDy = -(d.y * t_scale);
+    const float nDz = -(d.z * t_scale);
+    Hit h;
+    h.t = (RULE == 0) ? FLT_MAX : 999999.0f;
+    h.tri = -1;
+#pragma unroll
+    for (int g = 0; g < kRenderCullWords; ++g) {
+        uint64_t w = cm[g];
+        while (w != 0ull) {
+            const int i = 64 * g + __builtin_ctzll(w);
+            w &= w - 1ull;
+            exact_one_c<RULE>(tri, i, o, nDx, nDy, nDz, h);
+        }
+    }
+    return h;
+}
+
 // wave_candidates from the launch's precomputed forms (k_cull_forms; rt_cull.hpp's two halves),
 // for k_render_ps and k_cull_ps: a wave with at least one valid pixel whose lane 0 holds pixel
 // q (index in the 16x16 block, wave-uniform) and whose lanes hold 64 >> split_log2 consecutive

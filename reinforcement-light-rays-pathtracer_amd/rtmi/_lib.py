@@ -49,6 +49,11 @@ RT_SARSA_KNN_MAX = 8
 RT_IRR_MEAN = 0
 RT_IRR_CONE = 1
 RT_DQN_VIEW_IRRADIANCE = 0
+RT_GLYPH_MAX = 256
+RT_GLYPH_SECTORS = 144
+RT_GLYPH_TRIS = 288
+RT_GLYPH_RATIO = 0
+RT_GLYPH_MAGNITUDE = 1
 
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -81,6 +86,8 @@ EXPORTS = (
     "rt_sarsa_write", "rt_sarsa_bake",
     "rt_sarsa_knn_reach", "rt_sarsa_knn", "rt_render_irradiance", "rt_render_irradiance_tiles_device",
     "rt_rect_candidates_forms",
+    "rt_selected_read", "rt_glyph_mesh", "rt_glyph_colours", "rt_glyphs_create", "rt_glyphs_create_sized", "rt_glyphs_destroy",
+    "rt_glyphs_set_colours", "rt_glyphs_info", "rt_render_glyph_view", "rt_render_glyph_view_tiles_device",
 )
 
 
@@ -107,6 +114,10 @@ class RtIrrOpts(ctypes.Structure):
 
 class RtDqnViewOpts(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int32), ("tint", ctypes.c_int32)]
+
+
+class RtGlyphViewOpts(ctypes.Structure):
+    _fields_ = [("shade", ctypes.c_int32)]
 
 
 class RtError(RuntimeError):
@@ -247,6 +258,19 @@ def _declare(lib):
                                      ctypes.POINTER(RtIrrOpts), ctypes.c_uint32, _FP, _IP, _FP, _IP, _FP]),
         "rt_render_irradiance_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
                                                   ctypes.POINTER(RtIrrOpts), ctypes.c_uint32, _IP, i, i, _P, _P]),
+        "rt_selected_read": (i, [ctypes.c_char_p, _IP, _FP, _FP, _FP]),
+        "rt_glyph_mesh": (i, [_FP, _FP, ctypes.c_int32, f, _FP, _FP]),
+        "rt_glyph_colours": (i, [_FP, ctypes.c_int32, i, _FP]),
+        "rt_glyphs_create": (i, [_P, _FP, _FP, _FP, ctypes.c_int32, f, i, ctypes.POINTER(_P)]),
+        "rt_glyphs_create_sized": (i, [_P, _FP, _FP, _FP, _FP, ctypes.c_int32, i, ctypes.POINTER(_P)]),
+        "rt_glyphs_destroy": (i, [_P]),
+        "rt_glyphs_set_colours": (i, [_P, _FP]),
+        "rt_glyphs_info": (i, [_P, _IP, _IP, _IP]),
+        "rt_render_glyph_view": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                     ctypes.POINTER(RtGlyphViewOpts), ctypes.c_uint32, _FP, _FP, _IP, _IP, _IP, _FP]),
+        "rt_render_glyph_view_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
+                                                  ctypes.POINTER(RtGlyphViewOpts), ctypes.c_uint32, _P, _IP, i, i,
+                                                  _P, _P]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),
