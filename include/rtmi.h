@@ -668,6 +668,42 @@ int rt_sarsa_write(rt_sarsa* sarsa, int v0, int n, const float* q /* n x 144 */,
  * RT_OK; max_bounces = 1 gives the floor everywhere and 0 casts. */
 int rt_sarsa_bake(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa, const rt_params* params, int v0,
                   int n, uint32_t first_sample, uint64_t* out_casts /* may be NULL */, void* stream);
+/* An expected-value sweep of the volumes [v0, v0 + n), on the device (k_sweep, csrc/rt_sweep.hip):
+ * the Expected-SARSA target of a sector is one cast long, and evaluated from every volume's own
+ * position instead of along camera paths it is value iteration over the map -- every sector of
+ * every volume visited equally, no pixels, and light travels one bounce further per sweep.  For
+ * volume v, sector k and sample s in [first_sample, first_sample + params->spp):
+ *   the first ray of rt_sarsa_bake's (v, k, s): Philox counter (v * 144 + k, s, 1, 73),
+ *     grid_direction in the surface's shading frame, o = pos + dir * 1e-5f, d = normalize(dir);
+ *   one closest hit under params->hit_rule and params->t_scale (the bake's cast routes);
+ *   target (float32, as the render's TD event forms it, brdf = vol_brdf[v] = the surface's
+ *     luminance / pi):  brdf * env_light for a miss, brdf * the light's luminance for a light,
+ *     (irradiance[u] * (2 pi / 144)) * brdf for a surface, u = the nearest volume the render
+ *     finds for the hit point o + t * (d * t_scale) with the hit surface's stored normal (the
+ *     map's search mode; volume 0 where no volume has that normal);
+ *   llrint(target * 2^32) joins the sector's pending TD sum and 1 its pending count: the
+ *     accumulators a tile render leaves with apply = 0 (rt_sarsa_td_device).
+ * The sweep reads only the irradiance estimates as they stand when it starts (Jacobi: it never
+ * sees its own results) and writes only the pending sums and counts of its range.  apply != 0
+ * then runs rt_sarsa_apply on the stream: the running mean with alpha = 1 / (1 + visits), the
+ * RADIANCE_THRESHOLD floor, the irradiance increments and the CDFs.  A sector always receives
+ * exactly spp targets: spp_split, max_bounces, sampler, width and height are ignored.  A volume's
+ * deposit depends on neither v0, n, the kernel's chunking, the cast route nor the search mode.
+ * `scene` is the scene the map was made for.  Asynchronous on `stream` unless out_casts
+ * (n * 144 * spp, host) is given.  Refused as rt_sarsa_bake refuses (a range outside the map,
+ * spp <= 0, a bad hit_rule: RT_E_INVALID; a preset other than RT_PRESET_GPU: RT_E_UNSUPPORTED),
+ * and RT_E_UNSUPPORTED unless the map's TD mode is RT_SARSA_TD_FRAME; the map is then untouched.
+ * n = 0 deposits nothing and is RT_OK. */
+int rt_sarsa_sweep(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sarsa, const rt_params* params, int v0,
+                   int n, uint32_t first_sample, int apply, uint64_t* out_casts /* may be NULL */,
+                   void* stream);
+/* visits[v][k] = 0 for the volumes [v0, v0 + n), nothing else (stream-ordered).  The next applied
+ * targets then replace Q instead of joining its mean, (Q * 0 + sum) / (0 + n): forget + sweep is
+ * a pure Jacobi step, sweep alone averages with what the map knows.  On several GPUs every rank
+ * forgets the whole swept range, sweeps its own slice with apply = 0, the sums are all-reduced and
+ * every rank applies (rtmi.dist.sarsa_sweep): a separate entry so that this stays bit-identical
+ * across ranks.  RT_E_INVALID for a range outside the map; n = 0 is RT_OK. */
+int rt_sarsa_forget(rt_sarsa* sarsa, int v0, int n, void* stream);
 /* RadianceMap::find_closest_radiance_volume_iterative (radiance_map.cu:149-203), n queries. */
 int rt_sarsa_nearest(rt_ctx* ctx, const rt_sarsa* sarsa, const float* pos, const float* normal,
                      int n, int32_t* out);
@@ -1021,7 +1057,7 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 #define RT_KT_SARSA_VIEW 7    /* k_sarsa_view: the radiance-map view (rt_render_volume_view); k_glyph_view (rt_render_glyph_view) */
 #define RT_KT_SARSA_NEAREST 8 /* k_sarsa_nearest: rt_sarsa_nearest's queries (without its copies) */
 #define RT_KT_PROBE 9         /* k_probe: rt_probe_radiance's paths (without its fold) */
-#define RT_KT_BAKE 10         /* k_bake: rt_sarsa_bake's paths (without its finish) */
+#define RT_KT_BAKE 10         /* k_bake: rt_sarsa_bake's paths (without its finish); k_sweep: rt_sarsa_sweep (without its apply) */
 #define RT_KT_COUNT 11
 int rt_ktime_enable(int on);
 int rt_ktime_read(int kernel, double* total_ms, int64_t* launches);

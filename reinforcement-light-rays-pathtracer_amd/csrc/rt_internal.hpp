@@ -25,7 +25,7 @@ enum KtimeKernel {
     KT_SARSA_VIEW = 7,  // k_sarsa_view (the radiance-map view), k_glyph_view (the glyph view)
     KT_SARSA_NEAREST = 8,  // k_sarsa_nearest (rt_sarsa_nearest's queries)
     KT_PROBE = 9,  // k_probe (rt_probe_radiance)
-    KT_BAKE = 10,  // k_bake (rt_sarsa_bake's paths, without its finish)
+    KT_BAKE = 10,  // k_bake (rt_sarsa_bake's paths, without its finish), k_sweep (rt_sarsa_sweep, without its apply)
     KT_COUNT = 11
 };
 struct KernelTimer {
@@ -487,6 +487,12 @@ struct SarsaBakeView {
     const int32_t* vol_surf = nullptr;  // [n_vol] the surface each volume lies on
     float* csum = nullptr;              // the chunk-sum workspace
     unsigned long long* work = nullptr;  // [2] the queue's counter, the casts
+};
+// rt_sarsa_sweep (rt_sweep.hip) works on a map through this view (rt_sarsa_host.cpp: sarsa_sweep_view)
+struct SarsaSweepView {
+    SarsaMap m;
+    const int32_t* vol_surf = nullptr;    // [n_vol] the surface each volume lies on
+    unsigned long long* casts = nullptr;  // [1] the casts
 };
 hipError_t launch_sarsa_nearest(const SarsaMap& m, const float* pos, const float* nrm, int n, int32_t* out,
                                 hipStream_t stream);

@@ -644,6 +644,22 @@ int sarsa_bake_view(rt_sarsa* sa, size_t floats, SarsaBakeView* out) {
     return RT_OK;
 }
 
+// rt_sweep.hip's view of a map: its device arrays, the volumes' surfaces and the cast counter
+// (rt_sarsa_bake's second word: launches of one map share it in stream order).  A sweep deposits
+// into the frame-synchronous pending sums, so the map must be in RT_SARSA_TD_FRAME.
+int sarsa_sweep_view(rt_sarsa* sa, SarsaSweepView* out) {
+    if (sa->m.td_off || sa->m.td_inframe)
+        return err(RT_E_UNSUPPORTED, std::string("rt_sarsa_sweep deposits into the pending TD sums of RT_SARSA_TD_FRAME; the map is in ") +
+                                         (sa->m.td_off ? "RT_SARSA_TD_OFF" : "RT_SARSA_TD_INFRAME"));
+    SarsaBakeView b;
+    const int rc = sarsa_bake_view(sa, 0, &b);
+    if (rc != RT_OK) return rc;
+    out->m = b.m;
+    out->vol_surf = b.vol_surf;
+    out->casts = b.work + 1;
+    return RT_OK;
+}
+
 int sarsa_n_volumes(const rt_sarsa* sa) { return sa->n_vol; }
 int sarsa_device(const rt_sarsa* sa) { return sa->device; }
 
@@ -1276,6 +1292,19 @@ int rt_sarsa_apply(rt_sarsa* sa, void* stream) {
     if (!sa) return err(RT_E_INVALID, "NULL argument");
     RT_HIPE(hipSetDevice(sa->device));
     RT_HIPE(rt::launch_sarsa_apply(sa->m, (hipStream_t)stream));
+    return RT_OK;
+}
+
+int rt_sarsa_forget(rt_sarsa* sa, int v0, int n, void* stream) {
+    if (!sa) return err(RT_E_INVALID, "sarsa is NULL");
+    if (n < 0) return err(RT_E_INVALID, "n < 0 (got " + std::to_string(n) + ")");
+    if (v0 < 0 || n > sa->n_vol - v0)
+        return err(RT_E_INVALID, "volumes [" + std::to_string(v0) + ", " + std::to_string((long long)v0 + n) +
+                                     ") outside the map's [0, " + std::to_string(sa->n_vol) + ")");
+    if (n == 0) return RT_OK;
+    RT_HIPE(hipSetDevice(sa->device));
+    RT_HIPE(hipMemsetAsync(sa->m.visits + (size_t)v0 * rt::kSarsaSectors, 0,
+                           sizeof(uint32_t) * (size_t)n * rt::kSarsaSectors, (hipStream_t)stream));
     return RT_OK;
 }
 

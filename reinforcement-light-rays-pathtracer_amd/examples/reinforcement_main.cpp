@@ -19,6 +19,10 @@
 //     (the CPU engine's irradiance render of the map, draw_radiance_map_path_tracing: the map
 //      filled from ground truth, bake_spp paths per sector, then each camera hit drawn as the
 //      average estimate of its k closest volumes; one sample per frame, the last frame is saved)
+//   ./build/reinforcement_demo sweep <scene.obj> <kind> [frames] [spp] [out.bmp] [width height] [sweeps] [sweep_spp]
+//     (value iteration over the radiance map, rt_sarsa_sweep: `sweeps` sweeps of sweep_spp casts
+//      per sector, each with fresh samples and averaged with the ones before, then frames rendered
+//      from the frozen map; the last frame is saved)
 //   (kind: 1 door_room, 2 archway, 3 complex_light_room; scene "cornell" = the Cornell box)
 #include <stdio.h>
 #include <stdlib.h>
@@ -47,7 +51,7 @@ static vec4 camera_for(int kind) {  // GPU/main.cu:100-104
 
 int main(int argc, char** argv) {
     if (argc < 4) {
-        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi|importance|irradiance <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
+        fprintf(stderr, "usage: %s sarsa|dqn|neuralq|voronoi|importance|irradiance|sweep <scene.obj|cornell> <kind> [model] [frames] [spp] [out.bmp]\n", argv[0]);
         return 2;
     }
     const bool nq = strcmp(argv[1], "neuralq") == 0;
@@ -61,10 +65,13 @@ int main(int argc, char** argv) {
     const char* out = argc > a ? argv[a++] : "render.bmp";
     const bool importance = strcmp(argv[1], "importance") == 0;
     const bool irradiance = strcmp(argv[1], "irradiance") == 0;  // (its spp argument is bake_spp)
-    const bool sized = (voronoi || importance || irradiance) && argc > a + 1;
+    const bool sweep = strcmp(argv[1], "sweep") == 0;
+    const bool sized = (voronoi || importance || irradiance || sweep) && argc > a + 1;
     const int width = sized ? atoi(argv[a]) : 512;
     const int height = sized ? atoi(argv[a + 1]) : 512;
     const int bake_spp = (importance && argc > a + 2) ? atoi(argv[a + 2]) : 64;
+    const int sweeps = (sweep && argc > a + 2) ? atoi(argv[a + 2]) : 7;
+    const int sweep_spp = (sweep && argc > a + 3) ? atoi(argv[a + 3]) : 8;
     const int query_count = (irradiance && argc > a + 2) ? atoi(argv[a + 2]) : 3;
     if (width <= 0 || height <= 0) {
         fprintf(stderr, "bad screen size %d x %d\n", width, height);
@@ -106,6 +113,18 @@ int main(int argc, char** argv) {
             for (int f = 0; f < frames; ++f) {
                 const uint64_t casts = draw_importance_sampling_path_tracing(screen, camera, map, scene, spp);
                 printf("frame %d: importance sampling, average path length %.3f\n", f,
+                       (double)casts / ((double)screen.width * screen.height * spp));
+            }
+        } else if (sweep) {
+            RadianceMap map(ds);
+            printf("radiance volumes: %d (KD array %d)\n", map.radiance_volumes_count, map.radiance_array_size);
+            for (int k = 0; k < sweeps; ++k) {
+                const uint64_t casts = map.sweep(sweep_spp, (uint32_t)(k * sweep_spp), true, height);
+                printf("sweep %d: %d casts per sector, %llu ray casts\n", k, sweep_spp, (unsigned long long)casts);
+            }
+            for (int f = 0; f < frames; ++f) {
+                const uint64_t casts = draw_importance_sampling_path_tracing(screen, camera, map, scene, spp);
+                printf("frame %d: swept map, average path length %.3f\n", f,
                        (double)casts / ((double)screen.width * screen.height * spp));
             }
         } else if (irradiance) {

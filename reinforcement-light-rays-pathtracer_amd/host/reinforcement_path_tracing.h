@@ -117,6 +117,24 @@ class RadianceMap {
                                     nullptr));
         return casts;
     }
+    // One expected-value sweep of every volume (rt_sarsa_sweep): per sector `spp` single casts from
+    // the volume's own position, samples first_sample .. first_sample + spp - 1, each depositing
+    // the Expected-SARSA target -- the light, or the map's irradiance estimate where the cast
+    // lands -- then folded into Q as a frame's targets are (apply).  Value iteration over the map:
+    // light travels one bounce further per sweep.  Returns the ray casts.
+    uint64_t sweep(int spp = 8, uint32_t first_sample = 0, bool apply = true, int screen_height = 720) {
+        rt_params p;
+        rt_params_default(RT_PRESET_GPU, &p);
+        p.t_scale = (float)screen_height;
+        p.spp = spp;
+        uint64_t casts = 0;
+        detail::check(rt_sarsa_sweep(ds_.ctx(), ds_.scene(), map_, &p, 0, radiance_volumes_count, first_sample,
+                                     apply ? 1 : 0, &casts, nullptr));
+        return casts;
+    }
+    // visits = 0 everywhere (rt_sarsa_forget): the next sweep's targets replace Q instead of
+    // joining its running mean, forget() + sweep() is a pure Jacobi step
+    void forget() { detail::check(rt_sarsa_forget(map_, 0, radiance_volumes_count, nullptr)); }
     // RadianceTree::find_closest_radiance_volumes (Old_CPU_Rendering_Engine/Source/radiance_volumes/
     // radiance_tree.cpp:111-177) on the device (rt_sarsa_knn): the up to n volumes with this normal
     // closer than max_dist to position, nearest first (equal distances by index), as volume indices.

@@ -83,7 +83,7 @@ EXPORTS = (
     "rt_qtable_read", "rt_dqn_fit_order", "rt_dqn_fit_step_device", "rt_dqn_fit_loss_device", "rt_dqn_fit_error_device",
     "rt_dqn_fit_create", "rt_dqn_fit_destroy", "rt_dqn_fit_info", "rt_dqn_fit_epoch",
     "rt_probe_radiance", "rt_probe_radiance_device",
-    "rt_sarsa_write", "rt_sarsa_bake",
+    "rt_sarsa_write", "rt_sarsa_bake", "rt_sarsa_sweep", "rt_sarsa_forget",
     "rt_sarsa_knn_reach", "rt_sarsa_knn", "rt_render_irradiance", "rt_render_irradiance_tiles_device",
     "rt_rect_candidates_forms",
     "rt_selected_read", "rt_glyph_mesh", "rt_glyph_colours", "rt_glyphs_create", "rt_glyphs_create_sized", "rt_glyphs_destroy",
@@ -252,6 +252,8 @@ def _declare(lib):
                                          _P, _P]),
         "rt_sarsa_write": (i, [_P, i, i, _FP, _UP]),
         "rt_sarsa_bake": (i, [_P, _P, _P, ctypes.POINTER(RtParams), i, i, ctypes.c_uint32, _U64P, _P]),
+        "rt_sarsa_sweep": (i, [_P, _P, _P, ctypes.POINTER(RtParams), i, i, ctypes.c_uint32, i, _U64P, _P]),
+        "rt_sarsa_forget": (i, [_P, i, i, _P]),
         "rt_sarsa_knn_reach": (i, [_P, _FP]),
         "rt_sarsa_knn": (i, [_P, _P, _FP, _FP, i, i, f, _IP, _FP, _IP]),
         "rt_render_irradiance": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),

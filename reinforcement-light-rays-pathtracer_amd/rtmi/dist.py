@@ -116,3 +116,33 @@ def sarsa_frame(radiance_map, cam, params, tiles, n_real: int, tile_size: int, o
         ts, tc = td if td is not None else td_tensors(radiance_map, out.device)
         sum_td(ts, tc)
         radiance_map.apply(stream)
+
+
+def sweep_slice(n_volumes: int, rank: int, world: int):
+    """(v0, n) of rank's contiguous slice of [0, n_volumes): the first n_volumes % world ranks
+    take one volume more."""
+    base, extra = divmod(n_volumes, world)
+    return rank * base + min(rank, extra), base + (1 if rank < extra else 0)
+
+
+def sarsa_sweep(radiance_map, scene, params, first_sample: int = 0, replace: bool = False, device=None,
+                td=None) -> int:
+    """One expected-value sweep of the whole map over the ranks (RadianceMap.sweep): every rank
+    forgets the whole map when `replace` is set, sweeps its contiguous slice of the volumes with
+    apply=False, the pending sums are all-reduced (sum_td) and every rank applies -- integer sums,
+    so every rank's map is bit-identical to the single-GPU sweep's.  World size 1: the plain call.
+    Returns this rank's casts."""
+    world = dist.get_world_size() if dist.is_initialized() else 1
+    if replace:
+        radiance_map.forget()
+    if world == 1:
+        return radiance_map.sweep(scene, params, first_sample=first_sample, apply=True)
+    v0, n = sweep_slice(radiance_map.n_volumes, dist.get_rank(), world)
+    casts = radiance_map.sweep(scene, params, v0, n, first_sample, apply=False)
+    if td is None:
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        td = td_tensors(radiance_map, device)
+    sum_td(*td)
+    radiance_map.apply(0)
+    return casts

@@ -14,6 +14,9 @@
   .set_td_mode(TD_OFF)            render from the map as it stands, learning nothing
   .bake(scene, params, v0, n)     fill volumes from ground truth on the device (rt_sarsa_bake)
   .write(q, visits, v0)           Q rows (and visits) from host arrays into the map (rt_sarsa_write)
+  .sweep(scene, params, v0, n)    one expected-value sweep: the TD target of every sector from the volume's
+                                  own position, value iteration over the map (rt_sarsa_sweep)
+  .forget(v0, n)                  visits = 0: the next applied targets replace Q (rt_sarsa_forget)
   .frame_stats() / .append_stats_line(path)   sarsa_training_stats.txt (GPU/main.cu:321-339)
   .view(cam, params, first_sample, aov) / .view_tiles_device(...)   the Voronoi view (GPU/main.cu
                                   method 2): each camera hit in its nearest volume's colour
@@ -186,6 +189,27 @@ class RadianceMap:
         check(lib().rt_sarsa_bake(self.ctx.handle, scene.handle, self._h, ctypes.byref(params), int(v0), int(n),
                                   int(first_sample), ctypes.byref(casts), None))
         return int(casts.value)
+
+    def sweep(self, scene: Scene, params, v0: int = 0, n: int | None = None, first_sample: int = 0,
+              apply: bool = True) -> int:
+        """One expected-value sweep of the volumes [v0, v0 + n) (n None: to the end of the map): per
+        sector params.spp single casts from the volume's own position, each depositing the
+        Expected-SARSA target (the light, or the map's irradiance estimate where the cast lands)
+        into the pending TD sums; apply folds them into Q as a frame's are (rt_sarsa_sweep).  The
+        map must be in TD_FRAME.  Returns the casts, n * 144 * spp."""
+        if n is None:
+            n = self.n_volumes - int(v0)
+        casts = ctypes.c_uint64(0)
+        check(lib().rt_sarsa_sweep(self.ctx.handle, scene.handle, self._h, ctypes.byref(params), int(v0), int(n),
+                                   int(first_sample), int(bool(apply)), ctypes.byref(casts), None))
+        return int(casts.value)
+
+    def forget(self, v0: int = 0, n: int | None = None) -> None:
+        """visits = 0 for the volumes [v0, v0 + n), nothing else: the next applied targets replace Q
+        instead of joining its running mean (rt_sarsa_forget).  forget + sweep is a Jacobi step."""
+        if n is None:
+            n = self.n_volumes - int(v0)
+        check(lib().rt_sarsa_forget(self._h, int(v0), int(n), None))
 
     def nearest(self, pos: np.ndarray, nrm: np.ndarray) -> np.ndarray:
         p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
