@@ -388,6 +388,10 @@ class Sarsa:
         L.orc_sarsa_sample_stats.argtypes = [VP] + [ctypes.POINTER(ctypes.c_uint64)] * 3
         L.orc_sarsa_stats.argtypes = [VP, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
         L.orc_sarsa_load_q.argtypes = [VP, _FP]
+        L.orc_sarsa_search_stats.argtypes = [VP] + [ctypes.POINTER(ctypes.c_uint64)] * 2
+        L.orc_sarsa_set_visits.argtypes = [VP, ctypes.POINTER(ctypes.c_uint32)]
+        L.orc_sarsa_set_pending.argtypes = [VP, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_uint32)]
+        L.orc_sarsa_apply.argtypes = [VP]
         L.orc_sarsa_td_rect.argtypes = [VP, ctypes.POINTER(OrcCamera), ctypes.POINTER(OrcParams), ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                         ctypes.POINTER(ctypes.c_uint32)]
@@ -460,6 +464,27 @@ class Sarsa:
     def load_q(self, q):
         q = np.ascontiguousarray(q, np.float32).reshape(self.n_volumes, 144)
         self._L.orc_sarsa_load_q(self._h, _f(q))
+
+    def search_stats(self):
+        """last frame: (CDF samples whose draw equals some entry of the sampled row -- ties --,
+        searches in which a probe met cdf[mid] == r)"""
+        v = [ctypes.c_uint64(0) for _ in range(2)]
+        self._L.orc_sarsa_search_stats(self._h, *[ctypes.byref(x) for x in v])
+        return tuple(int(x.value) for x in v)
+
+    def set_visits(self, visits):
+        """the visit counts (n_volumes, 144), as RadianceMap.write's visits"""
+        vis = np.ascontiguousarray(visits, np.uint32).reshape(self.n_volumes, 144)
+        self._L.orc_sarsa_set_visits(self._h, vis.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+
+    def apply_pending(self, sums, counts):
+        """The fold of a frame's end on given pending TD sums (int64, fixed point 2^-32) and counts
+        (uint32), each (n_volumes, 144): what rtmi.dist.td_tensors + RadianceMap.apply() do."""
+        s = np.ascontiguousarray(sums, np.int64).reshape(self.n_volumes, 144)
+        c = np.ascontiguousarray(counts, np.uint32).reshape(self.n_volumes, 144)
+        self._L.orc_sarsa_set_pending(self._h, s.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                      c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        self._L.orc_sarsa_apply(self._h)
 
     def td_rect(self, cam: OrcCamera, params: OrcParams, rect):
         """(int64 sums, uint32 counts), each (n_volumes * 144,): the TD accumulators that the

@@ -1247,6 +1247,8 @@ typedef struct {
     uint64_t stat_paths, stat_zero; /* last frame: sum of per-pixel floor(path length mean), zero paths */
     uint64_t stat_null, stat_sector0, stat_cdf; /* last frame: failed CDF samples (null rays), CDF samples
                                                    that chose sector 0, all CDF samples */
+    uint64_t stat_tie, stat_eqprobe; /* last frame: CDF samples whose draw equals an entry of the sampled
+                                        row, searches in which a probe met cdf[mid] == r */
     /* scene (copied) */
     int n_surf, n_light;
     float *tri, *albedo, *emission, *normal;
@@ -1505,12 +1507,15 @@ ORC_API void orc_sarsa_nearest(const orc_sarsa *m, const float *pos, const float
 }
 
 /* sample_direction_from_radiance_distribution: 0 = no sector found */
-static int sarsa_sample(const orc_sarsa *m, int rv, float r, float rx, float ry, int *sector, v3 *dir, float *pdf) {
+static int sarsa_sample(orc_sarsa *m, int rv, float r, float rx, float ry, int *sector, v3 *dir, float *pdf) {
     const float *cdf = m->cdf + (size_t)rv * 144;
     const float RHO = 1.0f / (2.0f * 3.1415926535f);
     const float GRID_RHO = 1.0f / (12.0f * 12.0f);
     int found = -1;
     float dv = 0.0f;
+    /* instrumentation only (orc_sarsa_search_stats): the draw equals an entry of the row */
+    int tie = 0, eq_probe = 0;
+    for (int k = 0; k < 144; k++) tie |= cdf[k] == r;
     if (r <= cdf[0]) {
         found = 0;
         dv = cdf[0];
@@ -1519,10 +1524,19 @@ static int sarsa_sample(const orc_sarsa *m, int rv, float r, float rx, float ry,
         while (start <= end) {
             int mid = (end + start) / 2;
             float mv = cdf[mid], pv = mid > 0 ? cdf[mid - 1] : 0.0f;
+            eq_probe |= mv == r;
             if (r < mv && pv <= r) { found = mid; dv = mv - pv; break; }
             else if (mv < r) start = mid + 1;
             else end = mid - 1;
         }
+    }
+    if (tie) {
+        #pragma omp atomic
+        m->stat_tie += 1u;
+    }
+    if (eq_probe) {
+        #pragma omp atomic
+        m->stat_eqprobe += 1u;
     }
     if (found < 0) return 0;
     int sx = found / 12, sy = found - sx * 12;
@@ -1588,6 +1602,13 @@ static void td_inframe(orc_sarsa *m, int rv, int sector, float target) {
     float cc = m->ck[k], brdf = m->brdf[rv];
     m->accum[rv] = (m->accum[rv] - ((q_old * cc) * brdf)) + ((upd * cc) * brdf);
     m->Q[k] = upd;
+}
+
+/* more instrumentation of the last frame's CDF samples: those whose draw equals some entry of
+ * the sampled row (ties), and the searches in which a probe met cdf[mid] == r */
+ORC_API void orc_sarsa_search_stats(const orc_sarsa *m, uint64_t *ties, uint64_t *equal_probes) {
+    *ties = m->stat_tie;
+    *equal_probes = m->stat_eqprobe;
 }
 
 ORC_API void orc_sarsa_set_td_mode(orc_sarsa *m, int mode) { m->inframe = mode == 1; }
@@ -1738,6 +1759,19 @@ static void sarsa_apply(orc_sarsa *m) {
     }
 }
 
+/* The fold on host arrays (rt_sarsa_write's visits, the pending sums and counts of
+ * rt_sarsa_td_device, rt_sarsa_apply): visits, sums, counts are n_vol x 144 */
+ORC_API void orc_sarsa_set_visits(orc_sarsa *m, const uint32_t *visits) {
+    memcpy(m->visits, visits, sizeof(uint32_t) * (size_t)m->n_vol * 144);
+}
+
+ORC_API void orc_sarsa_set_pending(orc_sarsa *m, const int64_t *sums, const uint32_t *counts) {
+    memcpy(m->sum, sums, sizeof(int64_t) * (size_t)m->n_vol * 144);
+    memcpy(m->cnt, counts, sizeof(uint32_t) * (size_t)m->n_vol * 144);
+}
+
+ORC_API void orc_sarsa_apply(orc_sarsa *m) { sarsa_apply(m); }
+
 /* Q-table loader (rt_sarsa_load_q): Q from radiance_map_data.txt values, the irradiance
  * estimate of initialise_radiance_grid (radiance_volume.cu:46-63) over that Q, the CDF of
  * update_radiance_distribution; visits kept. */
@@ -1806,6 +1840,7 @@ static uint64_t sarsa_frame_rect(orc_sarsa *m, const orc_camera *cam, const orc_
     int per = p->spp / S;
     uint32_t base = m->frames * (uint32_t)p->spp;
     m->stat_null = m->stat_sector0 = m->stat_cdf = 0;
+    m->stat_tie = m->stat_eqprobe = 0;
     /* in-frame TD: one thread, pixels row by row, each pixel's chunks and samples in order */
     #pragma omp parallel for schedule(dynamic, 1) reduction(+:total, paths, zero) if(!m->inframe)
     for (int py = y0; py < y0 + h; py++) {
