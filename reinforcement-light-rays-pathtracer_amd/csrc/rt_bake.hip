@@ -16,33 +16,28 @@
 // The frame: a volume's sectors are laid out in normal_frame(N) of its surface normal N
 // (rt_sarsa_host.cpp, rt_sarsa_create_density), the probe's in the scene's shading frame of the
 // surface (rt_capi.cpp: normal_frame of the same stored normal), both with sector k = x * 12 + y
-// through grid_direction: the probe's sector k is the volume's sector k, and k_bake reads the
-// scene's frame as k_probe does.
+// through grid_direction: the probe's sector k is the volume's sector k, and both read the
+// scene's frame.
 //
-// k_bake: k_probe's persistent grid over the launch-wide queue of (volume, sector, chunk) items
-// (a wave claims 64 items per atomic and hands them to its lanes by ballot rank) and its cast
-// routes (the bounce-ray candidate table, the exact BVH, else the filter or the scan: the same
-// hit, bit for bit).  Unlike the probe it keeps three chunk sums per item, not six, writes no
-// rad / irr / dir arrays, and the result stays on the device: k_bake_fold (one lane per sector:
-// fold, luminance, floor, visits), k_bake_irradiance (one lane per volume) and the ranged
-// rebuild.  The entry walks its range in batches of a bounded chunk-sum workspace; a volume's
-// result depends on neither the batching, v0, n nor the route.
+// k_bake: a persistent grid over the launch-wide queue of (volume, sector, chunk) items (a wave
+// claims 64 items per atomic and hands them to its lanes by ballot rank).  The sample's first ray
+// (sector_first_ray), the cast on the route the host picked (closest_hit_route; leaving_route in
+// rt_capi.cpp: the same hit, bit for bit, on each) and the preset's bounce (surface_step) are
+// rt_paths.hpp's, shared with k_probe and k_sweep.  It keeps three chunk sums per item, reads
+// positions and surfaces from the map, writes no rad / irr / dir arrays, and the result
+// stays on the device: k_bake_fold (one lane per sector: fold, luminance, floor, visits),
+// k_bake_irradiance (one lane per volume) and the ranged rebuild.  The entry walks its range in
+// batches of a bounded chunk-sum workspace; a volume's result depends on neither the batching,
+// v0, n nor the route.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <algorithm>
 
-#include "../../include/rtmi.h"
-#include "rt_trace.hpp"
+#include "rt_paths.hpp"
 
 namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
-DeviceScene scene_launch_view(const rt_scene* s);
-int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
 int sarsa_bake_view(rt_sarsa* sa, size_t floats, SarsaBakeView* out);
 int sarsa_n_volumes(const rt_sarsa* sa);
 int sarsa_device(const rt_sarsa* sa);
@@ -51,14 +46,11 @@ int sarsa_device(const rt_sarsa* sa);
 namespace rt {
 namespace {
 
-static_assert(kSarsaSectors == kDqnActions && kSarsaSectors == kDqnGrid * kDqnGrid && kDqnGrid == kGridRes,
-              "the map's sectors are the sampler's 12 x 12 cells");
-static_assert(RT_PROBE_SECTORS == kSarsaSectors, "the probe's sectors");
+static_assert(kSarsaSectors == kDqnActions && kSarsaSectors == kDqnGrid * kDqnGrid && kDqnGrid == kGridRes, "the map's sectors are the sampler's 12 x 12 cells");
 // (volume * 144 + 143 fits 32 bits: maps hold at most 2^24 volumes, rt_sarsa_create_density)
 constexpr float kRadianceThreshold = (1.f / ((float)kGridRes * (float)kGridRes)) * 0.8f;  // RADIANCE_THRESHOLD
 constexpr size_t kBakeBatchFloats = (size_t)1 << 26;  // the chunk-sum workspace of one batch: 256 MiB
 
-constexpr int kRouteSel = 0, kRouteTable = 1, kRouteBvh = 2;
 // Waves per SIMD the launch bounds ask for: k_probe's (rt_probe.hip probe_waves), whose path
 // loop this is.  The table route's casts wait on two dependent lookups and gain from occupancy;
 // the scan and the BVH are bound by their own loops.
@@ -110,13 +102,8 @@ __global__ __launch_bounds__(256, bake_waves(ROUTE, RULE, NW)) void k_bake(const
         const float4 B4 = shade[tri0 * kShadeF4 + 2];
         const float4 P4 = a.vol_pos[vol];
         const f3 pos = make3(P4.x, P4.y, P4.z);
-        uint32_t w[4];
-        philox4x32_10(pix, s, 1u, 1u + kDqnActions / 2, a.seed_lo, a.seed_hi, w);
-        const int gx = sector / kDqnGrid, gy = sector - gx * kDqnGrid;
-        const f3 dir = grid_direction((float)gx + u01(w[0]), (float)gy + u01(w[1]), make3(N4.x, N4.y, N4.z),
-                                      make3(T4.x, T4.y, T4.z), make3(B4.x, B4.y, B4.z), pos);
-        o = make3(pos.x + dir.x * kEps, pos.y + dir.y * kEps, pos.z + dir.z * kEps);
-        d = normalize(dir);
+        sector_first_ray(pix, s, sector, make3(N4.x, N4.y, N4.z), make3(T4.x, T4.y, T4.z), make3(B4.x, B4.y, B4.z), pos,
+                         a.seed_lo, a.seed_hi, &o, &d);
         tp = make3(1.0f, 1.0f, 1.0f);
         depth = 1;
         surf = tri0;
@@ -181,19 +168,9 @@ __global__ __launch_bounds__(256, bake_waves(ROUTE, RULE, NW)) void k_bake(const
             if (exhausted) break;
             continue;  // (every claimed item ended without a cast)
         }
-        Hit h;
-        if constexpr (ROUTE == kRouteTable) {
-            h = closest_hit_ctab<RULE, NW>(a.scene, a.scene.ctab[RULE], surf, o, d, a.t_scale, active, wl);
-            if (!active) continue;
-        } else if constexpr (ROUTE == kRouteBvh) {
-            if (!active) continue;
-            h = closest_hit_bvh<RULE>(a.scene, o, d, a.t_scale, s_stk + threadIdx.x);
-        } else {
-            if (!active) continue;
-            // the filter's bounds hold for origins within origin_bound
-            const float om = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-            h = closest_hit_sel<RULE>(a.scene, a.use_filter && om <= a.scene.origin_bound, o, d, a.t_scale);
-        }
+        const Hit h = closest_hit_route<RULE, ROUTE, NW>(a.scene, a.use_filter, surf, o, d, a.t_scale, active, wl,
+                                                         ROUTE == kRouteBvh ? s_stk + threadIdx.x : nullptr);
+        if (!active) continue;
         ++n_casts;
         bool terminal = false;
         f3 L = make3(0.0f, 0.0f, 0.0f);
@@ -205,39 +182,7 @@ __global__ __launch_bounds__(256, bake_waves(ROUTE, RULE, NW)) void k_bake(const
             const float4 e = shade[h.tri * kShadeF4 + 3];
             L = make3(tp.x * e.x, tp.y * e.y, tp.z * e.z);
         } else {
-            // as k_render<1, ...> and k_probe: position, sample a direction, update the throughput
-            const float Dx = d.x * a.t_scale, Dy = d.y * a.t_scale, Dz = d.z * a.t_scale;
-            const f3 pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
-            const float4 N = shade[h.tri * kShadeF4 + 0];
-            const float4 T = shade[h.tri * kShadeF4 + 1];
-            const float4 B = shade[h.tri * kShadeF4 + 2];
-            float r1, r2;
-            draw2(pix, s, 1u + (uint32_t)depth, a.seed_lo, a.seed_hi, &r1, &r2);
-            float cos_theta, sin_theta;
-            if (SAMPLER == 0) {
-                cos_theta = r1;
-                sin_theta = sqrtf(1.0f - r1 * r1);
-            } else {
-                cos_theta = sqrtf(r1);
-                sin_theta = sqrtf(1.0f - r1);
-            }
-            float sphi, cphi;
-            sincos_turn(r2, &sphi, &cphi);
-            const float sx = sin_theta * cphi, sz = sin_theta * sphi;
-            const f3 sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x, (sx * B.y + cos_theta * N.y) + sz * T.y,
-                                (sx * B.z + cos_theta * N.z) + sz * T.z);
-            if (SAMPLER == 0) {
-                const float4 c = shade[h.tri * kShadeF4 + 3];
-                tp.x = div_rho((tp.x * c.x) * cos_theta);
-                tp.y = div_rho((tp.y * c.y) * cos_theta);
-                tp.z = div_rho((tp.z * c.z) * cos_theta);
-            } else {
-                const float4 c = shade[h.tri * kShadeF4 + 4];
-                tp = make3(tp.x * c.x, tp.y * c.y, tp.z * c.z);
-            }
-            o = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
-            d = normalize(sd);
-            surf = h.tri;
+            surf = surface_step<SAMPLER>(h, o, d, tp, a.t_scale, shade, pix, s, depth, a.seed_lo, a.seed_hi);
             ++depth;
             if (depth == a.max_bounces) terminal = true;  // loop exhausted -> 0
         }
@@ -329,15 +274,6 @@ hipError_t launch_bake(const BakeLaunch& a, const SarsaMap& m, int sampler, int 
     return launch_sarsa_rebuild_range(m, a.v0, a.n, stream);
 }
 
-int berr(int code, const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-
 }  // namespace
 }  // namespace rt
 
@@ -346,51 +282,34 @@ extern "C" {
 int rt_sarsa_bake(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_params* p, int v0, int n,
                   uint32_t first_sample, uint64_t* out_casts, void* stream_) {
     using namespace rt;
-    // rt_probe_radiance's conditions (rt_probe.hip check_probe), then the map's
-    if (!ctx) return berr(RT_E_INVALID, "ctx is NULL");
-    if (!scene) return berr(RT_E_INVALID, "scene is NULL");
-    if (!sa) return berr(RT_E_INVALID, "sarsa is NULL");
-    if (!p) return berr(RT_E_INVALID, "params is NULL");
-    if (n < 0) return berr(RT_E_INVALID, "n < 0 (got %d)", n);
-    if (p->spp <= 0) return berr(RT_E_INVALID, "spp must be > 0 (got %d)", p->spp);
+    if (ctx && scene && !sa) return errorf(RT_E_INVALID, "sarsa is NULL");  // (after ctx and scene, before params)
+    int rc = check_leaving_args(ctx, scene, p, n);
+    if (rc != RT_OK) return rc;
     const int split = p->spp_split <= 0 ? 1 : p->spp_split;
-    if (p->spp % split != 0) return berr(RT_E_INVALID, "spp_split %d does not divide spp %d", split, p->spp);
-    if (p->max_bounces < 1) return berr(RT_E_INVALID, "max_bounces must be >= 1 (got %d)", p->max_bounces);
+    if (p->spp % split != 0) return errorf(RT_E_INVALID, "spp_split %d does not divide spp %d", split, p->spp);
+    if (p->max_bounces < 1) return errorf(RT_E_INVALID, "max_bounces must be >= 1 (got %d)", p->max_bounces);
     if (p->sampler != RT_SAMPLER_UNIFORM && p->sampler != RT_SAMPLER_COSINE)
-        return berr(RT_E_INVALID, "bad sampler %d", p->sampler);
-    if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU)
-        return berr(RT_E_INVALID, "bad hit_rule %d", p->hit_rule);
+        return errorf(RT_E_INVALID, "bad sampler %d", p->sampler);
     if (p->preset != RT_PRESET_GPU)
-        return berr(RT_E_UNSUPPORTED, "rt_sarsa_bake follows the GPU-engine preset's path (got preset %d)", p->preset);
+        return errorf(RT_E_UNSUPPORTED, "rt_sarsa_bake follows the GPU-engine preset's path (got preset %d)", p->preset);
     const int n_vol = sarsa_n_volumes(sa);
     if (v0 < 0 || n > n_vol - v0)
-        return berr(RT_E_INVALID, "volumes [%d, %lld) outside the map's [0, %d)", v0, (long long)v0 + n, n_vol);
-    if (sarsa_device(sa) != ctx_device(ctx)) return berr(RT_E_INVALID, "radiance map belongs to another device");
+        return errorf(RT_E_INVALID, "volumes [%d, %lld) outside the map's [0, %d)", v0, (long long)v0 + n, n_vol);
+    if (sarsa_device(sa) != ctx_device(ctx)) return errorf(RT_E_INVALID, "radiance map belongs to another device");
     if (n == 0) {
         if (out_casts) *out_casts = 0;
         return RT_OK;
     }
     hipStream_t stream = (hipStream_t)stream_;
     hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return berr(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     BakeLaunch a;
-    a.scene = scene_launch_view(scene);
-    int route = a.scene.bvh_nodes != nullptr ? kRouteBvh : kRouteSel;
-    // every ray leaves a known surface: the bounce-ray candidate table, where the scene may have one
-    if (route == kRouteSel && a.scene.mf_frag != nullptr && a.scene.n_surf > 0 &&
-        a.scene.n_tri <= 64 * kCtabMaxWords && p->t_scale > 0.0f && p->t_scale <= kFiltMaxTScale) {
-        const int rc = scene_ensure_ctab(scene, p->hit_rule, p->t_scale, /*wanted=*/true);
-        if (rc != RT_OK) return rc;
-        a.scene = scene_launch_view(scene);
-        const CtabDev& T = a.scene.ctab[p->hit_rule];
-        if (T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze && p->t_scale >= T.ts_min &&
-            T.words <= (a.scene.n_tri <= 64 ? 1 : 4))
-            route = kRouteTable;
-    }
+    const int route = leaving_route(scene, p, &a.scene);
+    if (route < 0) return route;
     const size_t per_vol = (size_t)kSarsaSectors * (size_t)split * 3;
     const int batch = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, kBakeBatchFloats / per_vol));
     SarsaBakeView view;
-    const int rc = sarsa_bake_view(sa, (size_t)batch * per_vol, &view);
+    rc = sarsa_bake_view(sa, (size_t)batch * per_vol, &view);
     if (rc != RT_OK) return rc;
     a.vol_pos = view.m.vol_pos;
     a.vol_surf = view.vol_surf;
@@ -413,12 +332,12 @@ int rt_sarsa_bake(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_par
         a.n = std::min(batch, n - b0);
         e = launch_bake(a, view.m, p->sampler, p->hit_rule, route, stream);
     }
-    if (e != hipSuccess) return berr(RT_E_HIP, "rt_sarsa_bake: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_sarsa_bake: %s", hipGetErrorString(e));
     if (out_casts) {
         unsigned long long casts = 0;
         e = hipStreamSynchronize(stream);
         if (e == hipSuccess) e = hipMemcpy(&casts, a.casts, sizeof(casts), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return berr(RT_E_HIP, "rt_sarsa_bake: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return errorf(RT_E_HIP, "rt_sarsa_bake: %s", hipGetErrorString(e));
         *out_casts = casts;
     }
     return RT_OK;

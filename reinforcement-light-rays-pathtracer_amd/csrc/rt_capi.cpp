@@ -24,21 +24,13 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
+using rt::errorf;
 
 #define RT_HIP(expr)                                                                    \
     do {                                                                                \
         hipError_t e_ = (expr);                                                         \
         if (e_ != hipSuccess)                                                           \
-            return fail(RT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));       \
+            return errorf(RT_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));       \
     } while (0)
 
 }  // namespace
@@ -47,6 +39,24 @@ namespace rt {
 int set_error(int code, const char* msg) {
     g_err = msg;
     return code;
+}
+int errorf(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return set_error(code, buf);
+}
+int check_leaving_args(const rt_ctx* ctx, const rt_scene* scene, const rt_params* p, int n) {
+    if (!ctx) return errorf(RT_E_INVALID, "ctx is NULL");
+    if (!scene) return errorf(RT_E_INVALID, "scene is NULL");
+    if (!p) return errorf(RT_E_INVALID, "params is NULL");
+    if (n < 0) return errorf(RT_E_INVALID, "n < 0 (got %d)", n);
+    if (p->spp <= 0) return errorf(RT_E_INVALID, "spp must be > 0 (got %d)", p->spp);
+    if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU)
+        return errorf(RT_E_INVALID, "bad hit_rule %d", p->hit_rule);
+    return RT_OK;
 }
 }  // namespace rt
 
@@ -371,25 +381,25 @@ int rt::ensure_blocks_impl(rt_ctx* ctx, const std::vector<rt::BlockDesc>& blocks
 namespace {
 
 int check_params(const rt_params* p) {
-    if (!p) return fail(RT_E_INVALID, "params is NULL");
-    if (p->width <= 0 || p->height <= 0) return fail(RT_E_INVALID, "bad image size %dx%d", p->width, p->height);
-    if (p->spp <= 0) return fail(RT_E_INVALID, "spp must be > 0");
-    if (p->max_bounces < 0) return fail(RT_E_INVALID, "max_bounces must be >= 0");
-    if (p->preset != RT_PRESET_CPU && p->preset != RT_PRESET_GPU) return fail(RT_E_INVALID, "bad preset %d", p->preset);
+    if (!p) return errorf(RT_E_INVALID, "params is NULL");
+    if (p->width <= 0 || p->height <= 0) return errorf(RT_E_INVALID, "bad image size %dx%d", p->width, p->height);
+    if (p->spp <= 0) return errorf(RT_E_INVALID, "spp must be > 0");
+    if (p->max_bounces < 0) return errorf(RT_E_INVALID, "max_bounces must be >= 0");
+    if (p->preset != RT_PRESET_CPU && p->preset != RT_PRESET_GPU) return errorf(RT_E_INVALID, "bad preset %d", p->preset);
     if (p->sampler != RT_SAMPLER_UNIFORM && p->sampler != RT_SAMPLER_COSINE)
-        return fail(RT_E_INVALID, "bad sampler %d", p->sampler);
+        return errorf(RT_E_INVALID, "bad sampler %d", p->sampler);
     if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU)
-        return fail(RT_E_INVALID, "bad hit_rule %d", p->hit_rule);
+        return errorf(RT_E_INVALID, "bad hit_rule %d", p->hit_rule);
     if (p->preset == RT_PRESET_CPU && p->max_bounces > 2)
-        return fail(RT_E_UNSUPPORTED, "CPU preset supports max_bounces <= 2 (got %d)", p->max_bounces);
+        return errorf(RT_E_UNSUPPORTED, "CPU preset supports max_bounces <= 2 (got %d)", p->max_bounces);
     if (p->preset == RT_PRESET_GPU && p->max_bounces < 1)
-        return fail(RT_E_INVALID, "GPU preset needs max_bounces >= 1");
+        return errorf(RT_E_INVALID, "GPU preset needs max_bounces >= 1");
     const int split = p->spp_split <= 0 ? 1 : p->spp_split;
     if (split > 64 || (split & (split - 1)) != 0)
-        return fail(RT_E_INVALID, "spp_split must be a power of two <= 64 (got %d)", p->spp_split);
-    if (p->spp % split != 0) return fail(RT_E_INVALID, "spp_split %d does not divide spp %d", split, p->spp);
+        return errorf(RT_E_INVALID, "spp_split must be a power of two <= 64 (got %d)", p->spp_split);
+    if (p->spp % split != 0) return errorf(RT_E_INVALID, "spp_split %d does not divide spp %d", split, p->spp);
     if ((int64_t)p->width * (int64_t)p->height > (int64_t)1 << 31)
-        return fail(RT_E_INVALID, "image too large");
+        return errorf(RT_E_INVALID, "image too large");
     return RT_OK;
 }
 
@@ -489,6 +499,22 @@ int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wante
     sc->ctab_bytes[rule] = sizeof(uint64_t) * (ct.masks.size() + ct.gdict.size() + ct.cop.size()) +
                            sizeof(uint16_t) * ct.gid.size() + sizeof(float4) * ct.tri.size();
     return RT_OK;
+}
+
+int leaving_route(const rt_scene* scene, const rt_params* p, DeviceScene* launch_scene) {
+    DeviceScene& d = *launch_scene;
+    d = scene_launch_view(scene);
+    if (d.bvh_nodes != nullptr) return kRouteBvh;
+    if (d.mf_frag == nullptr || d.n_surf <= 0 || d.n_tri > 64 * kCtabMaxWords || !(p->t_scale > 0.0f) ||
+        !(p->t_scale <= kFiltMaxTScale))
+        return kRouteSel;
+    const int rc = scene_ensure_ctab(scene, p->hit_rule, p->t_scale, /*wanted=*/true);
+    if (rc != RT_OK) return rc;
+    d = scene_launch_view(scene);
+    const CtabDev& T = d.ctab[p->hit_rule];
+    const bool served = T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze &&
+                        p->t_scale >= T.ts_min && T.words <= (d.n_tri <= 64 ? 1 : 4);
+    return served ? kRouteTable : kRouteSel;
 }
 }  // namespace rt
 namespace {
@@ -756,7 +782,7 @@ extern "C" {
 const char* rt_last_error(void) { return g_err.c_str(); }
 
 int rt_params_default(int preset, rt_params* p) {
-    if (!p) return fail(RT_E_INVALID, "params is NULL");
+    if (!p) return errorf(RT_E_INVALID, "params is NULL");
     memset(p, 0, sizeof(*p));
     if (preset == RT_PRESET_CPU) {
         p->width = 512; p->height = 512; p->spp = 16; p->max_bounces = 2;
@@ -765,7 +791,7 @@ int rt_params_default(int preset, rt_params* p) {
         p->width = 720; p->height = 720; p->spp = 32; p->max_bounces = 80;
         p->hit_rule = RT_HIT_RULE_GPU;
     } else {
-        return fail(RT_E_INVALID, "bad preset %d", preset);
+        return errorf(RT_E_INVALID, "bad preset %d", preset);
     }
     p->preset = preset;
     p->sampler = RT_SAMPLER_UNIFORM;
@@ -777,14 +803,14 @@ int rt_params_default(int preset, rt_params* p) {
 }
 
 int rt_ctx_create(int device_ordinal, rt_ctx** out) {
-    if (!out) return fail(RT_E_INVALID, "out is NULL");
+    if (!out) return errorf(RT_E_INVALID, "out is NULL");
     *out = nullptr;
     int n = 0;
     RT_HIP(hipGetDeviceCount(&n));
     if (device_ordinal < 0 || device_ordinal >= n)
-        return fail(RT_E_INVALID, "device %d out of range (%d devices)", device_ordinal, n);
+        return errorf(RT_E_INVALID, "device %d out of range (%d devices)", device_ordinal, n);
     rt_ctx* c = new (std::nothrow) rt_ctx();
-    if (!c) return fail(RT_E_NOMEM, "out of host memory");
+    if (!c) return errorf(RT_E_NOMEM, "out of host memory");
     c->device = device_ordinal;
     int rc = set_device(c);
     if (rc != RT_OK) {
@@ -815,12 +841,12 @@ int rt_scene_create(rt_ctx* ctx, const float* tri_v, const float* albedo, int n_
                     int n_light, rt_scene** out) {
     using rt::f3;
     using rt::make3;
-    if (!ctx || !out) return fail(RT_E_INVALID, "ctx/out is NULL");
+    if (!ctx || !out) return errorf(RT_E_INVALID, "ctx/out is NULL");
     *out = nullptr;
-    if (n_surf < 0 || n_light < 0 || n_surf + n_light <= 0) return fail(RT_E_INVALID, "empty scene");
+    if (n_surf < 0 || n_light < 0 || n_surf + n_light <= 0) return errorf(RT_E_INVALID, "empty scene");
     if ((n_surf > 0 && (!tri_v || !albedo)) || (n_light > 0 && (!light_v || !emission || !light_group)))
-        return fail(RT_E_INVALID, "missing scene arrays");
-    if (n_surf + n_light > (1 << 24)) return fail(RT_E_INVALID, "too many triangles");
+        return errorf(RT_E_INVALID, "missing scene arrays");
+    if (n_surf + n_light > (1 << 24)) return errorf(RT_E_INVALID, "too many triangles");
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     const int n = n_surf + n_light;
@@ -828,7 +854,7 @@ int rt_scene_create(rt_ctx* ctx, const float* tri_v, const float* albedo, int n_
     std::vector<float4> shade((size_t)n * rt::kShadeF4);
     std::vector<int32_t> code_cpu(n), code_gpu(n);
     rt_scene* sc = new (std::nothrow) rt_scene();
-    if (!sc) return fail(RT_E_NOMEM, "out of host memory");
+    if (!sc) return errorf(RT_E_NOMEM, "out of host memory");
     sc->ctx = ctx;
     sc->n_surf = n_surf;
     sc->n_light = n_light;
@@ -926,7 +952,7 @@ int rt_scene_create(rt_ctx* ctx, const float* tri_v, const float* albedo, int n_
     }
     if (e != hipSuccess) {
         cleanup();
-        return fail(RT_E_HIP, "scene upload failed: %s", hipGetErrorString(e));
+        return errorf(RT_E_HIP, "scene upload failed: %s", hipGetErrorString(e));
     }
     // large scenes: the exact BVH path (a scene it cannot be built for keeps the scan)
     if (n > RT_BVH_AUTO_MIN && scene_build_bvh(sc) != RT_OK) scene_free_bvh(sc);
@@ -956,8 +982,8 @@ int rt_scene_destroy(rt_scene* scene) {
 }
 
 int rt_scene_ctab_info(const rt_scene* scene, int hit_rule, int* built, double* build_s, uint64_t* bytes) {
-    if (!scene) return fail(RT_E_INVALID, "scene is NULL");
-    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit_rule %d", hit_rule);
+    if (!scene) return errorf(RT_E_INVALID, "scene is NULL");
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return errorf(RT_E_INVALID, "bad hit_rule %d", hit_rule);
     std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(scene)->ctab_mu);
     const bool on = scene->dev.ctab[hit_rule].masks != nullptr;
     if (built) *built = on ? 1 : 0;
@@ -967,14 +993,14 @@ int rt_scene_ctab_info(const rt_scene* scene, int hit_rule, int* built, double* 
 }
 
 int rt_scene_set_accel(rt_scene* scene, int mode) {
-    if (!scene) return fail(RT_E_INVALID, "scene is NULL");
+    if (!scene) return errorf(RT_E_INVALID, "scene is NULL");
     if (mode != RT_ACCEL_AUTO && mode != RT_ACCEL_SCAN && mode != RT_ACCEL_BVH)
-        return fail(RT_E_INVALID, "bad accel mode %d", mode);
+        return errorf(RT_E_INVALID, "bad accel mode %d", mode);
     int rc = set_device(scene->ctx);
     if (rc != RT_OK) return rc;
     if (mode == RT_ACCEL_BVH || (mode == RT_ACCEL_AUTO && scene->dev.n_tri > RT_BVH_AUTO_MIN)) {
         rc = scene_build_bvh(scene);
-        if (rc != RT_OK) return fail(rc, "BVH build failed (scene outside the filter's ranges?)");
+        if (rc != RT_OK) return errorf(rc, "BVH build failed (scene outside the filter's ranges?)");
     }
     scene->accel = mode;
     return RT_OK;
@@ -983,9 +1009,9 @@ int rt_scene_set_accel(rt_scene* scene, int mode) {
 int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, const int32_t* surf, const float* orig,
                        const float* dir, int n_rays, uint64_t* masks, int64_t* stats) {
     if (!tri_v || n <= 0 || n > 64 * rt::kCtabMaxWords || n_surf <= 0 || n_surf > n)
-        return fail(RT_E_INVALID, "need 1 to %d triangles", 64 * rt::kCtabMaxWords);
-    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit rule %d", hit_rule);
-    if (n_rays < 0 || (n_rays > 0 && (!surf || !orig || !dir || !masks))) return fail(RT_E_INVALID, "missing ray arrays");
+        return errorf(RT_E_INVALID, "need 1 to %d triangles", 64 * rt::kCtabMaxWords);
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return errorf(RT_E_INVALID, "bad hit rule %d", hit_rule);
+    if (n_rays < 0 || (n_rays > 0 && (!surf || !orig || !dir || !masks))) return errorf(RT_E_INVALID, "missing ray arrays");
     std::vector<float4> isect((size_t)n * rt::kIsectF4);
     double vmax = 0.0;
     for (int i = 0; i < n; ++i) isect_record(tri_v + (size_t)i * 9, &isect[(size_t)i * 3]);
@@ -994,7 +1020,7 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
     const double mf_bound = (double)round_up(vmax * (1.0 + ldexp(1.0, -10)) + ldexp(1.0, -10));
     rt::CtabHost h;
     if (!rt::ctab_build(isect.data(), n, n_surf, mf_bound, hit_rule, rt::kCtabTsMin, &h))
-        return fail(RT_E_UNSUPPORTED, "candidate table build failed");
+        return errorf(RT_E_UNSUPPORTED, "candidate table build failed");
     for (int r = 0; r < n_rays; ++r)
         rt::ctab_lookup(h, surf[r], orig + (size_t)r * 3, dir + (size_t)r * 3, masks + (size_t)r * h.words);
     if (stats) {
@@ -1013,11 +1039,11 @@ int rt_ctab_candidates(const float* tri_v, int n, int n_surf, int hit_rule, cons
 }
 
 int rt_bvh_check(const float* tri_v, int n, int64_t* stats) {
-    if (!tri_v || n <= 0) return fail(RT_E_INVALID, "no triangles");
+    if (!tri_v || n <= 0) return errorf(RT_E_INVALID, "no triangles");
     std::vector<float4> isect((size_t)n * rt::kIsectF4);
     for (int i = 0; i < n; ++i) isect_record(tri_v + (size_t)i * 9, &isect[(size_t)i * 3]);
     rt::BvhHost h;
-    if (!rt::bvh_build(isect.data(), n, &h)) return fail(RT_E_UNSUPPORTED, "BVH build failed");
+    if (!rt::bvh_build(isect.data(), n, &h)) return errorf(RT_E_UNSUPPORTED, "BVH build failed");
     const std::string err = rt::bvh_check(isect.data(), n, h);
     if (stats) {
         int64_t leaves = 0;
@@ -1031,12 +1057,12 @@ int rt_bvh_check(const float* tri_v, int n, int64_t* stats) {
         stats[2] = (int64_t)h.dlist.size();
         stats[3] = leaves;
     }
-    if (!err.empty()) return fail(RT_E_INTERNAL, "BVH invariant: %s", err.c_str());
+    if (!err.empty()) return errorf(RT_E_INTERNAL, "BVH invariant: %s", err.c_str());
     return RT_OK;
 }
 
 int rt_scene_accel_info(const rt_scene* scene, int* n_nodes, int* depth, int64_t* dir_entries) {
-    if (!scene) return fail(RT_E_INVALID, "scene is NULL");
+    if (!scene) return errorf(RT_E_INVALID, "scene is NULL");
     if (n_nodes) *n_nodes = scene->has_bvh ? scene->bvh.n_nodes : 0;
     if (depth) *depth = scene->has_bvh ? scene->bvh.depth : 0;
     if (dir_entries) *dir_entries = scene->has_bvh ? (int64_t)scene->bvh.dlist.size() : 0;
@@ -1051,7 +1077,7 @@ static int intersect_bvh_host(rt_ctx* ctx, const rt_scene* scene, const float* o
     // builds the BVH once if the scene has none yet (kept for later calls; rt_scene_set_accel
     // builds it up front); the scene's accel mode is not touched
     rc = scene_build_bvh(const_cast<rt_scene*>(scene));
-    if (rc != RT_OK) return fail(rc, "BVH build failed");
+    if (rc != RT_OK) return errorf(rc, "BVH build failed");
     const rt::DeviceScene ds = launch_scene(scene, /*force_bvh=*/true);
     float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
     int32_t* d_h = nullptr;
@@ -1069,22 +1095,22 @@ static int intersect_bvh_host(rt_ctx* ctx, const rt_scene* scene, const float* o
     (void)hipFree(d_d);
     (void)hipFree(d_t);
     (void)hipFree(d_h);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_intersect_method(BVH): %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_intersect_method(BVH): %s", hipGetErrorString(e));
     return RT_OK;
 }
 
 int rt_scene_normals(const rt_scene* scene, float* out) {
-    if (!scene || !out) return fail(RT_E_INVALID, "scene/out is NULL");
+    if (!scene || !out) return errorf(RT_E_INVALID, "scene/out is NULL");
     memcpy(out, scene->normals.data(), sizeof(float) * scene->normals.size());
     return RT_OK;
 }
 
 int rt_intersect_device(rt_ctx* ctx, const rt_scene* scene, const float* d_orig, const float* d_dir,
                         int n, float t_scale, int hit_rule, float* d_t, int32_t* d_hit, void* stream) {
-    if (!ctx || !scene) return fail(RT_E_INVALID, "ctx/scene is NULL");
-    if (n < 0) return fail(RT_E_INVALID, "n < 0");
-    if (n > 0 && (!d_orig || !d_dir || !d_t || !d_hit)) return fail(RT_E_INVALID, "NULL buffer");
-    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit_rule");
+    if (!ctx || !scene) return errorf(RT_E_INVALID, "ctx/scene is NULL");
+    if (n < 0) return errorf(RT_E_INVALID, "n < 0");
+    if (n > 0 && (!d_orig || !d_dir || !d_t || !d_hit)) return errorf(RT_E_INVALID, "NULL buffer");
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return errorf(RT_E_INVALID, "bad hit_rule");
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     if (scene_uses_bvh(scene)) {  // the BVH path checks each ray's range itself
@@ -1100,11 +1126,11 @@ int rt_intersect_device(rt_ctx* ctx, const rt_scene* scene, const float* d_orig,
 
 int rt_intersect(rt_ctx* ctx, const rt_scene* scene, const float* orig, const float* dir, int n,
                  float t_scale, int hit_rule, float* out_t, int32_t* out_hit) {
-    if (!ctx || !scene) return fail(RT_E_INVALID, "ctx/scene is NULL");
-    if (n < 0) return fail(RT_E_INVALID, "n < 0");
+    if (!ctx || !scene) return errorf(RT_E_INVALID, "ctx/scene is NULL");
+    if (n < 0) return errorf(RT_E_INVALID, "n < 0");
     if (n == 0) return RT_OK;
-    if (!orig || !dir || !out_t || !out_hit) return fail(RT_E_INVALID, "NULL buffer");
-    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit_rule");
+    if (!orig || !dir || !out_t || !out_hit) return errorf(RT_E_INVALID, "NULL buffer");
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return errorf(RT_E_INVALID, "bad hit_rule");
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
@@ -1135,27 +1161,27 @@ int rt_intersect(rt_ctx* ctx, const rt_scene* scene, const float* orig, const fl
     (void)hipFree(d_d);
     (void)hipFree(d_t);
     (void)hipFree(d_h);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_intersect: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_intersect: %s", hipGetErrorString(e));
     return RT_OK;
 }
 
 int rt_intersect_method(rt_ctx* ctx, const rt_scene* scene, const float* orig, const float* dir, int n,
                         float t_scale, int hit_rule, int method, float* out_t, int32_t* out_hit,
                         int32_t* out_cand) {
-    if (!ctx || !scene) return fail(RT_E_INVALID, "ctx/scene is NULL");
-    if (n < 0) return fail(RT_E_INVALID, "n < 0");
+    if (!ctx || !scene) return errorf(RT_E_INVALID, "ctx/scene is NULL");
+    if (n < 0) return errorf(RT_E_INVALID, "n < 0");
     if (n == 0) return RT_OK;
-    if (!orig || !dir || !out_t || !out_hit) return fail(RT_E_INVALID, "NULL buffer");
-    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit_rule");
+    if (!orig || !dir || !out_t || !out_hit) return errorf(RT_E_INVALID, "NULL buffer");
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return errorf(RT_E_INVALID, "bad hit_rule");
     if (method == RT_ISECT_BVH) {
-        if (out_cand) return fail(RT_E_INVALID, "out_cand needs RT_ISECT_MFMA");
+        if (out_cand) return errorf(RT_E_INVALID, "out_cand needs RT_ISECT_MFMA");
         return intersect_bvh_host(ctx, scene, orig, dir, n, t_scale, hit_rule, out_t, out_hit);
     }
     if (method != RT_ISECT_SCAN && method != RT_ISECT_FILTER && method != RT_ISECT_MFMA)
-        return fail(RT_E_INVALID, "bad method %d", method);
-    if (out_cand && method != RT_ISECT_MFMA) return fail(RT_E_INVALID, "out_cand needs RT_ISECT_MFMA");
+        return errorf(RT_E_INVALID, "bad method %d", method);
+    if (out_cand && method != RT_ISECT_MFMA) return errorf(RT_E_INVALID, "out_cand needs RT_ISECT_MFMA");
     if (method == RT_ISECT_MFMA && (!scene->dev.mf_frag || !(t_scale > 0.0f && t_scale <= rt::kFiltMaxTScale)))
-        return fail(RT_E_UNSUPPORTED, "no matrix-core filter image for this scene / t_scale");
+        return errorf(RT_E_UNSUPPORTED, "no matrix-core filter image for this scene / t_scale");
     if (method == RT_ISECT_FILTER) {
         float omax = 0.0f, dmax = 0.0f;
         for (size_t k = 0; k < 3 * (size_t)n; ++k) {
@@ -1163,7 +1189,7 @@ int rt_intersect_method(rt_ctx* ctx, const rt_scene* scene, const float* orig, c
             dmax = fmaxf(dmax, fabsf(dir[k]));
         }
         if (!(dmax <= 2.0f) || !rt::filter_usable(scene->dev, omax, 0.0f, 0.0f, t_scale))
-            return fail(RT_E_UNSUPPORTED, "rays outside the filter's bounds");
+            return errorf(RT_E_UNSUPPORTED, "rays outside the filter's bounds");
     }
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;
@@ -1192,44 +1218,44 @@ int rt_intersect_method(rt_ctx* ctx, const rt_scene* scene, const float* orig, c
     (void)hipFree(d_t);
     (void)hipFree(d_h);
     if (d_c) (void)hipFree(d_c);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_intersect_method: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_intersect_method: %s", hipGetErrorString(e));
     return RT_OK;
 }
 
 int rt_intersect_cand(rt_ctx* ctx, const rt_scene* scene, const float* orig, const float* dir, int n, float t_scale,
                       int hit_rule, int source, const int32_t* surf, const uint64_t* masks_in, int pair_cap,
                       float* out_t, int32_t* out_hit, uint64_t* out_masks) {
-    if (!ctx || !scene) return fail(RT_E_INVALID, "ctx/scene is NULL");
-    if (n < 0) return fail(RT_E_INVALID, "n < 0");
-    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return fail(RT_E_INVALID, "bad hit_rule");
-    if (source != RT_CAND_TABLE && source != RT_CAND_GIVEN) return fail(RT_E_INVALID, "bad source %d", source);
+    if (!ctx || !scene) return errorf(RT_E_INVALID, "ctx/scene is NULL");
+    if (n < 0) return errorf(RT_E_INVALID, "n < 0");
+    if (hit_rule != RT_HIT_RULE_CPU && hit_rule != RT_HIT_RULE_GPU) return errorf(RT_E_INVALID, "bad hit_rule");
+    if (source != RT_CAND_TABLE && source != RT_CAND_GIVEN) return errorf(RT_E_INVALID, "bad source %d", source);
     const int n_tri = scene->dev.n_tri;
     if (n_tri > 64 * rt::kCtabMaxWords || scene_uses_bvh(scene))
-        return fail(RT_E_UNSUPPORTED, "the candidate route serves scan scenes of at most %d triangles",
+        return errorf(RT_E_UNSUPPORTED, "the candidate route serves scan scenes of at most %d triangles",
                     64 * rt::kCtabMaxWords);
     if (!rt::cand_pair_cap_served(n_tri, pair_cap))
-        return fail(RT_E_INVALID, "no render kernel uses pair cap %d with %d triangles", pair_cap, n_tri);
-    if (source == RT_CAND_GIVEN && out_masks) return fail(RT_E_INVALID, "out_masks needs RT_CAND_TABLE");
+        return errorf(RT_E_INVALID, "no render kernel uses pair cap %d with %d triangles", pair_cap, n_tri);
+    if (source == RT_CAND_GIVEN && out_masks) return errorf(RT_E_INVALID, "out_masks needs RT_CAND_TABLE");
     if (n == 0) return RT_OK;
-    if (!orig || !dir || !out_t || !out_hit) return fail(RT_E_INVALID, "NULL buffer");
-    if (source == RT_CAND_TABLE ? !surf : !masks_in) return fail(RT_E_INVALID, "the source's per-ray input is NULL");
+    if (!orig || !dir || !out_t || !out_hit) return errorf(RT_E_INVALID, "NULL buffer");
+    if (source == RT_CAND_TABLE ? !surf : !masks_in) return errorf(RT_E_INVALID, "the source's per-ray input is NULL");
     const int words = (n_tri + 63) / 64;
     if (source == RT_CAND_GIVEN) {  // a bit past the last triangle would index past the scene's records
         const uint64_t live = (n_tri % 64) ? ((1ull << (n_tri % 64)) - 1ull) : ~0ull;
         for (size_t r = 0; r < (size_t)n; ++r)
             if (masks_in[r * words + (words - 1)] & ~live)
-                return fail(RT_E_INVALID, "ray %zu: a candidate bit past triangle %d", r, n_tri - 1);
+                return errorf(RT_E_INVALID, "ray %zu: a candidate bit past triangle %d", r, n_tri - 1);
     }
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     if (source == RT_CAND_TABLE) {
         if (hit_rule == RT_HIT_RULE_CPU && !(t_scale >= rt::kCtabTsMin))
-            return fail(RT_E_UNSUPPORTED, "the CPU rule's table serves t_scale >= %g", (double)rt::kCtabTsMin);
+            return errorf(RT_E_UNSUPPORTED, "the CPU rule's table serves t_scale >= %g", (double)rt::kCtabTsMin);
         rc = rt::scene_ensure_ctab(scene, hit_rule, t_scale, /*wanted=*/true);
         if (rc != RT_OK) return rc;
         const rt::CtabDev& T = scene->dev.ctab[hit_rule];
         if (T.masks == nullptr || T.words != words || !(t_scale >= T.ts_min))
-            return fail(RT_E_UNSUPPORTED, "no candidate table for this scene / hit rule / t_scale");
+            return errorf(RT_E_UNSUPPORTED, "no candidate table for this scene / hit rule / t_scale");
     }
     float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
     int32_t *d_h = nullptr, *d_s = nullptr;
@@ -1258,17 +1284,17 @@ int rt_intersect_cand(rt_ctx* ctx, const rt_scene* scene, const float* orig, con
     if (d_s) (void)hipFree(d_s);
     if (d_mi) (void)hipFree(d_mi);
     if (d_mo) (void)hipFree(d_mo);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_intersect_cand: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_intersect_cand: %s", hipGetErrorString(e));
     return RT_OK;
 }
 
 int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt_params* params,
               int x0, int y0, int w, int h, float* out_rgb, uint64_t* out_ray_casts) {
-    if (!ctx || !scene || !cam || !out_rgb) return fail(RT_E_INVALID, "NULL argument");
+    if (!ctx || !scene || !cam || !out_rgb) return errorf(RT_E_INVALID, "NULL argument");
     int rc = check_params(params);
     if (rc != RT_OK) return rc;
     if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 + w > params->width || y0 + h > params->height)
-        return fail(RT_E_INVALID, "rectangle outside the image");
+        return errorf(RT_E_INVALID, "rectangle outside the image");
     rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     std::vector<rt::BlockDesc> blocks;
@@ -1310,7 +1336,7 @@ int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt
     (void)hipFree(d_blocks);
     (void)hipFree(d_out);
     (void)hipFree(d_casts);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_render: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_render: %s", hipGetErrorString(e));
     if (out_ray_casts) *out_ray_casts = casts;
     return RT_OK;
 }
@@ -1318,17 +1344,17 @@ int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt
 int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam,
                            const rt_params* params, const int32_t* tiles, int n_tiles, int tile_size,
                            float* d_out, uint64_t* d_casts, void* stream) {
-    if (!ctx || !scene || !cam) return fail(RT_E_INVALID, "NULL argument");
+    if (!ctx || !scene || !cam) return errorf(RT_E_INVALID, "NULL argument");
     int rc = check_params(params);
     if (rc != RT_OK) return rc;
-    if (n_tiles < 0) return fail(RT_E_INVALID, "n_tiles < 0");
+    if (n_tiles < 0) return errorf(RT_E_INVALID, "n_tiles < 0");
     if (n_tiles == 0) return RT_OK;
-    if (!tiles || !d_out) return fail(RT_E_INVALID, "NULL tiles/out");
-    if (tile_size <= 0 || tile_size % 16 != 0) return fail(RT_E_INVALID, "tile_size must be a positive multiple of 16");
+    if (!tiles || !d_out) return errorf(RT_E_INVALID, "NULL tiles/out");
+    if (tile_size <= 0 || tile_size % 16 != 0) return errorf(RT_E_INVALID, "tile_size must be a positive multiple of 16");
     for (int k = 0; k < n_tiles; ++k) {
         const int tx = tiles[2 * k], ty = tiles[2 * k + 1];
         if (tx < 0 || ty < 0 || tx >= params->width || ty >= params->height)
-            return fail(RT_E_INVALID, "tile %d origin (%d,%d) outside the image", k, tx, ty);
+            return errorf(RT_E_INVALID, "tile %d origin (%d,%d) outside the image", k, tx, ty);
     }
     rc = set_device(ctx);
     if (rc != RT_OK) return rc;
@@ -1374,9 +1400,9 @@ int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* 
 }
 
 int rt_selftest(rt_ctx* ctx, int which, uint64_t* result) {
-    if (!ctx || !result) return fail(RT_E_INVALID, "NULL argument");
+    if (!ctx || !result) return errorf(RT_E_INVALID, "NULL argument");
     if (which < RT_SELFTEST_RCP || which > RT_SELFTEST_PHILOX_PX)
-        return fail(RT_E_INVALID, "unknown self-test %d", which);
+        return errorf(RT_E_INVALID, "unknown self-test %d", which);
     int rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     unsigned long long* d_m = nullptr;
@@ -1393,7 +1419,7 @@ int rt_selftest(rt_ctx* ctx, int which, uint64_t* result) {
     if (e == hipSuccess) e = hipMemcpy(&f, d_f, sizeof(f), hipMemcpyDeviceToHost);
     (void)hipFree(d_m);
     (void)hipFree(d_f);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_selftest: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_selftest: %s", hipGetErrorString(e));
     result[0] = m;
     result[1] = f;
     return RT_OK;
@@ -1403,14 +1429,14 @@ int rt_selftest(rt_ctx* ctx, int which, uint64_t* result) {
 // ---- checks of the primary-ray cull (k_cull_ps) on the host ----
 
 int rt_filter_build(const float* tri_v, int n, float* out_filt) {
-    if (!tri_v || !out_filt || n <= 0) return fail(RT_E_INVALID, "bad arguments");
+    if (!tri_v || !out_filt || n <= 0) return errorf(RT_E_INVALID, "bad arguments");
     const double obound = filter_origin_bound(tri_v, (size_t)n * 9);
     for (int i = 0; i < n; ++i) {
         float4 rec[3];
         isect_record(tri_v + (size_t)i * 9, rec);
         float4 f[rt::kFiltF4];
         if (!build_filter(rec[0], rec[1], rec[2], obound, f))
-            return fail(RT_E_UNSUPPORTED, "no filter record for triangle %d (coordinates too large)", i);
+            return errorf(RT_E_UNSUPPORTED, "no filter record for triangle %d (coordinates too large)", i);
         memcpy(out_filt + (size_t)i * 4 * rt::kFiltF4, f, sizeof(f));
     }
     return RT_OK;
@@ -1418,11 +1444,11 @@ int rt_filter_build(const float* tri_v, int n, float* out_filt) {
 
 int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt_params* params,
                          int x0, int y0, int w, int h, uint64_t* out, int64_t* n_words) {
-    if (!ctx || !scene || !cam || !out || !n_words) return fail(RT_E_INVALID, "NULL argument");
+    if (!ctx || !scene || !cam || !out || !n_words) return errorf(RT_E_INVALID, "NULL argument");
     int rc = check_params(params);
     if (rc != RT_OK) return rc;
     if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 + w > params->width || y0 + h > params->height)
-        return fail(RT_E_INVALID, "rectangle outside the image");
+        return errorf(RT_E_INVALID, "rectangle outside the image");
     rc = set_device(ctx);
     if (rc != RT_OK) return rc;
     std::vector<rt::BlockDesc> blocks;
@@ -1430,12 +1456,12 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
         for (int bx = 0; bx < w; bx += 16) blocks.push_back({x0 + bx, y0 + by, bx, by});
     // k_cull_ps covers what k_render_ps's launch condition covers: the CPU preset, scenes of
     // <= 64 * kRenderCullWords triangles (wider scenes would get truncated masks)
-    if (params->preset != RT_PRESET_CPU) return fail(RT_E_UNSUPPORTED, "the primary-ray cull is CPU-preset only");
+    if (params->preset != RT_PRESET_CPU) return errorf(RT_E_UNSUPPORTED, "the primary-ray cull is CPU-preset only");
     if (scene->dev.n_tri > 64 * rt::kRenderCullWords)
-        return fail(RT_E_UNSUPPORTED, "the primary-ray cull covers scenes of <= %d triangles (this one has %d)",
+        return errorf(RT_E_UNSUPPORTED, "the primary-ray cull covers scenes of <= %d triangles (this one has %d)",
                     64 * rt::kRenderCullWords, scene->dev.n_tri);
     rt::RenderLaunch a = make_launch(scene, cam, params);
-    if (!a.use_filter) return fail(RT_E_UNSUPPORTED, "no filter records for this scene and camera");
+    if (!a.use_filter) return errorf(RT_E_UNSUPPORTED, "no filter records for this scene and camera");
     a.n_blocks = (int)blocks.size();
     a.clip_x1 = x0 + w;
     a.clip_y1 = y0 + h;
@@ -1443,7 +1469,7 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
     if (*n_words < words) {
         const long long cap = (long long)*n_words;
         *n_words = words;
-        return fail(RT_E_INVALID, "out holds %lld words, %lld needed", cap, (long long)words);
+        return errorf(RT_E_INVALID, "out holds %lld words, %lld needed", cap, (long long)words);
     }
     rt::BlockDesc* d_blocks = nullptr;
     hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
@@ -1460,16 +1486,16 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(out, a.cull, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToHost);
     (void)hipFree(d_blocks);
-    if (e != hipSuccess) return fail(RT_E_HIP, "rt_cull_masks_device: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_cull_masks_device: %s", hipGetErrorString(e));
     *n_words = words;
     return RT_OK;
 }
 
 int rt_rect_candidates(const float* filt, int n_tri, const rt_camera* cam, const rt_params* p, int px0, int py0,
                        int px1, int py1, uint64_t* masks) {
-    if (!filt || !cam || !p || !masks || n_tri <= 0) return fail(RT_E_INVALID, "bad arguments");
-    if (p->preset != RT_PRESET_CPU) return fail(RT_E_UNSUPPORTED, "the primary-ray phase is CPU-preset only");
-    if (px0 > px1 || py0 > py1) return fail(RT_E_INVALID, "empty rectangle");
+    if (!filt || !cam || !p || !masks || n_tri <= 0) return errorf(RT_E_INVALID, "bad arguments");
+    if (p->preset != RT_PRESET_CPU) return errorf(RT_E_UNSUPPORTED, "the primary-ray phase is CPU-preset only");
+    if (px0 > px1 || py0 > py1) return errorf(RT_E_INVALID, "empty rectangle");
     const rt::CamRect c = rt::make_cam_rect(cam->pos[0], cam->pos[1], cam->pos[2], (float)cos((double)cam->yaw_y),
                                             (float)sin((double)cam->yaw_y), p->width, p->height, p->t_scale,
                                             px0, px1, py0, py1);
@@ -1485,9 +1511,9 @@ int rt_rect_candidates(const float* filt, int n_tri, const rt_camera* cam, const
 
 int rt_rect_candidates_forms(const float* filt, int n_tri, const rt_camera* cam, const rt_params* p, int px0, int py0,
                              int px1, int py1, uint64_t* masks) {
-    if (!filt || !cam || !p || !masks || n_tri <= 0) return fail(RT_E_INVALID, "bad arguments");
-    if (p->preset != RT_PRESET_CPU) return fail(RT_E_UNSUPPORTED, "the primary-ray phase is CPU-preset only");
-    if (px0 > px1 || py0 > py1) return fail(RT_E_INVALID, "empty rectangle");
+    if (!filt || !cam || !p || !masks || n_tri <= 0) return errorf(RT_E_INVALID, "bad arguments");
+    if (p->preset != RT_PRESET_CPU) return errorf(RT_E_UNSUPPORTED, "the primary-ray phase is CPU-preset only");
+    if (px0 > px1 || py0 > py1) return errorf(RT_E_INVALID, "empty rectangle");
     const rt::CamConst k = rt::make_cam_const(cam->pos[0], cam->pos[1], cam->pos[2], (float)cos((double)cam->yaw_y),
                                               (float)sin((double)cam->yaw_y), p->width, p->height, p->t_scale);
     const rt::CamRect c = rt::cam_rect_of(k, px0, px1, py0, py1);

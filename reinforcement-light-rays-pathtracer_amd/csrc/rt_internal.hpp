@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/rtmi.h"
 #include "rt_math.hpp"
 
 namespace rt {
@@ -480,6 +481,23 @@ bool sarsa_prof_compiled();  // rt_sarsa.hip was built with RT_SARSA_PROF=1 (per
 bool sarsa_ctab_compiled();  // rt_sarsa.hip was built with RT_SARSA_CTAB=1 (the table route of its persistent kernel)
 hipError_t launch_sarsa_rebuild(const SarsaMap& m, hipStream_t stream);  // CDF + argmax from Q
 hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStream_t stream);  // of [v0, v0 + n)
+// ---- what the entries that cast from surface points share on the host (rt_capi.cpp): ----
+// ---- rt_probe_radiance, rt_sarsa_bake, rt_sarsa_sweep                                 ----
+int set_error(int code, const char* msg);         // the thread's rt_last_error text; returns code
+int errorf(int code, const char* fmt, ...);       // set_error of the formatted text
+int ctx_device(const rt_ctx* ctx);
+DeviceScene scene_launch_view(const rt_scene* s);
+int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
+// ctx, scene, params, n, spp and hit_rule as all three entries want them, or RT_E_INVALID
+int check_leaving_args(const rt_ctx* ctx, const rt_scene* scene, const rt_params* p, int n);
+// The cast route of rays that leave known surfaces of the scene (closest_hit_route, rt_paths.hpp):
+// the exact BVH if the scene's accel mode turns it on, else the bounce-ray candidate table where
+// the scene may have one (built and uploaded here on first use) and it serves params' hit rule
+// and t_scale, else the filter or the scan.  *launch_scene: the view the launch takes.  Returns
+// the route, or the (negative) error code of the table's upload.
+constexpr int kRouteSel = 0, kRouteTable = 1, kRouteBvh = 2;
+int leaving_route(const rt_scene* scene, const rt_params* p, DeviceScene* launch_scene);
+
 // rt_sarsa_bake (rt_bake.hip) works on a map through this view (rt_sarsa_host.cpp: sarsa_bake_view)
 struct SarsaBakeView {
     SarsaMap m;

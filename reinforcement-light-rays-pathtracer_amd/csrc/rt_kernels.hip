@@ -30,7 +30,7 @@
 
 #include <type_traits>
 
-#include "rt_trace.hpp"
+#include "rt_paths.hpp"
 
 namespace rt {
 
@@ -261,27 +261,9 @@ __global__ __launch_bounds__(256, MF > 0 ? RT_MF_RENDER_WAVES : RT_MIN_WAVES) vo
             terminal = true;  // bounces == MAX_RAY_BOUNCES -> vec3(0)
         } else {
             // surface: position, sample a direction, update the estimator
-            const float Dx = d.x * a.t_scale, Dy = d.y * a.t_scale, Dz = d.z * a.t_scale;
-            const f3 pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
-            const float4 N = shade[h.tri * kShadeF4 + 0];
-            const float4 T = shade[h.tri * kShadeF4 + 1];
-            const float4 B = shade[h.tri * kShadeF4 + 2];
-            float r1, r2;
-            draw2(pix, (uint32_t)s, 1u + (uint32_t)depth, a.seed_lo, a.seed_hi, &r1, &r2);
-            float cos_theta, sin_theta;
-            if (SAMPLER == 0) {
-                cos_theta = r1;
-                sin_theta = sqrtf(1.0f - r1 * r1);
-            } else {
-                cos_theta = sqrtf(r1);
-                sin_theta = sqrtf(1.0f - r1);
-            }
-            float sphi, cphi;
-            sincos_turn(r2, &sphi, &cphi);
-            const float sx = sin_theta * cphi, sz = sin_theta * sphi;
-            const f3 sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x,
-                                (sx * B.y + cos_theta * N.y) + sz * T.y,
-                                (sx * B.z + cos_theta * N.z) + sz * T.z);
+            f3 pos, sd;
+            const float cos_theta = bounce_direction<SAMPLER>(h, o, d, a.t_scale, shade, pix, (uint32_t)s, depth, a.seed_lo,
+                                                              a.seed_hi, &pos, &sd);
             if (PRESET == 0) {
                 if (depth == 0) {
                     f_tri0 = h.tri;
@@ -291,15 +273,7 @@ __global__ __launch_bounds__(256, MF > 0 ? RT_MF_RENDER_WAVES : RT_MIN_WAVES) vo
                     f_cos1 = cos_theta;
                 }
             } else {
-                if (SAMPLER == 0) {
-                    const float4 c = shade[h.tri * kShadeF4 + 3];
-                    tp.x = div_rho((tp.x * c.x) * cos_theta);
-                    tp.y = div_rho((tp.y * c.y) * cos_theta);
-                    tp.z = div_rho((tp.z * c.z) * cos_theta);
-                } else {
-                    const float4 c = shade[h.tri * kShadeF4 + 4];
-                    tp = make3(tp.x * c.x, tp.y * c.y, tp.z * c.z);
-                }
+                tp = bounce_throughput<SAMPLER>(tp, shade, h.tri, cos_theta);
             }
             o = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
             d = normalize(sd);
@@ -495,39 +469,7 @@ __global__ __launch_bounds__(256, CT ? RT_PQ_CT_WAVES : RT_MF_RENDER_WAVES) void
             const float4 e = shade[h.tri * kShadeF4 + 3];
             L = make3(tp.x * e.x, tp.y * e.y, tp.z * e.z);
         } else {
-            // as k_render<1, ...>: position, sample a direction, update the throughput
-            const float Dx = d.x * a.t_scale, Dy = d.y * a.t_scale, Dz = d.z * a.t_scale;
-            const f3 pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
-            const float4 N = shade[h.tri * kShadeF4 + 0];
-            const float4 T = shade[h.tri * kShadeF4 + 1];
-            const float4 B = shade[h.tri * kShadeF4 + 2];
-            float r1, r2;
-            draw2(pix, (uint32_t)s, 1u + (uint32_t)depth, a.seed_lo, a.seed_hi, &r1, &r2);
-            float cos_theta, sin_theta;
-            if (SAMPLER == 0) {
-                cos_theta = r1;
-                sin_theta = sqrtf(1.0f - r1 * r1);
-            } else {
-                cos_theta = sqrtf(r1);
-                sin_theta = sqrtf(1.0f - r1);
-            }
-            float sphi, cphi;
-            sincos_turn(r2, &sphi, &cphi);
-            const float sx = sin_theta * cphi, sz = sin_theta * sphi;
-            const f3 sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x, (sx * B.y + cos_theta * N.y) + sz * T.y,
-                                (sx * B.z + cos_theta * N.z) + sz * T.z);
-            if (SAMPLER == 0) {
-                const float4 c = shade[h.tri * kShadeF4 + 3];
-                tp.x = div_rho((tp.x * c.x) * cos_theta);
-                tp.y = div_rho((tp.y * c.y) * cos_theta);
-                tp.z = div_rho((tp.z * c.z) * cos_theta);
-            } else {
-                const float4 c = shade[h.tri * kShadeF4 + 4];
-                tp = make3(tp.x * c.x, tp.y * c.y, tp.z * c.z);
-            }
-            o = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
-            d = normalize(sd);
-            surf = h.tri;
+            surf = surface_step<SAMPLER>(h, o, d, tp, a.t_scale, shade, pix, (uint32_t)s, depth, a.seed_lo, a.seed_hi);
             ++depth;
             if (depth == a.max_bounces) terminal = true;  // loop exhausted -> 0
         }

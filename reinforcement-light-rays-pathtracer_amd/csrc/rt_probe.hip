@@ -17,29 +17,17 @@
 // Item j = (p * 144 + k) * split + c: the lanes of a wave share a point, and neighbouring
 // lanes its sector (one candidate-table entry, one cube-map bin).  k_probe_fold adds each
 // sector's chunk sums in chunk order and divides by spp.
-// Cast routes (the same hit, bit for bit): the scene's bounce-ray candidate table (every ray
-// here leaves a known surface), the exact BVH when the scene's accel mode turns it on, else
-// the two-phase filter (origins inside its bound) or the scan.
+// The sample's first ray (sector_first_ray), the cast on the route the host picked
+// (closest_hit_route; leaving_route in rt_capi.cpp: the same hit, bit for bit, on each) and the
+// preset's bounce (surface_step) are rt_paths.hpp's, shared with k_bake and k_sweep.
 #include <hip/hip_runtime.h>
-
-#include <float.h>
-#include <stdarg.h>
-#include <stdio.h>
 
 #include <algorithm>
 #include <map>
 #include <memory>
 #include <mutex>
 
-#include "../../include/rtmi.h"
-#include "rt_trace.hpp"
-
-namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
-DeviceScene scene_launch_view(const rt_scene* s);
-int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
-}  // namespace rt
+#include "rt_paths.hpp"
 
 namespace rt {
 namespace {
@@ -48,7 +36,6 @@ constexpr int kProbeSectors = RT_PROBE_SECTORS;
 static_assert(kProbeSectors == kDqnActions && kProbeSectors == kDqnGrid * kDqnGrid, "the sampler's 12 x 12 cells");
 constexpr uint32_t kProbeMaxId = (uint32_t)(((uint64_t)1 << 32) / kProbeSectors);  // ids below: id * 144 + 143 fits
 
-constexpr int kRouteSel = 0, kRouteTable = 1, kRouteBvh = 2;
 // Waves per SIMD the launch bounds ask for.  The table route's casts wait on two dependent
 // lookups and gain from occupancy, as k_render_pq<.., CT>'s: 6 waves (80 VGPRs) is the most
 // the kernel holds without spilling (71-80 used; 8 waves spill 5-75 VGPRs to scratch), 5 for
@@ -106,15 +93,10 @@ __global__ __launch_bounds__(256, probe_waves(ROUTE, RULE, NW)) void k_probe(con
         const float4 B4 = shade[tri0 * kShadeF4 + 2];
         const f3 N = make3(N4.x, N4.y, N4.z);
         const f3 pos = make3(a.pos[(size_t)point * 3 + 0], a.pos[(size_t)point * 3 + 1], a.pos[(size_t)point * 3 + 2]);
-        uint32_t w[4];
-        philox4x32_10(pix, s, 1u, 1u + kDqnActions / 2, a.seed_lo, a.seed_hi, w);
-        const int gx = sector / kDqnGrid, gy = sector - gx * kDqnGrid;
-        const f3 dir = grid_direction((float)gx + u01(w[0]), (float)gy + u01(w[1]), N, make3(T4.x, T4.y, T4.z),
-                                      make3(B4.x, B4.y, B4.z), pos);
+        const f3 dir = sector_first_ray(pix, s, sector, N, make3(T4.x, T4.y, T4.z), make3(B4.x, B4.y, B4.z), pos,
+                                        a.seed_lo, a.seed_hi, &o, &d);
         if (first && a.out_dir != nullptr)
             store_rgb(a.out_dir + ((size_t)point * kProbeSectors + sector) * 3, dir.x, dir.y, dir.z);
-        o = make3(pos.x + dir.x * kEps, pos.y + dir.y * kEps, pos.z + dir.z * kEps);
-        d = normalize(dir);
         cosn = dot(N, d);
         tp = make3(1.0f, 1.0f, 1.0f);
         depth = 1;
@@ -182,19 +164,9 @@ __global__ __launch_bounds__(256, probe_waves(ROUTE, RULE, NW)) void k_probe(con
             if (exhausted) break;
             continue;  // (every claimed item ended without a cast)
         }
-        Hit h;
-        if constexpr (ROUTE == kRouteTable) {
-            h = closest_hit_ctab<RULE, NW>(a.scene, a.scene.ctab[RULE], surf, o, d, a.t_scale, active, wl);
-            if (!active) continue;
-        } else if constexpr (ROUTE == kRouteBvh) {
-            if (!active) continue;
-            h = closest_hit_bvh<RULE>(a.scene, o, d, a.t_scale, s_stk + threadIdx.x);
-        } else {
-            if (!active) continue;
-            // the filter's bounds hold for origins within origin_bound (the caller's point may lie anywhere)
-            const float om = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-            h = closest_hit_sel<RULE>(a.scene, a.use_filter && om <= a.scene.origin_bound, o, d, a.t_scale);
-        }
+        const Hit h = closest_hit_route<RULE, ROUTE, NW>(a.scene, a.use_filter, surf, o, d, a.t_scale, active, wl,
+                                                         ROUTE == kRouteBvh ? s_stk + threadIdx.x : nullptr);
+        if (!active) continue;
         ++n_casts;
         bool terminal = false;
         f3 L = make3(0.0f, 0.0f, 0.0f);
@@ -206,39 +178,7 @@ __global__ __launch_bounds__(256, probe_waves(ROUTE, RULE, NW)) void k_probe(con
             const float4 e = shade[h.tri * kShadeF4 + 3];
             L = make3(tp.x * e.x, tp.y * e.y, tp.z * e.z);
         } else {
-            // as k_render<1, ...>: position, sample a direction, update the throughput
-            const float Dx = d.x * a.t_scale, Dy = d.y * a.t_scale, Dz = d.z * a.t_scale;
-            const f3 pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
-            const float4 N = shade[h.tri * kShadeF4 + 0];
-            const float4 T = shade[h.tri * kShadeF4 + 1];
-            const float4 B = shade[h.tri * kShadeF4 + 2];
-            float r1, r2;
-            draw2(pix, s, 1u + (uint32_t)depth, a.seed_lo, a.seed_hi, &r1, &r2);
-            float cos_theta, sin_theta;
-            if (SAMPLER == 0) {
-                cos_theta = r1;
-                sin_theta = sqrtf(1.0f - r1 * r1);
-            } else {
-                cos_theta = sqrtf(r1);
-                sin_theta = sqrtf(1.0f - r1);
-            }
-            float sphi, cphi;
-            sincos_turn(r2, &sphi, &cphi);
-            const float sx = sin_theta * cphi, sz = sin_theta * sphi;
-            const f3 sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x, (sx * B.y + cos_theta * N.y) + sz * T.y,
-                                (sx * B.z + cos_theta * N.z) + sz * T.z);
-            if (SAMPLER == 0) {
-                const float4 c = shade[h.tri * kShadeF4 + 3];
-                tp.x = div_rho((tp.x * c.x) * cos_theta);
-                tp.y = div_rho((tp.y * c.y) * cos_theta);
-                tp.z = div_rho((tp.z * c.z) * cos_theta);
-            } else {
-                const float4 c = shade[h.tri * kShadeF4 + 4];
-                tp = make3(tp.x * c.x, tp.y * c.y, tp.z * c.z);
-            }
-            o = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
-            d = normalize(sd);
-            surf = h.tri;
+            surf = surface_step<SAMPLER>(h, o, d, tp, a.t_scale, shade, pix, s, depth, a.seed_lo, a.seed_hi);
             ++depth;
             if (depth == a.max_bounces) terminal = true;  // loop exhausted -> 0
         }
@@ -335,29 +275,15 @@ ProbeWorkspace* workspace_for(const rt_ctx* ctx) {
     return w.get();
 }
 
-int perr(int code, const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-
 // what both entries check before they look at the point list
 int check_probe(const rt_ctx* ctx, const rt_scene* scene, const rt_params* p, int n) {
-    if (!ctx) return perr(RT_E_INVALID, "ctx is NULL");
-    if (!scene) return perr(RT_E_INVALID, "scene is NULL");
-    if (!p) return perr(RT_E_INVALID, "params is NULL");
-    if (n < 0) return perr(RT_E_INVALID, "n < 0 (got %d)", n);
-    if (p->spp <= 0) return perr(RT_E_INVALID, "spp must be > 0 (got %d)", p->spp);
+    const int rc = check_leaving_args(ctx, scene, p, n);
+    if (rc != RT_OK) return rc;
     const int split = p->spp_split <= 0 ? 1 : p->spp_split;
-    if (p->spp % split != 0) return perr(RT_E_INVALID, "spp_split %d does not divide spp %d", split, p->spp);
-    if (p->max_bounces < 1) return perr(RT_E_INVALID, "max_bounces must be >= 1 (got %d)", p->max_bounces);
+    if (p->spp % split != 0) return errorf(RT_E_INVALID, "spp_split %d does not divide spp %d", split, p->spp);
+    if (p->max_bounces < 1) return errorf(RT_E_INVALID, "max_bounces must be >= 1 (got %d)", p->max_bounces);
     if (p->sampler != RT_SAMPLER_UNIFORM && p->sampler != RT_SAMPLER_COSINE)
-        return perr(RT_E_INVALID, "bad sampler %d", p->sampler);
-    if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU)
-        return perr(RT_E_INVALID, "bad hit_rule %d", p->hit_rule);
+        return errorf(RT_E_INVALID, "bad sampler %d", p->sampler);
     return RT_OK;
 }
 
@@ -365,21 +291,10 @@ int probe_device(rt_ctx* ctx, const rt_scene* scene, const rt_params* p, const f
                  const uint32_t* d_ids, int n, uint32_t first_sample, float* d_rad, float* d_irr, float* d_dir,
                  uint64_t* d_casts, hipStream_t stream) {
     hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return perr(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     ProbeLaunch a;
-    a.scene = scene_launch_view(scene);
-    int route = a.scene.bvh_nodes != nullptr ? kRouteBvh : kRouteSel;
-    // every ray leaves a known surface: the bounce-ray candidate table, where the scene may have one
-    if (route == kRouteSel && a.scene.mf_frag != nullptr && a.scene.n_surf > 0 &&
-        a.scene.n_tri <= 64 * kCtabMaxWords && p->t_scale > 0.0f && p->t_scale <= kFiltMaxTScale) {
-        const int rc = scene_ensure_ctab(scene, p->hit_rule, p->t_scale, /*wanted=*/true);
-        if (rc != RT_OK) return rc;
-        a.scene = scene_launch_view(scene);
-        const CtabDev& T = a.scene.ctab[p->hit_rule];
-        if (T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze && p->t_scale >= T.ts_min &&
-            T.words <= (a.scene.n_tri <= 64 ? 1 : 4))
-            route = kRouteTable;
-    }
+    const int route = leaving_route(scene, p, &a.scene);
+    if (route < 0) return route;
     a.pos = d_pos;
     a.tri = d_tri;
     a.ids = d_ids;
@@ -405,17 +320,17 @@ int probe_device(rt_ctx* ctx, const rt_scene* scene, const rt_params* p, const f
         ws->csum = nullptr;
         ws->cap = 0;
         e = hipMalloc(&ws->csum, sizeof(float) * floats);
-        if (e != hipSuccess) return perr(RT_E_NOMEM, "rt_probe_radiance: %zu bytes of chunk sums: %s", sizeof(float) * floats, hipGetErrorString(e));
+        if (e != hipSuccess) return errorf(RT_E_NOMEM, "rt_probe_radiance: %zu bytes of chunk sums: %s", sizeof(float) * floats, hipGetErrorString(e));
         ws->cap = floats;
     }
     if (!ws->work) {
         e = hipMalloc(&ws->work, sizeof(unsigned long long));
-        if (e != hipSuccess) return perr(RT_E_NOMEM, "rt_probe_radiance: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return errorf(RT_E_NOMEM, "rt_probe_radiance: %s", hipGetErrorString(e));
     }
     a.csum = ws->csum;
     a.work = ws->work;
     e = launch_probe(a, p->sampler, p->hit_rule, route, stream);
-    if (e != hipSuccess) return perr(RT_E_HIP, "rt_probe_radiance: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_probe_radiance: %s", hipGetErrorString(e));
     return RT_OK;
 }
 
@@ -436,10 +351,10 @@ int rt_probe_radiance_device(rt_ctx* ctx, const rt_scene* scene, const rt_params
     const int rc = rt::check_probe(ctx, scene, params, n);
     if (rc != RT_OK) return rc;
     if (n == 0) return RT_OK;
-    if (!d_pos) return rt::perr(RT_E_INVALID, "pos is NULL");
-    if (!d_tri) return rt::perr(RT_E_INVALID, "tri is NULL");
-    if (!d_ids) return rt::perr(RT_E_INVALID, "ids is NULL");
-    if (!d_rad) return rt::perr(RT_E_INVALID, "out_rad is NULL");
+    if (!d_pos) return rt::errorf(RT_E_INVALID, "pos is NULL");
+    if (!d_tri) return rt::errorf(RT_E_INVALID, "tri is NULL");
+    if (!d_ids) return rt::errorf(RT_E_INVALID, "ids is NULL");
+    if (!d_rad) return rt::errorf(RT_E_INVALID, "out_rad is NULL");
     return rt::probe_device(ctx, scene, params, d_pos, d_tri, d_ids, n, first_sample, d_rad, d_irr, d_dir, d_casts,
                             (hipStream_t)stream);
 }
@@ -450,20 +365,20 @@ int rt_probe_radiance(rt_ctx* ctx, const rt_scene* scene, const rt_params* param
     int rc = rt::check_probe(ctx, scene, params, n);
     if (rc != RT_OK) return rc;
     if (n == 0) return RT_OK;
-    if (!pos) return rt::perr(RT_E_INVALID, "pos is NULL");
-    if (!tri) return rt::perr(RT_E_INVALID, "tri is NULL");
-    if (!ids) return rt::perr(RT_E_INVALID, "ids is NULL");
-    if (!out_rad) return rt::perr(RT_E_INVALID, "out_rad is NULL");
+    if (!pos) return rt::errorf(RT_E_INVALID, "pos is NULL");
+    if (!tri) return rt::errorf(RT_E_INVALID, "tri is NULL");
+    if (!ids) return rt::errorf(RT_E_INVALID, "ids is NULL");
+    if (!out_rad) return rt::errorf(RT_E_INVALID, "out_rad is NULL");
     const int n_surf = rt::scene_launch_view(scene).n_surf;
     for (int p = 0; p < n; ++p) {
         if (tri[p] < 0 || tri[p] >= n_surf)
-            return rt::perr(RT_E_INVALID, "tri[%d] = %d outside [0, %d)", p, tri[p], n_surf);
+            return rt::errorf(RT_E_INVALID, "tri[%d] = %d outside [0, %d)", p, tri[p], n_surf);
         if (ids[p] >= rt::kProbeMaxId)
-            return rt::perr(RT_E_INVALID, "ids[%d] = %u: ids * %d must fit 32 bits (ids < %u)", p, ids[p],
+            return rt::errorf(RT_E_INVALID, "ids[%d] = %u: ids * %d must fit 32 bits (ids < %u)", p, ids[p],
                             rt::kProbeSectors, rt::kProbeMaxId);
     }
     hipError_t e = hipSetDevice(rt::ctx_device(ctx));
-    if (e != hipSuccess) return rt::perr(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return rt::errorf(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     float *d_pos = nullptr, *d_rad = nullptr, *d_irr = nullptr, *d_dir = nullptr;
     int32_t* d_tri = nullptr;
     uint32_t* d_ids = nullptr;
@@ -498,7 +413,7 @@ int rt_probe_radiance(rt_ctx* ctx, const rt_scene* scene, const rt_params* param
     (void)hipFree(d_dir);
     (void)hipFree(d_casts);
     if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return rt::perr(RT_E_HIP, "rt_probe_radiance: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return rt::errorf(RT_E_HIP, "rt_probe_radiance: %s", hipGetErrorString(e));
     if (out_casts) *out_casts = casts;
     return RT_OK;
 }

@@ -3,10 +3,11 @@
 // estimate the map holds at the point the cast lands on.  The render forms it along camera paths
 // (rt_sarsa.hip sarsa_step); here it is formed from every volume's own position, which is value
 // iteration over the map: for volume v, sector k and sample s
-//   the first ray of rt_sarsa_bake's (v, k, s)  (Philox counter (v * 144 + k, s, 1, 73),
-//     grid_direction in the surface's shading frame, o = pos + dir * 1e-5f, d = normalize(dir)),
-//   one closest hit under the hit rule and t_scale, by k_bake's routes (the bounce-ray candidate
-//     table, the exact BVH, else the filter or the scan: the same hit, bit for bit),
+//   the first ray of rt_sarsa_bake's (v, k, s)  (sector_first_ray, rt_paths.hpp: Philox counter
+//     (v * 144 + k, s, 1, 73), grid_direction in the surface's shading frame, o = pos + dir * 1e-5f,
+//     d = normalize(dir)),
+//   one closest hit under the hit rule and t_scale, on the route leaving_route picks
+//     (closest_hit_route, rt_paths.hpp: the same hit, bit for bit, on each),
 //   target = brdf * env_light (miss), brdf * tri_lum[hit] (light), (accum[u] * kIrrScale) * brdf
 //     (surface), brdf = vol_brdf[v], u = the nearest volume the render finds for the hit point
 //     o + t * (d * t_scale) with the hit surface's stored normal (the map's search mode),
@@ -28,19 +29,12 @@
 // BVH route's stack (as in k_sarsa_render_pq).
 #include <hip/hip_runtime.h>
 
-#include <stdarg.h>
-#include <stdio.h>
-
 #include <algorithm>
 
-#include "../../include/rtmi.h"
+#include "rt_paths.hpp"
 #include "rt_sarsa_search.hpp"
 
 namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
-DeviceScene scene_launch_view(const rt_scene* s);
-int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
 int sarsa_sweep_view(rt_sarsa* sa, SarsaSweepView* out);
 int sarsa_n_volumes(const rt_sarsa* sa);
 int sarsa_device(const rt_sarsa* sa);
@@ -53,7 +47,6 @@ static_assert(kSarsaSectors == kDqnActions && kSarsaSectors == kDqnGrid * kDqnGr
               "the map's sectors are the sampler's 12 x 12 cells");
 constexpr float kIrrScale = (2.f * kPi) / ((float)(kGridRes * kGridRes));  // get_irradiance_estimate (rt_sarsa.hip)
 
-constexpr int kRouteSel = 0, kRouteTable = 1, kRouteBvh = 2;
 // Waves per SIMD the launch bounds ask for.  The stack block (30 KB per workgroup) lets five
 // workgroups share a CU; the BVH traversal's state wants the registers of four (k_sarsa_render_pq).
 __host__ __device__ constexpr int sweep_waves(int route) { return route == kRouteBvh ? 4 : 5; }
@@ -116,33 +109,16 @@ __global__ __launch_bounds__(256, sweep_waves(ROUTE)) void k_sweep(const SweepLa
         vpos = make3(P4.x, P4.y, P4.z);
         brdf = m.vol_brdf[vol];
     }
-    const int gx = sector / kDqnGrid, gy = sector - gx * kDqnGrid;
     long long sum = 0;  // the chunk's targets, fixed point 2^-32
     for (int k = 0; k < a.per_chunk; ++k) {
         const bool active = k < count;
         f3 o = vpos, d = make3(0.f, 0.f, 1.f);
-        if (active) {
-            // k_bake's first ray of sample s: the sampler's jittered direction inside the sector
-            uint32_t w[4];
-            philox4x32_10(pix, s0 + (uint32_t)k, 1u, 1u + kDqnActions / 2, a.seed_lo, a.seed_hi, w);
-            const f3 dir = grid_direction((float)gx + u01(w[0]), (float)gy + u01(w[1]), N, T, B, vpos);
-            o = make3(vpos.x + dir.x * kEps, vpos.y + dir.y * kEps, vpos.z + dir.z * kEps);
-            d = normalize(dir);
-        }
-        Hit h;
-        h.t = 0.0f;
-        h.tri = -1;
-        if constexpr (ROUTE == kRouteTable) {
-            wave_lds_sync();  // the previous search's stack accesses stay before the exact phase
-            h = closest_hit_ctab<RULE, NW>(a.scene, a.scene.ctab[RULE], tri0, o, d, a.t_scale, active, wl);
-            wave_lds_sync();  // and its LDS traffic before the next search
-        } else if constexpr (ROUTE == kRouteBvh) {
-            if (active) h = closest_hit_bvh<RULE, 64>(a.scene, o, d, a.t_scale, st);
-        } else if (active) {
-            // the filter's bounds hold for origins within origin_bound
-            const float om = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fabsf(o.z));
-            h = closest_hit_sel<RULE>(a.scene, a.use_filter && om <= a.scene.origin_bound, o, d, a.t_scale);
-        }
+        if (active) sector_first_ray(pix, s0 + (uint32_t)k, sector, N, T, B, vpos, a.seed_lo, a.seed_hi, &o, &d);
+        // (the table route's exact phase shares the stack block with the searches: the previous
+        // search's stack accesses stay before it, and its LDS traffic before the next search)
+        if constexpr (ROUTE == kRouteTable) wave_lds_sync();
+        const Hit h = closest_hit_route<RULE, ROUTE, NW, 64>(a.scene, a.use_filter, tri0, o, d, a.t_scale, active, wl, st);
+        if constexpr (ROUTE == kRouteTable) wave_lds_sync();
         // the nearest volume of a surface hit, as k_sarsa_render_pq searches it
         const bool is_surf = active && (h.tri >= 0) && (h.tri < n_surf);
         f3 pos = o;
@@ -195,15 +171,6 @@ void launch_sweep_t(const SweepLaunch& a, const SarsaMap& m, int route, hipStrea
         hipLaunchKernelGGL((k_sweep<RULE, kRouteSel, 1>), dim3(wgs), dim3(256), 0, stream, a, m);
 }
 
-int serr(int code, const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return set_error(code, buf);
-}
-
 }  // namespace
 }  // namespace rt
 
@@ -212,23 +179,18 @@ extern "C" {
 int rt_sarsa_sweep(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_params* p, int v0, int n,
                    uint32_t first_sample, int apply, uint64_t* out_casts, void* stream_) {
     using namespace rt;
-    // rt_sarsa_bake's conditions (spp_split, max_bounces and sampler are not used: not checked)
-    if (!ctx) return serr(RT_E_INVALID, "ctx is NULL");
-    if (!scene) return serr(RT_E_INVALID, "scene is NULL");
-    if (!sa) return serr(RT_E_INVALID, "sarsa is NULL");
-    if (!p) return serr(RT_E_INVALID, "params is NULL");
-    if (n < 0) return serr(RT_E_INVALID, "n < 0 (got %d)", n);
-    if (p->spp <= 0) return serr(RT_E_INVALID, "spp must be > 0 (got %d)", p->spp);
-    if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU)
-        return serr(RT_E_INVALID, "bad hit_rule %d", p->hit_rule);
+    // (spp_split, max_bounces and sampler are not used: not checked)
+    if (ctx && scene && !sa) return errorf(RT_E_INVALID, "sarsa is NULL");  // (after ctx and scene, before params)
+    int rc = check_leaving_args(ctx, scene, p, n);
+    if (rc != RT_OK) return rc;
     if (p->preset != RT_PRESET_GPU)
-        return serr(RT_E_UNSUPPORTED, "rt_sarsa_sweep casts the GPU-engine preset's rays (got preset %d)", p->preset);
+        return errorf(RT_E_UNSUPPORTED, "rt_sarsa_sweep casts the GPU-engine preset's rays (got preset %d)", p->preset);
     const int n_vol = sarsa_n_volumes(sa);
     if (v0 < 0 || n > n_vol - v0)
-        return serr(RT_E_INVALID, "volumes [%d, %lld) outside the map's [0, %d)", v0, (long long)v0 + n, n_vol);
-    if (sarsa_device(sa) != ctx_device(ctx)) return serr(RT_E_INVALID, "radiance map belongs to another device");
+        return errorf(RT_E_INVALID, "volumes [%d, %lld) outside the map's [0, %d)", v0, (long long)v0 + n, n_vol);
+    if (sarsa_device(sa) != ctx_device(ctx)) return errorf(RT_E_INVALID, "radiance map belongs to another device");
     SarsaSweepView view;
-    int rc = sarsa_sweep_view(sa, &view);  // (refuses a map that is not in RT_SARSA_TD_FRAME)
+    rc = sarsa_sweep_view(sa, &view);  // (refuses a map that is not in RT_SARSA_TD_FRAME)
     if (rc != RT_OK) return rc;
     hipStream_t stream = (hipStream_t)stream_;
     if (n == 0) {
@@ -237,21 +199,10 @@ int rt_sarsa_sweep(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_pa
         return RT_OK;
     }
     hipError_t e = hipSetDevice(ctx_device(ctx));
-    if (e != hipSuccess) return serr(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     SweepLaunch a;
-    a.scene = scene_launch_view(scene);
-    // the route, as rt_sarsa_bake picks it: every ray leaves a known surface
-    int route = a.scene.bvh_nodes != nullptr ? kRouteBvh : kRouteSel;
-    if (route == kRouteSel && a.scene.mf_frag != nullptr && a.scene.n_surf > 0 &&
-        a.scene.n_tri <= 64 * kCtabMaxWords && p->t_scale > 0.0f && p->t_scale <= kFiltMaxTScale) {
-        rc = scene_ensure_ctab(scene, p->hit_rule, p->t_scale, /*wanted=*/true);
-        if (rc != RT_OK) return rc;
-        a.scene = scene_launch_view(scene);
-        const CtabDev& T = a.scene.ctab[p->hit_rule];
-        if (T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze && p->t_scale >= T.ts_min &&
-            T.words <= (a.scene.n_tri <= 64 ? 1 : 4))
-            route = kRouteTable;
-    }
+    const int route = leaving_route(scene, p, &a.scene);
+    if (route < 0) return route;
     a.vol_surf = view.vol_surf;
     a.v0 = v0;
     a.n = n;
@@ -278,7 +229,7 @@ int rt_sarsa_sweep(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_pa
             launch_sweep_t<1>(a, view.m, route, stream);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) return serr(RT_E_HIP, "rt_sarsa_sweep: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_sarsa_sweep: %s", hipGetErrorString(e));
     if (apply) {
         rc = rt_sarsa_apply(sa, stream_);
         if (rc != RT_OK) return rc;
@@ -287,7 +238,7 @@ int rt_sarsa_sweep(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_pa
         unsigned long long casts = 0;
         e = hipStreamSynchronize(stream);
         if (e == hipSuccess) e = hipMemcpy(&casts, a.casts, sizeof(casts), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return serr(RT_E_HIP, "rt_sarsa_sweep: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return errorf(RT_E_HIP, "rt_sarsa_sweep: %s", hipGetErrorString(e));
         *out_casts = casts;
     }
     return RT_OK;

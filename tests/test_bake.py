@@ -161,35 +161,77 @@ DEFINITION_CASES = [(scene, spp, split, rule, env)
                     for env in (0.0, 0.75)] + [("cornell", 8, 4, 0, 0.5), ("cornell", 5, 1, 0, 0.0)]
 
 
+# The instantiations of k_bake (sampler x hit rule x {table of one mask word, table of four,
+# exact BVH, filter / scan}) that neither the cases above (uniform sampler; door_room's table has four
+# words, cornell's one) nor test_gpu_bake_is_invariant (the BVH at rule 1) launch, once each at 8
+# samples in 4 chunks over the first 5 and the last 3 volumes.
+# (id, scene, rule, env, sampler, t_scale or None for the default, exact BVH)
+BEYOND_T = 32768.0  # past the filter's and the tables' t_scale range: the plain scan
+INSTANTIATION_CASES = [
+    ("cornell-rule1-table1", "cornell", 1, 0.5, 0, None, False),
+    ("cornell-rule0-bvh", "cornell", 0, 0.5, 0, None, True),
+    ("cornell-rule0-filter", "cornell", 0, 0.5, 0, 128.0, False),
+    ("door_room-rule1-scan", "door_room", 1, 0.75, 0, BEYOND_T, False),
+    ("cornell-rule0-table1-cosine", "cornell", 0, 0.5, 1, None, False),
+    ("cornell-rule1-table1-cosine", "cornell", 1, 0.5, 1, None, False),
+    ("door_room-rule0-table4-cosine", "door_room", 0, 0.75, 1, None, False),
+    ("door_room-rule1-table4-cosine", "door_room", 1, 0.75, 1, None, False),
+    ("cornell-rule0-bvh-cosine", "cornell", 0, 0.5, 1, None, True),
+    ("cornell-rule1-bvh-cosine", "cornell", 1, 0.5, 1, None, True),
+    ("cornell-rule0-filter-cosine", "cornell", 0, 0.5, 1, 128.0, False),
+    ("door_room-rule1-scan-cosine", "door_room", 1, 0.75, 1, BEYOND_T, False),
+]
+DEFINITION_PARAMS = ([c + (None,) for c in DEFINITION_CASES] +
+                     [(c[1], 8, 4, c[2], c[3], c[4:]) for c in INSTANTIATION_CASES])
+DEFINITION_IDS = (["-".join(str(x) for x in c) for c in DEFINITION_CASES] + [c[0] for c in INSTANTIATION_CASES])
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("scene,spp,split,rule,env", DEFINITION_CASES)
-def test_gpu_bake_equals_its_definition(rtmi_mod, worlds, scene, spp, split, rule, env):
+@pytest.mark.parametrize("scene,spp,split,rule,env,inst", DEFINITION_PARAMS, ids=DEFINITION_IDS)
+def test_gpu_bake_equals_its_definition(rtmi_mod, gpu_ctx, worlds, scene, spp, split, rule, env, inst):
     """Q, visits and casts of a bake == the formula on rtmi.probe.radiance of the same volumes,
     bit for bit; nothing outside the range moves.  Ranges: the whole map, one volume, and
-    [7, 7 + 130) (v0 != 0, no multiple of 64)."""
+    [7, 7 + 130) (v0 != 0, no multiple of 64); for the cases that are there for the kernel they
+    launch (inst: sampler, t_scale, exact BVH), the first 5 volumes and the last 3."""
     w = worlds(scene)
     p = gpu_params(rtmi_mod, spp=spp, spp_split=split, hit_rule=rule, env_light=env)
     assert w.n > 7 + 130
-    for v0, n in ((0, w.n), (w.n - 3, 1), (7, 130)):
-        idx = np.arange(v0, v0 + n)
-        ref = w.probe(p, idx)
-        want = w.q_of(ref["rad"], idx)
-        with w.new_map() as rm:
-            casts = rm.bake(w.sc, p, v0, n)
-            q, cdf, vis, irr = rm.read()
-            ps, pc = pending(rtmi_mod, rm)
-        assert casts == ref["casts"], (v0, n)
-        assert np.array_equal(q[idx], want), (v0, n, np.abs(q[idx] - want).max())
-        assert (vis[idx] == spp).all()
-        out = np.ones(w.n, bool)
-        out[idx] = False
-        for got, before in zip((q, cdf, vis, irr), w.fresh):
-            assert np.array_equal(got[out], before[out]), (v0, n)
-        assert not ps.any() and not pc.any()
-        # a distribution over the range: a monotone CDF that ends at 1
-        assert (np.diff(cdf[idx], axis=1) >= 0).all() and np.allclose(cdf[idx, -1], 1.0, atol=1e-5)
-        if n == w.n:
-            assert (q > THRESHOLD).any(), "no sector received light: the case checks nothing"
+    ranges = ((0, w.n), (w.n - 3, 1), (7, 130))
+    sc = w.sc
+    if inst is not None:
+        sampler, t_scale, bvh = inst
+        p.sampler = sampler
+        if t_scale is not None:
+            p.t_scale = t_scale
+        ranges = ((0, 5), (w.n - 3, 3))
+        if bvh:
+            sc = rtmi_mod.Scene(gpu_ctx, w.g)
+            sc.set_accel(rtmi_mod.ACCEL_BVH)
+    lit = False
+    try:
+        for v0, n in ranges:
+            idx = np.arange(v0, v0 + n)
+            ref = w.probe(p, idx, scene=sc)
+            want = w.q_of(ref["rad"], idx)
+            with w.new_map() as rm:
+                casts = rm.bake(sc, p, v0, n)
+                q, cdf, vis, irr = rm.read()
+                ps, pc = pending(rtmi_mod, rm)
+            assert casts == ref["casts"], (v0, n)
+            assert np.array_equal(q[idx], want), (v0, n, np.abs(q[idx] - want).max())
+            assert (vis[idx] == spp).all()
+            out = np.ones(w.n, bool)
+            out[idx] = False
+            for got, before in zip((q, cdf, vis, irr), w.fresh):
+                assert np.array_equal(got[out], before[out]), (v0, n)
+            assert not ps.any() and not pc.any()
+            # a distribution over the range: a monotone CDF that ends at 1
+            assert (np.diff(cdf[idx], axis=1) >= 0).all() and np.allclose(cdf[idx, -1], 1.0, atol=1e-5)
+            lit = lit or bool((q[idx] > THRESHOLD).any())
+    finally:
+        if sc is not w.sc:
+            sc.close()
+    assert lit, "no sector received light: the case checks nothing"
 
 
 @pytest.mark.gpu

@@ -293,17 +293,37 @@ TWO_CAST_CASES = [
     ("archway-rule0-scan", "archway", 0, 0.25, 128.0, True),
     ("cornell-rule1-far", "cornell", 1, 0.5, None, True),
 ]
+# The instantiations of k_probe (sampler x hit rule x {table of one mask word, table of four,
+# exact BVH, filter / scan}) that neither the cases above (uniform sampler) nor the other tests of
+# this file launch, once each at 8 samples in 4 chunks.  One cast per path: the sampler does not
+# enter the result, the kernel it selects does.
+# (id, scene, hit rule, env_light, t_scale, far, sampler, exact BVH)
+BEYOND_T = 32768.0  # past the filter's and the tables' t_scale range: the plain scan
+INSTANTIATION_CASES = [
+    ("archway-rule0-table4", "archway", 0, 0.25, None, False, 0, False),
+    ("archway-rule1-scan", "archway", 1, 0.25, BEYOND_T, False, 0, False),
+    ("cornell-rule0-bvh", "cornell", 0, 0.0, None, False, 0, True),
+    ("cornell-rule0-cosine", "cornell", 0, 0.0, None, False, 1, False),
+    ("archway-rule0-table4-cosine", "archway", 0, 0.25, None, False, 1, False),
+    ("archway-rule1-table4-cosine", "archway", 1, 0.25, None, False, 1, False),
+    ("cornell-rule0-bvh-cosine", "cornell", 0, 0.0, None, False, 1, True),
+    ("cornell-rule1-bvh-cosine", "cornell", 1, 0.0, None, False, 1, True),
+    ("cornell-rule0-filter-cosine", "cornell", 0, 0.0, 128.0, False, 1, False),
+    ("archway-rule1-scan-cosine", "archway", 1, 0.25, BEYOND_T, False, 1, False),
+]
+TWO_CAST_PARAMS = ([c + (0, False, spp, split) for c in TWO_CAST_CASES for spp, split in [(1, 1), (5, 1), (8, 4)]] +
+                   [c + (8, 4) for c in INSTANTIATION_CASES])
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("spp,split", [(1, 1), (5, 1), (8, 4)])
-@pytest.mark.parametrize("scene,rule,env,t_scale,far", [c[1:] for c in TWO_CAST_CASES],
-                         ids=[c[0] for c in TWO_CAST_CASES])
-def test_two_cast_paths_bit_for_bit(rtmi_mod, oracle_mod, gpu_ctx, worlds, scene, rule, env, t_scale, far, spp, split):
+@pytest.mark.parametrize("scene,rule,env,t_scale,far,sampler,bvh,spp,split", [c[1:] for c in TWO_CAST_PARAMS],
+                         ids=[f"{c[0]}-{c[-2]}-{c[-1]}" for c in TWO_CAST_PARAMS])
+def test_two_cast_paths_bit_for_bit(rtmi_mod, oracle_mod, gpu_ctx, worlds, scene, rule, env, t_scale, far, sampler, bvh,
+                                    spp, split):
     w = worlds(scene)
     first = 3
     kw = {} if t_scale is None else {"t_scale": t_scale}
-    p = gpu_params(rtmi_mod, spp=spp, spp_split=split, max_bounces=2, hit_rule=rule, env_light=env, **kw)
+    p = gpu_params(rtmi_mod, spp=spp, spp_split=split, max_bounces=2, hit_rule=rule, env_light=env, sampler=sampler, **kw)
     pos = w.pos
     if far:
         pos = (w.pos - f32(20.0) * oracle_mod.normals(w.geom.all_triangles())[w.tri]).astype(np.float32)
@@ -312,12 +332,20 @@ def test_two_cast_paths_bit_for_bit(rtmi_mod, oracle_mod, gpu_ctx, worlds, scene
     if env > 0:
         assert (rad == f32(env)).all(axis=-1).any(), "no first cast missed: env_light is not exercised"
     assert rad.any()
-    for n in (1, 3, 5):
-        got = rtmi_mod.probe.radiance(gpu_ctx, w.scene, p, pos[:n], w.tri[:n], w.ids[:n], first_sample=first)
-        assert got["casts"] == n * SECTORS * spp
-        k = ok[:n]
-        assert np.array_equal(bits(got["rad"])[k], bits(rad[:n])[k])
-        assert np.array_equal(bits(got["irr"])[k], bits(irr[:n])[k])
+    scene_ = w.scene
+    if bvh:
+        scene_ = rtmi_mod.Scene(gpu_ctx, w.geom)
+        scene_.set_accel(rtmi_mod.ACCEL_BVH)
+    try:
+        for n in (1, 3, 5):
+            got = rtmi_mod.probe.radiance(gpu_ctx, scene_, p, pos[:n], w.tri[:n], w.ids[:n], first_sample=first)
+            assert got["casts"] == n * SECTORS * spp
+            k = ok[:n]
+            assert np.array_equal(bits(got["rad"])[k], bits(rad[:n])[k])
+            assert np.array_equal(bits(got["irr"])[k], bits(irr[:n])[k])
+    finally:
+        if bvh:
+            scene_.close()
 
 
 @pytest.mark.gpu
