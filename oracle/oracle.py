@@ -158,6 +158,20 @@ def pass_masks(tri, orig, direction, t_scale, hit_rule):
     return out
 
 
+def pass_t(tri, orig, direction, t_scale, hit_rule):
+    """(n_rays, n_tri) float32: the t of each triangle's exact test under the rule's arithmetic
+    and pass conditions (no closest-hit window), +inf where it does not pass (orc_pass_t)."""
+    t_all = np.ascontiguousarray(tri, np.float32).reshape(-1, 9)
+    o = np.ascontiguousarray(orig, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+    n, nt = o.shape[0], t_all.shape[0]
+    out = np.zeros((n, nt), np.float32)
+    L = lib()
+    L.orc_pass_t.argtypes = [_FP, ctypes.c_int, _FP, _FP, ctypes.c_int, ctypes.c_float, ctypes.c_int, _FP]
+    L.orc_pass_t(_f(t_all), nt, _f(o), _f(d), n, t_scale, hit_rule, _f(out))
+    return out
+
+
 def primary_hits(tri, n_surf, n_light, cam, params, rect, s0, s1):
     """Triangle index (-1 = miss) hit by the camera ray of every pixel of rect = (x, y, w, h)
     and sample in [s0, s1): array (h, w, s1 - s0)."""

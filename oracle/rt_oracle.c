@@ -302,6 +302,33 @@ typedef struct {
     int tri;       /* unified triangle index, -1 none */
 } hit_t;
 
+/* The test of triangle i without the closest-hit window: 1 and *t_out if it passes the rule's
+ * detA, t, u, v conditions (rule 0: through inv = 1 / detA, and t > 1e-5; rule 1: divided
+ * directly), else 0.  nD = -(d * t_scale). */
+static inline int tri_pass_t(const float *tri, int i, v3 o, v3 nD, int hit_rule, float *t_out) {
+    v3 v0 = vtx(tri, i, 0), v1 = vtx(tri, i, 1), v2 = vtx(tri, i, 2);
+    v3 e1 = mk(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z);
+    v3 e2 = mk(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z);
+    v3 b = mk(o.x - v0.x, o.y - v0.y, o.z - v0.z);
+    float detA = det3(nD, e1, e2);
+    if (!(detA != 0.0f)) return 0;
+    float t, u, v;
+    if (hit_rule == 0) {
+        float inv = 1.0f / detA;
+        t = det3(b, e1, e2) * inv;
+        u = det3(nD, b, e2) * inv;
+        v = det3(nD, e1, b) * inv;
+        if (!(t >= 0.0f && u >= 0.0f && v >= 0.0f && (u + v) <= 1.0f && t > 1e-5f)) return 0;
+    } else {
+        t = det3(b, e1, e2) / detA;
+        u = det3(nD, b, e2) / detA;
+        v = det3(nD, e1, b) / detA;
+        if (!(t >= 0.0f && u >= 0.0f && v >= 0.0f && (u + v) <= 1.0f)) return 0;
+    }
+    *t_out = t;
+    return 1;
+}
+
 /* mask (NULL: every triangle): only the triangles whose bit is set are tested, in index order */
 static hit_t closest_hit_masked(const orc_scene *sc, v3 o, v3 d, float t_scale, int hit_rule,
                                 const uint64_t *mask) {
@@ -313,29 +340,10 @@ static hit_t closest_hit_masked(const orc_scene *sc, v3 o, v3 d, float t_scale, 
     int n = sc->n_surf + sc->n_light;
     for (int i = 0; i < n; i++) {
         if (mask && !((mask[i / 64] >> (i % 64)) & 1u)) continue;
-        v3 v0 = vtx(sc->tri, i, 0), v1 = vtx(sc->tri, i, 1), v2 = vtx(sc->tri, i, 2);
-        v3 e1 = mk(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z);
-        v3 e2 = mk(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z);
-        v3 b = mk(o.x - v0.x, o.y - v0.y, o.z - v0.z);
-        float detA = det3(nD, e1, e2);
-        if (!(detA != 0.0f)) continue;
-        float t, u, v;
-        if (hit_rule == 0) {
-            float inv = 1.0f / detA;
-            t = det3(b, e1, e2) * inv;
-            u = det3(nD, b, e2) * inv;
-            v = det3(nD, e1, b) * inv;
-            if (t >= 0.0f && u >= 0.0f && v >= 0.0f && (u + v) <= 1.0f &&
-                t < h.t + 1e-5f && t > 1e-5f) {
-                h.t = t; h.tri = i;
-            }
-        } else {
-            t = det3(b, e1, e2) / detA;
-            u = det3(nD, b, e2) / detA;
-            v = det3(nD, e1, b) / detA;
-            if (t >= 0.0f && u >= 0.0f && v >= 0.0f && (u + v) <= 1.0f && t < h.t) {
-                h.t = t; h.tri = i;
-            }
+        float t;
+        if (!tri_pass_t(sc->tri, i, o, nD, hit_rule, &t)) continue;
+        if (hit_rule == 0 ? (t < h.t + 1e-5f) : (t < h.t)) {
+            h.t = t; h.tri = i;
         }
     }
     return h;
@@ -436,6 +444,26 @@ ORC_API void orc_pass_masks(const float *tri, int n_tri, const float *orig, cons
             }
             if (t >= 0.0f && u >= 0.0f && v >= 0.0f && (u + v) <= 1.0f && (hit_rule != 0 || t > 1e-5f))
                 m[i / 64] |= 1ull << (i % 64);
+        }
+    }
+}
+
+/* out[r * n_tri + i] = the t of triangle i's test for ray r under the rule's arithmetic and
+ * pass conditions (closest_hit_masked's per-triangle code, no closest-hit window), +inf if
+ * it does not pass: what a test needs to count the triangles below a ray's rule-0 cut or at
+ * bit-equal t without restating the arithmetic. */
+ORC_API void orc_pass_t(const float *tri, int n_tri, const float *orig, const float *dir, int n,
+                        float t_scale, int hit_rule, float *out) {
+    #pragma omp parallel for schedule(static)
+    for (int r = 0; r < n; r++) {
+        v3 o = mk(orig[r * 3], orig[r * 3 + 1], orig[r * 3 + 2]);
+        v3 d = mk(dir[r * 3], dir[r * 3 + 1], dir[r * 3 + 2]);
+        v3 D = mk(d.x * t_scale, d.y * t_scale, d.z * t_scale);
+        v3 nD = mk(-D.x, -D.y, -D.z);
+        float *row = out + (size_t)r * n_tri;
+        for (int i = 0; i < n_tri; i++) {
+            float t;
+            row[i] = tri_pass_t(tri, i, o, nD, hit_rule, &t) ? t : INFINITY;
         }
     }
 }
