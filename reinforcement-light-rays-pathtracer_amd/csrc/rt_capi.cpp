@@ -18,7 +18,7 @@
 
 #include "../../include/rtmi.h"
 #include "rt_cull.hpp"
-#include "rt_internal.hpp"
+#include "rt_hostframe.hpp"
 
 namespace {
 
@@ -1297,26 +1297,20 @@ int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt
         return errorf(RT_E_INVALID, "rectangle outside the image");
     rc = set_device(ctx);
     if (rc != RT_OK) return rc;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < h; by += 16)
-        for (int bx = 0; bx < w; bx += 16) blocks.push_back({x0 + bx, y0 + by, bx, by});
-    rt::BlockDesc* d_blocks = nullptr;
-    float* d_out = nullptr;
-    unsigned long long* d_casts = nullptr;
-    const size_t out_bytes = sizeof(float) * 3 * (size_t)w * (size_t)h;
     rc = rt::scene_ensure_ctab(scene, params->hit_rule, params->t_scale,
                                rt::ctab_wanted(scene, cam, params, rt::kCtabForRender));
     if (rc != RT_OK) return rc;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_casts, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_casts, 0, sizeof(unsigned long long));
-    if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
+    float* d_out;
+    unsigned long long* d_casts;
+    unsigned long long casts = 0;
+    rt::HostFrame f(x0, y0, w, h);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * (size_t)w * (size_t)h);
+    f.out(&d_casts, &casts, sizeof(casts), 0);
+    hipError_t e = f.begin();
     if (e == hipSuccess) {
         rt::RenderLaunch a = make_launch(scene, cam, params);
-        a.blocks = d_blocks;
-        a.n_blocks = (int)blocks.size();
+        a.blocks = f.blocks();
+        a.n_blocks = f.n_blocks();
         a.clip_x1 = x0 + w;
         a.clip_y1 = y0 + h;
         a.out_pitch = w;
@@ -1329,16 +1323,9 @@ int rt_render(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt
             e = rt::launch_render(a, 0, &cf);
         }
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_rgb, d_out, out_bytes, hipMemcpyDeviceToHost);
-    unsigned long long casts = 0;
-    if (e == hipSuccess) e = hipMemcpy(&casts, d_casts, sizeof(casts), hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(d_casts);
-    if (e != hipSuccess) return errorf(RT_E_HIP, "rt_render: %s", hipGetErrorString(e));
-    if (out_ray_casts) *out_ray_casts = casts;
-    return RT_OK;
+    rc = f.finish(RT_OK, e, "rt_render");
+    if (rc == RT_OK && out_ray_casts) *out_ray_casts = casts;
+    return rc;
 }
 
 int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam,
@@ -1451,9 +1438,7 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
         return errorf(RT_E_INVALID, "rectangle outside the image");
     rc = set_device(ctx);
     if (rc != RT_OK) return rc;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < h; by += 16)
-        for (int bx = 0; bx < w; bx += 16) blocks.push_back({x0 + bx, y0 + by, bx, by});
+    rt::HostFrame f(x0, y0, w, h);  // (the block list alone: the masks are the context's)
     // k_cull_ps covers what k_render_ps's launch condition covers: the CPU preset, scenes of
     // <= 64 * kRenderCullWords triangles (wider scenes would get truncated masks)
     if (params->preset != RT_PRESET_CPU) return errorf(RT_E_UNSUPPORTED, "the primary-ray cull is CPU-preset only");
@@ -1462,7 +1447,7 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
                     64 * rt::kRenderCullWords, scene->dev.n_tri);
     rt::RenderLaunch a = make_launch(scene, cam, params);
     if (!a.use_filter) return errorf(RT_E_UNSUPPORTED, "no filter records for this scene and camera");
-    a.n_blocks = (int)blocks.size();
+    a.n_blocks = f.n_blocks();
     a.clip_x1 = x0 + w;
     a.clip_y1 = y0 + h;
     const int64_t words = (int64_t)a.n_blocks * a.split * 4 * rt::kRenderCullWords;
@@ -1471,21 +1456,17 @@ int rt_cull_masks_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* ca
         *n_words = words;
         return errorf(RT_E_INVALID, "out holds %lld words, %lld needed", cap, (long long)words);
     }
-    rt::BlockDesc* d_blocks = nullptr;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
+    hipError_t e = f.begin();
     if (e == hipSuccess) {
-        a.blocks = d_blocks;
-        rc = rt::ctx_cull(ctx, &a);
-        if (rc != RT_OK) e = hipErrorOutOfMemory;
+        a.blocks = f.blocks();
+        if (rt::ctx_cull(ctx, &a) != RT_OK) e = hipErrorOutOfMemory;
     }
     rt::CullLaunch cf{};
     if (e == hipSuccess) rt::ctx_cull_forms(ctx, scene, a, 0, &cf);
     if (e == hipSuccess) e = rt::launch_cull(a, 0, &cf);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out, a.cull, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
+    rc = f.finish(RT_OK, e, "rt_cull_masks_device");  // (synchronises)
+    if (rc != RT_OK) return rc;
+    e = hipMemcpy(out, a.cull, sizeof(uint64_t) * (size_t)words, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return errorf(RT_E_HIP, "rt_cull_masks_device: %s", hipGetErrorString(e));
     *n_words = words;
     return RT_OK;

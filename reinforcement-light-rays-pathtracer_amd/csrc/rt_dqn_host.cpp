@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/rtmi.h"
-#include "rt_internal.hpp"
+#include "rt_hostframe.hpp"
 
 namespace rt {
 int set_error(int code, const char* msg);
@@ -492,7 +492,7 @@ int run_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_came
 
 int check_dqn_params(const rt_params* p) {
     if (!p) return err(RT_E_INVALID, "params is NULL");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return err(RT_E_INVALID, "bad image size / spp");
+    if (rt::params_size_bad(p)) return err(RT_E_INVALID, "bad image size / spp");
     if (p->max_bounces < 1) return err(RT_E_INVALID, "max_bounces must be >= 1");
     if (p->preset != RT_PRESET_GPU || p->hit_rule != RT_HIT_RULE_GPU)
         return err(RT_E_UNSUPPORTED, "the DQN renderer implements the GPU-engine preset (hit rule GPU)");
@@ -503,7 +503,7 @@ int check_dqn_params(const rt_params* p) {
 int check_dqn_view_params(const rt_params* p, const rt_dqn_view_opts* o) {
     if (!p || !o) return err(RT_E_INVALID, "NULL argument");
     if (o->mode != RT_DQN_VIEW_IRRADIANCE) return err(RT_E_INVALID, "bad view mode");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return err(RT_E_INVALID, "bad image size / spp");
+    if (rt::params_size_bad(p)) return err(RT_E_INVALID, "bad image size / spp");
     if (p->preset != RT_PRESET_GPU || p->hit_rule != RT_HIT_RULE_GPU)
         return err(RT_E_UNSUPPORTED, "the Q-network view implements the GPU-engine preset (hit rule GPU)");
     return RT_OK;
@@ -622,46 +622,20 @@ int rt_render_dqn_view(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, co
     if (rc != RT_OK) return rc;
     RT_HIPE(hipSetDevice(rt::ctx_device(ctx)));
     const int w = params->width, h = params->height;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < h; by += 16)
-        for (int bx = 0; bx < w; bx += 16) blocks.push_back({bx, by, bx, by});
     const size_t np = (size_t)w * h;
-    rt::BlockDesc* d_blocks = nullptr;
-    float* d_out = nullptr;
+    float* d_out;
     rt::DqnView aov;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
-    if (e == hipSuccess && out_tri) e = hipMalloc(&aov.out_tri, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_pos) e = hipMalloc(&aov.out_pos, sizeof(float) * 3 * np);
-    if (e == hipSuccess && out_q) e = hipMalloc(&aov.out_q, sizeof(float) * rt::kDqnActions * np);
-    if (e == hipSuccess && out_action) e = hipMalloc(&aov.out_action, sizeof(int32_t) * np);
+    rt::HostFrame f(0, 0, w, h);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * np);
+    f.out(&aov.out_tri, out_tri, sizeof(int32_t) * np);
+    f.out(&aov.out_pos, out_pos, sizeof(float) * 3 * np);
     // pixels without a surface hit: Q zeros, action -1 (the kernels write the surface pixels)
-    if (e == hipSuccess && out_q) e = hipMemset(aov.out_q, 0, sizeof(float) * rt::kDqnActions * np);
-    if (e == hipSuccess && out_action) e = hipMemset(aov.out_action, 0xff, sizeof(int32_t) * np);
+    f.out(&aov.out_q, out_q, sizeof(float) * rt::kDqnActions * np, 0);
+    f.out(&aov.out_action, out_action, sizeof(int32_t) * np, 0xff);
+    const hipError_t e = f.begin();
     if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = run_dqn_view(ctx, scene, dqn, cam, params, opts, first_sample, d_blocks, (int)blocks.size(), w, h, w,
-                          d_out, aov, 0);
-        if (rc == RT_OK) e = hipDeviceSynchronize();
-    }
-    const bool ok = rc == RT_OK;
-    if (ok && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    if (ok && e == hipSuccess && out_tri) e = hipMemcpy(out_tri, aov.out_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (ok && e == hipSuccess && out_pos) e = hipMemcpy(out_pos, aov.out_pos, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    if (ok && e == hipSuccess && out_q)
-        e = hipMemcpy(out_q, aov.out_q, sizeof(float) * rt::kDqnActions * np, hipMemcpyDeviceToHost);
-    if (ok && e == hipSuccess && out_action)
-        e = hipMemcpy(out_action, aov.out_action, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(aov.out_tri);
-    (void)hipFree(aov.out_pos);
-    (void)hipFree(aov.out_q);
-    (void)hipFree(aov.out_action);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_dqn_view: ") + hipGetErrorString(e));
-    return RT_OK;
+        rc = run_dqn_view(ctx, scene, dqn, cam, params, opts, first_sample, f.blocks(), f.n_blocks(), w, h, w, d_out, aov, 0);
+    return f.finish(rc, e, "rt_render_dqn_view");
 }
 
 int rt_render_dqn_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam,
@@ -689,33 +663,18 @@ int rt_render_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const r
     if (w <= 0 || h <= 0 || x0 < 0 || y0 < 0 || x0 + w > params->width || y0 + h > params->height)
         return err(RT_E_INVALID, "rectangle outside the image");
     RT_HIPE(hipSetDevice(rt::ctx_device(ctx)));
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < h; by += 16)
-        for (int bx = 0; bx < w; bx += 16) blocks.push_back({x0 + bx, y0 + by, bx, by});
-    rt::BlockDesc* d_blocks = nullptr;
-    float* d_out = nullptr;
-    uint64_t* d_casts = nullptr;
-    const size_t ob = sizeof(float) * 3 * (size_t)w * h;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
-    if (e == hipSuccess) e = hipMalloc(&d_casts, sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMemset(d_casts, 0, sizeof(uint64_t));
-    if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = run_dqn(ctx, scene, dqn, cam, params, d_blocks, (int)blocks.size(), x0 + w, y0 + h, w, d_out, d_casts, 0);
-        if (rc == RT_OK) e = hipDeviceSynchronize();
-    }
+    float* d_out;
+    uint64_t* d_casts;
     uint64_t casts = 0;
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, ob, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(&casts, d_casts, sizeof(casts), hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(d_casts);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_dqn: ") + hipGetErrorString(e));
-    if (out_ray_casts) *out_ray_casts = casts;
-    return RT_OK;
+    rt::HostFrame f(x0, y0, w, h);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * (size_t)w * h);
+    f.out(&d_casts, &casts, sizeof(casts), 0);
+    const hipError_t e = f.begin();
+    if (e == hipSuccess)
+        rc = run_dqn(ctx, scene, dqn, cam, params, f.blocks(), f.n_blocks(), x0 + w, y0 + h, w, d_out, d_casts, 0);
+    rc = f.finish(rc, e, "rt_render_dqn");
+    if (rc == RT_OK && out_ray_casts) *out_ray_casts = casts;
+    return rc;
 }
 
 }  // extern "C"

@@ -16,9 +16,9 @@
 // colours (glyph_colours).  The file reader is rt_selected_read (rt_sarsa_host.cpp, the Q-table
 // parser).
 //
-// k_glyph_view: k_sarsa_view's lane layout (one lane per (pixel, chunk), a wave over 16 x 4
-// pixels at split 1, the shuffle fold of the chunk sums) and k_probe's LDS stack column for the
-// BVH walks.  Per sample two casts of the same camera ray -- the scene's (k_sarsa_view's route:
+// k_glyph_view: the camera-hit frame of rt_view.hpp (one lane per (pixel, chunk), a wave over
+// 16 x 4 pixels at split 1, the shuffle fold of the chunk sums) and k_probe's LDS stack column for
+// the BVH walks.  Per sample two casts of the same camera ray -- the scene's (the frame's routes:
 // the rectangle cull or the scan; the scene's BVH where its accel mode turns it on) and the
 // glyph soup's (its BVH, or the plain scan: RTMI_GLYPH_BVH=0) -- and the winner rule of the
 // scan over the soup "scene surfaces, glyph triangles, lights".  Every route gives the same
@@ -36,13 +36,11 @@
 #include <vector>
 
 #include "../../include/rtmi.h"
-#include "rt_trace.hpp"
+#include "rt_hostframe.hpp"
+#include "rt_view.hpp"
 
 namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
 const DeviceScene& scene_device(const rt_scene* s);
-DeviceScene scene_launch_view(const rt_scene* s);
 int ctx_blocks(rt_ctx* ctx, const int32_t* tiles, int n_tiles, int tile_size, int width, int height,
                const BlockDesc** d_blocks, int* n_blocks);
 RenderLaunch render_launch(const rt_scene* scene, const rt_camera* cam, const rt_params* p);
@@ -57,9 +55,8 @@ static_assert(kGlyphSectors == RT_GLYPH_SECTORS && kGlyphTris == RT_GLYPH_TRIS &
 // The view: see the head of the file.  SBVH / GBVH: the scene's / the glyph soup's cast takes
 // the exact BVH (closest_hit_bvh, its stack in the lane's LDS column; the two walks run one
 // after the other and share it).  cull: the scene's cast takes the cull of the wave's pixel
-// rectangle (launch_glyph_view, as launch_sarsa_view).  Every lane of a wave that has a pixel
-// runs all per_chunk trips: a lane outside the image or the tile casts nothing but stays for
-// the cull's ballots and the fold's shuffles.
+// rectangle (launch_glyph_view: view_cull_wanted).  The lane layout, the trips and the fold are
+// rt_view.hpp's.
 // out_tri / out_glyph / out_sector / out_t (each may be null): the scene's own hit (-1: miss),
 // the winning glyph and its sector (-1: no glyph won) and the winner's t (+inf: a miss) of
 // sample a.sample_base, by output pixel.
@@ -68,45 +65,27 @@ __global__ __launch_bounds__(256) void k_glyph_view(const RenderLaunch a, const 
                                                     int32_t* __restrict__ out_tri, int32_t* __restrict__ out_glyph,
                                                     int32_t* __restrict__ out_sector, float* __restrict__ out_t) {
     __shared__ int s_stk[(SBVH || GBVH) ? kBvhMaxDepth * 256 : 1];
-    const int lg = a.split_log2;
-    const BlockDesc blk = a.blocks[blockIdx.x >> lg];
-    const int part = blockIdx.x & (a.split - 1);
-    const int q = (part << (8 - lg)) + ((int)threadIdx.x >> lg);
-    const int chunk = threadIdx.x & (a.split - 1);
-    const int lane = threadIdx.x & 63;
-    const int lx = q & 15, ly = q >> 4;
-    const int px = blk.px0 + lx, py = blk.py0 + ly;
-    const bool valid = (px < a.clip_x1) && (py < a.clip_y1);
-    if (__ballot(valid) == 0ull) return;  // (whole waves outside the image)
-    const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
+    ViewLane v;
+    if (!view_lane(a, &v)) return;
     const float4* __restrict__ shade = a.scene.shade;
     const int n_surf = a.scene.n_surf;
     int* const stk = s_stk + ((SBVH || GBVH) ? (int)threadIdx.x : 0);
     const f3 o = make3(a.cam_x, a.cam_y, a.cam_z);
-    uint64_t cm[kRenderCullWords] = {0ull, 0ull, 0ull, 0ull};
-    if (!SBVH && cull) wave_candidates<1>(a, valid, px, py, lane, cm);
+    uint64_t cm[kRenderCullWords];
+    view_cull<1>(a, v, !SBVH && cull, cm);
     // what the pixel shows where no glyph wins and a base was given (the same for every sample)
     f3 base = make3(0.f, 0.f, 0.f);
-    if (valid && g.base != nullptr) {
-        const float* b = g.base + (size_t)pix * 3;
+    if (v.valid && g.base != nullptr) {
+        const float* b = g.base + (size_t)v.pix * 3;
         base = make3(b[0], b[1], b[2]);
     }
-    f3 acc = make3(0.f, 0.f, 0.f);
-    for (int k = 0; k < a.per_chunk; ++k) {
-        const int s = chunk * a.per_chunk + k;
-        Hit hs, hg;
-        hs.t = hg.t = 999999.0f;
-        hs.tri = hg.tri = -1;
-        f3 d = make3(0.f, 0.f, 1.f);
-        if (valid) {
-            float r1, r2;
-            draw2(pix, a.sample_base + (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
-            camera_ray<1>(a, px, py, r1, r2, &d);
-            if constexpr (SBVH)
-                hs = closest_hit_bvh<1>(a.scene, o, d, a.t_scale, stk);
-            else
-                hs = cull ? view_hit_culled<1>(a.scene, cm, o, d, a.t_scale)
-                          : closest_hit<1>(a.scene.isect, a.scene.n_tri, o, d, a.t_scale);
+    view_frame(a, v, [&](int s, bool first) {
+        f3 d;
+        const Hit hs = view_camera_hit<1, SBVH>(a, v, s, cull, cm, o, stk, &d);
+        Hit hg;
+        hg.t = 0.0f;
+        hg.tri = -1;
+        if (v.valid) {
             if constexpr (GBVH)
                 hg = closest_hit_bvh<1>(g.soup, o, d, a.t_scale, stk);
             else
@@ -124,47 +103,30 @@ __global__ __launch_bounds__(256) void k_glyph_view(const RenderLaunch a, const 
                 const float f = 0.25f + 0.75f * fmaxf(-((nq.x * d.x + nq.y * d.y) + nq.z * d.z), 0.f);
                 c = make3(c.x * f, c.y * f, c.z * f);
             }
-        } else if (valid) {
+        } else if (v.valid) {
             if (g.base != nullptr) {
                 c = base;
             } else if (hs.tri < 0) {
                 c = make3(a.env_light, a.env_light, a.env_light);
             } else {  // a surface's albedo, a light's emission
-                const float4 v = shade[hs.tri * kShadeF4 + (hs.tri < n_surf ? 4 : 3)];
-                c = make3(v.x, v.y, v.z);
+                const float4 e = shade[hs.tri * kShadeF4 + (hs.tri < n_surf ? 4 : 3)];
+                c = make3(e.x, e.y, e.z);
             }
         }
-        acc.x = acc.x + c.x;
-        acc.y = acc.y + c.y;
-        acc.z = acc.z + c.z;
-        if (k == 0 && chunk == 0 && valid) {
-            const size_t op = (size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx);
-            if (out_tri != nullptr) out_tri[op] = hs.tri;
+        if (first) {
+            const size_t op = v.op(a);
+            view_write_tri(op, out_tri, hs.tri);
             if (out_glyph != nullptr) out_glyph[op] = gwin ? hg.tri / kGlyphTris : -1;
             if (out_sector != nullptr) out_sector[op] = gwin ? (hg.tri % kGlyphTris) >> 1 : -1;
             if (out_t != nullptr) out_t[op] = gwin ? hg.t : (hs.tri >= 0 ? hs.t : __builtin_inff());
         }
-    }
-    const int fbase = lane & ~(a.split - 1);
-    f3 tot = acc;
-    for (int k = 1; k < a.split; ++k) {
-        const float vx = __shfl(acc.x, fbase + k, 64);
-        const float vy = __shfl(acc.y, fbase + k, 64);
-        const float vz = __shfl(acc.z, fbase + k, 64);
-        tot.x = tot.x + vx;
-        tot.y = tot.y + vy;
-        tot.z = tot.z + vz;
-    }
-    if (valid && chunk == 0) {
-        const float fs = (float)a.spp;
-        float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
-        store_rgb(dst, tot.x / fs, tot.y / fs, tot.z / fs);
-    }
+        return c;
+    });
 }
 
 }  // namespace
 
-// the scene's camera rays take the rectangle cull where launch_sarsa_view takes it, or the
+// the scene's camera rays take the rectangle cull where view_cull_wanted says, or the
 // scene's BVH when the launch's view of the scene carries one
 hipError_t launch_glyph_view(const RenderLaunch& a, const GlyphSet& g, int32_t* out_tri, int32_t* out_glyph,
                              int32_t* out_sector, float* out_t, hipStream_t stream) {
@@ -172,12 +134,10 @@ hipError_t launch_glyph_view(const RenderLaunch& a, const GlyphSet& g, int32_t* 
     if (a.out == nullptr || a.hit_rule != 1) return hipErrorInvalidValue;
     if (g.soup.n_tri > 0 && (g.soup.isect == nullptr || g.colour == nullptr || g.qnormal == nullptr))
         return hipErrorInvalidValue;
-    if (a.split < 1 || a.split > 64 || (1 << a.split_log2) != a.split || a.per_chunk * a.split != a.spp)
-        return hipErrorInvalidValue;
+    if (!view_split_ok(a)) return hipErrorInvalidValue;
     const bool sbvh = a.scene.bvh_nodes != nullptr;
     const bool gbvh = g.soup.n_tri > 0 && g.soup.bvh_nodes != nullptr;
-    const int cull = (!sbvh && a.use_filter && a.scene.filt != nullptr && a.scene.n_tri <= 64 * kRenderCullWords &&
-                      a.cos_x == 1.0f && a.sin_x == 0.0f) ? 1 : 0;
+    const int cull = !sbvh && view_cull_wanted(a);
     const dim3 grid((unsigned)(a.n_blocks * a.split));
     KernelTimer kt(KT_SARSA_VIEW, stream);
     if (sbvh && gbvh)
@@ -321,11 +281,8 @@ int upload_f4(float4* dst, const float* src, size_t entries) {
 // what the view refuses before any device work: values first (RT_E_INVALID), then the engine
 int check_view_params(const rt_params* p) {
     if (!p) return err(RT_E_INVALID, "params is NULL");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return err(RT_E_INVALID, "bad image size / spp");
-    const int split = p->spp_split <= 0 ? 1 : p->spp_split;
-    if (split > 64 || (split & (split - 1)) != 0) return err(RT_E_INVALID, "spp_split must be a power of two <= 64");
-    if (p->spp % split != 0) return err(RT_E_INVALID, "spp_split does not divide spp");
-    if ((int64_t)p->width * (int64_t)p->height > (int64_t)1 << 31) return err(RT_E_INVALID, "image too large");
+    if (rt::params_size_bad(p)) return err(RT_E_INVALID, "bad image size / spp");
+    if (const char* why = rt::params_split_refusal(p)) return err(RT_E_INVALID, why);
     if (p->preset != RT_PRESET_GPU) return err(RT_E_UNSUPPORTED, "the glyph view implements the GPU-engine preset");
     if (p->hit_rule != RT_HIT_RULE_GPU) return err(RT_E_UNSUPPORTED, "the glyph view implements the GPU engine's hit rule");
     return RT_OK;
@@ -343,13 +300,7 @@ int view_frame(const rt_scene* scene, const rt_glyphs* gl, const rt_camera* cam,
                int n_blocks, int out_pitch, float* d_out, int32_t* d_tri, int32_t* d_glyph, int32_t* d_sector, float* d_t,
                hipStream_t stream) {
     rt::RenderLaunch a = rt::render_launch(scene, cam, p);
-    a.blocks = d_blocks;
-    a.n_blocks = n_blocks;
-    a.clip_x1 = p->width;
-    a.clip_y1 = p->height;
-    a.out_pitch = out_pitch;
-    a.out = d_out;
-    a.sample_base = first_sample;
+    rt::fill_view_launch(&a, p, d_blocks, n_blocks, out_pitch, d_out, first_sample);
     rt::GlyphSet g;  // (an empty set: a soup of no triangles)
     if (gl->mesh) g.soup = glyph_bvh_wanted() ? rt::scene_launch_view(gl->mesh) : rt::scene_device(gl->mesh);
     g.colour = gl->d_colour;
@@ -462,45 +413,21 @@ int rt_render_glyph_view(rt_ctx* ctx, const rt_scene* scene, const rt_glyphs* gl
     if (gl->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "the glyph set belongs to another device");
     RT_HIPG(hipSetDevice(gl->device));
     const int W = params->width, H = params->height;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < H; by += 16)
-        for (int bx = 0; bx < W; bx += 16) blocks.push_back({bx, by, bx, by});
-    rt::BlockDesc* d_blocks = nullptr;
-    float *d_out = nullptr, *d_base = nullptr, *d_t = nullptr;
-    int32_t *d_tri = nullptr, *d_glyph = nullptr, *d_sector = nullptr;
     const size_t np = (size_t)W * H;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
-    if (e == hipSuccess && base_rgb) e = hipMalloc(&d_base, sizeof(float) * 3 * np);
-    if (e == hipSuccess && out_tri) e = hipMalloc(&d_tri, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_glyph) e = hipMalloc(&d_glyph, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_sector) e = hipMalloc(&d_sector, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_t) e = hipMalloc(&d_t, sizeof(float) * np);
+    float *d_out, *d_base, *d_t;
+    int32_t *d_tri, *d_glyph, *d_sector;
+    rt::HostFrame f(0, 0, W, H);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * np);
+    f.in(&d_base, base_rgb, sizeof(float) * 3 * np);
+    f.out(&d_tri, out_tri, sizeof(int32_t) * np);
+    f.out(&d_glyph, out_glyph, sizeof(int32_t) * np);
+    f.out(&d_sector, out_sector, sizeof(int32_t) * np);
+    f.out(&d_t, out_t, sizeof(float) * np);
+    const hipError_t e = f.begin();
     if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess && base_rgb) e = hipMemcpy(d_base, base_rgb, sizeof(float) * 3 * np, hipMemcpyHostToDevice);
-    rc = RT_OK;
-    if (e == hipSuccess)
-        rc = view_frame(scene, gl, cam, params, opts, first_sample, d_base, d_blocks, (int)blocks.size(), W, d_out, d_tri,
+        rc = view_frame(scene, gl, cam, params, opts, first_sample, d_base, f.blocks(), f.n_blocks(), W, d_out, d_tri,
                         d_glyph, d_sector, d_t, 0);
-    if (rc == RT_OK && e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_tri) e = hipMemcpy(out_tri, d_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_glyph)
-        e = hipMemcpy(out_glyph, d_glyph, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_sector)
-        e = hipMemcpy(out_sector, d_sector, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_t) e = hipMemcpy(out_t, d_t, sizeof(float) * np, hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(d_base);
-    (void)hipFree(d_tri);
-    (void)hipFree(d_glyph);
-    (void)hipFree(d_sector);
-    (void)hipFree(d_t);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_glyph_view: ") + hipGetErrorString(e));
-    return RT_OK;
+    return f.finish(rc, e, "rt_render_glyph_view");
 }
 
 int rt_render_glyph_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_glyphs* gl, const rt_camera* cam,

@@ -265,6 +265,33 @@ inline int filter_usable(const DeviceScene& s, float cx, float cy, float cz, flo
     return (m <= s.origin_bound && t_scale > 0.0f && t_scale <= kFiltMaxTScale) ? 1 : 0;
 }
 
+// ---- the host's half of the camera-hit views (rt_view.hpp): launch_sarsa_view, launch_sarsa_irr, ----
+// ---- launch_glyph_view                                                                          ----
+// the (pixel, chunk) split a view kernel can run: a power of two <= 64 that divides spp
+inline bool view_split_ok(const RenderLaunch& a) {
+    return a.split >= 1 && a.split <= 64 && (1 << a.split_log2) == a.split && a.per_chunk * a.split == a.spp;
+}
+// 1: the camera rays take the rectangle cull, where k_render_ps takes it (filter records valid for
+// this camera and t_scale -- use_filter is filter_usable's, so they exist --, at most 256
+// triangles) and the GPU preset's ray is the cull's camera model: pitch 0 (camera_ray's second
+// rotation is then the identity, exactly)
+inline int view_cull_wanted(const RenderLaunch& a) {
+    return (a.use_filter && a.scene.filt != nullptr && a.scene.n_tri <= 64 * kRenderCullWords && a.cos_x == 1.0f &&
+            a.sin_x == 0.0f) ? 1 : 0;
+}
+// what a view's launch adds to render_launch's: the block list, the clip (the whole image), the
+// output and the first sample index
+inline void fill_view_launch(RenderLaunch* a, const rt_params* p, const BlockDesc* d_blocks, int n_blocks,
+                             int out_pitch, float* d_out, uint32_t first_sample) {
+    a->blocks = d_blocks;
+    a->n_blocks = n_blocks;
+    a->clip_x1 = p->width;
+    a->clip_y1 = p->height;
+    a->out_pitch = out_pitch;
+    a->out = d_out;
+    a->sample_base = first_sample;
+}
+
 // ---- DQN Q-value network (dq_network/fc_layer) and its wavefront renderer ----
 // Four ReLU layers n_in -> h1 -> h2 -> h3 -> n_out (NN_Builders/dq_network.cu:8-33).
 // Layer 0's input is x = Scene::vertices - p, the vertices relative to the ray
@@ -434,7 +461,7 @@ struct SarsaMap {
     float root_x = 0.f, root_y = 0.f, root_z = 0.f;  // position of KD element 0 (0 if internal)
     float max_dist = 0.003f;            // MAX_DIST (compared with delta^2)
     int max_wgs = 0;                    // host: cap on the persistent render's workgroups (0: none)
-    // Exact fast path of the nearest-volume search (rt_sarsa.hip sarsa_nearest_grid):
+    // Exact fast path of the nearest-volume search (rt_sarsa_search.hpp sarsa_nearest_grid):
     // per normal class (volumes whose normals compare equal), a uniform grid of cell
     // size >= grid_h over the class's volume positions.
     int use_grid = 0;

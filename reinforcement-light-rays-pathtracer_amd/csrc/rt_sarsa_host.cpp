@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/rtmi.h"
-#include "rt_internal.hpp"
+#include "rt_hostframe.hpp"
 
 namespace rt {
 int set_error(int code, const char* msg);
@@ -430,16 +430,12 @@ float initial_irradiance(const float* cc, const float* q, float lum) {
 // view: rt_render_volume_view's parameters (it casts camera rays only: max_bounces is ignored)
 int check_sarsa_params(const rt_params* p, bool view = false) {
     if (!p) return err(RT_E_INVALID, "params is NULL");
-    if (p->width <= 0 || p->height <= 0 || p->spp <= 0) return err(RT_E_INVALID, "bad image size / spp");
+    if (rt::params_size_bad(p)) return err(RT_E_INVALID, "bad image size / spp");
     if (!view && p->max_bounces < 1) return err(RT_E_INVALID, "max_bounces must be >= 1");
     if (p->preset != RT_PRESET_GPU)
         return err(RT_E_UNSUPPORTED, "the SARSA renderer implements the GPU-engine preset");
     if (p->hit_rule != RT_HIT_RULE_CPU && p->hit_rule != RT_HIT_RULE_GPU) return err(RT_E_INVALID, "bad hit_rule");
-    const int split = p->spp_split <= 0 ? 1 : p->spp_split;
-    if (split > 64 || (split & (split - 1)) != 0)
-        return err(RT_E_INVALID, "spp_split must be a power of two <= 64");
-    if (p->spp % split != 0) return err(RT_E_INVALID, "spp_split does not divide spp");
-    if ((int64_t)p->width * (int64_t)p->height > (int64_t)1 << 31) return err(RT_E_INVALID, "image too large");
+    if (const char* why = rt::params_split_refusal(p)) return err(RT_E_INVALID, why);
     return RT_OK;
 }
 
@@ -538,13 +534,7 @@ int view_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const 
         if (rc != RT_OK) return rc;
     }
     rt::RenderLaunch a = rt::render_launch(scene, cam, p);
-    a.blocks = d_blocks;
-    a.n_blocks = n_blocks;
-    a.clip_x1 = p->width;
-    a.clip_y1 = p->height;
-    a.out_pitch = out_pitch;
-    a.out = d_out;
-    a.sample_base = first_sample;
+    rt::fill_view_launch(&a, p, d_blocks, n_blocks, out_pitch, d_out, first_sample);
     RT_HIPE(rt::launch_sarsa_view(a, sa->m, sa->d_view, d_tri, d_vol, d_pos, stream));
     return RT_OK;
 }
@@ -1228,33 +1218,18 @@ int rt_render_sarsa(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_c
     if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
     RT_HIPE(hipSetDevice(sa->device));
     const int W = params->width, H = params->height;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < H; by += 16)
-        for (int bx = 0; bx < W; bx += 16) blocks.push_back({bx, by, bx, by});
-    rt::BlockDesc* d_blocks = nullptr;
-    float* d_out = nullptr;
-    unsigned long long* d_casts = nullptr;
-    const size_t ob = sizeof(float) * 3 * (size_t)W * H;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, ob);
-    if (e == hipSuccess) e = hipMalloc(&d_casts, sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(d_casts, 0, sizeof(unsigned long long));
-    if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
-    rc = RT_OK;
-    for (int f = 0; e == hipSuccess && rc == RT_OK && f < frames; ++f)
-        rc = render_frame(sa, scene, cam, params, d_blocks, (int)blocks.size(), W, H, W, d_out, d_casts, 0, true);
-    if (rc == RT_OK && e == hipSuccess) e = hipDeviceSynchronize();
+    float* d_out;
+    unsigned long long* d_casts;
     unsigned long long casts = 0;
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, ob, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(&casts, d_casts, sizeof(casts), hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(d_casts);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_sarsa: ") + hipGetErrorString(e));
-    if (out_ray_casts) *out_ray_casts = casts;
-    return RT_OK;
+    rt::HostFrame f(0, 0, W, H);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * (size_t)W * H);
+    f.out(&d_casts, &casts, sizeof(casts), 0);
+    const hipError_t e = f.begin();
+    for (int k = 0; e == hipSuccess && rc == RT_OK && k < frames; ++k)
+        rc = render_frame(sa, scene, cam, params, f.blocks(), f.n_blocks(), W, H, W, d_out, d_casts, 0, true);
+    rc = f.finish(rc, e, "rt_render_sarsa");
+    if (rc == RT_OK && out_ray_casts) *out_ray_casts = casts;
+    return rc;
 }
 
 int rt_render_sarsa_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,
@@ -1331,40 +1306,18 @@ int rt_render_volume_view(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, cons
     if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
     RT_HIPE(hipSetDevice(sa->device));
     const int W = params->width, H = params->height;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < H; by += 16)
-        for (int bx = 0; bx < W; bx += 16) blocks.push_back({bx, by, bx, by});
-    rt::BlockDesc* d_blocks = nullptr;
-    float *d_out = nullptr, *d_pos = nullptr;
-    int32_t *d_tri = nullptr, *d_vol = nullptr;
     const size_t np = (size_t)W * H;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
-    if (e == hipSuccess && out_tri) e = hipMalloc(&d_tri, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_vol) e = hipMalloc(&d_vol, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_pos) e = hipMalloc(&d_pos, sizeof(float) * 3 * np);
+    float *d_out, *d_pos;
+    int32_t *d_tri, *d_vol;
+    rt::HostFrame f(0, 0, W, H);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * np);
+    f.out(&d_tri, out_tri, sizeof(int32_t) * np);
+    f.out(&d_vol, out_vol, sizeof(int32_t) * np);
+    f.out(&d_pos, out_pos, sizeof(float) * 3 * np);
+    const hipError_t e = f.begin();
     if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
-    rc = RT_OK;
-    if (e == hipSuccess)
-        rc = view_frame(sa, scene, cam, params, first_sample, d_blocks, (int)blocks.size(), W, d_out, d_tri, d_vol,
-                        d_pos, 0);
-    if (rc == RT_OK && e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_tri)
-        e = hipMemcpy(out_tri, d_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_vol)
-        e = hipMemcpy(out_vol, d_vol, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_pos)
-        e = hipMemcpy(out_pos, d_pos, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(d_tri);
-    (void)hipFree(d_vol);
-    (void)hipFree(d_pos);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_volume_view: ") + hipGetErrorString(e));
-    return RT_OK;
+        rc = view_frame(sa, scene, cam, params, first_sample, f.blocks(), f.n_blocks(), W, d_out, d_tri, d_vol, d_pos, 0);
+    return f.finish(rc, e, "rt_render_volume_view");
 }
 
 int rt_render_volume_view_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,
@@ -1426,13 +1379,7 @@ int irr_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const r
               uint32_t first_sample, const rt::BlockDesc* d_blocks, int n_blocks, int out_pitch, float* d_out,
               int32_t* d_tri, float* d_pos, int32_t* d_vol, float* d_dist, hipStream_t stream) {
     rt::RenderLaunch a = rt::render_launch(scene, cam, p);
-    a.blocks = d_blocks;
-    a.n_blocks = n_blocks;
-    a.clip_x1 = p->width;
-    a.clip_y1 = p->height;
-    a.out_pitch = out_pitch;
-    a.out = d_out;
-    a.sample_base = first_sample;
+    rt::fill_view_launch(&a, p, d_blocks, n_blocks, out_pitch, d_out, first_sample);
     RT_HIPE(rt::launch_sarsa_irr(a, sa->m, o->k, o->radius, o->weight == RT_IRR_CONE, o->tint != 0, d_tri, d_pos, d_vol,
                                  d_dist, stream));
     return RT_OK;
@@ -1489,44 +1436,20 @@ int rt_render_irradiance(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const
     if (sa->device != rt::ctx_device(ctx)) return err(RT_E_INVALID, "radiance map belongs to another device");
     RT_HIPE(hipSetDevice(sa->device));
     const int W = params->width, H = params->height;
-    std::vector<rt::BlockDesc> blocks;
-    for (int by = 0; by < H; by += 16)
-        for (int bx = 0; bx < W; bx += 16) blocks.push_back({bx, by, bx, by});
-    rt::BlockDesc* d_blocks = nullptr;
-    float *d_out = nullptr, *d_pos = nullptr, *d_dist = nullptr;
-    int32_t *d_tri = nullptr, *d_vol = nullptr;
     const size_t np = (size_t)W * H, nk = np * (size_t)opts->k;
-    hipError_t e = hipMalloc(&d_blocks, sizeof(rt::BlockDesc) * blocks.size());
-    if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(float) * 3 * np);
-    if (e == hipSuccess && out_tri) e = hipMalloc(&d_tri, sizeof(int32_t) * np);
-    if (e == hipSuccess && out_pos) e = hipMalloc(&d_pos, sizeof(float) * 3 * np);
-    if (e == hipSuccess && out_vol) e = hipMalloc(&d_vol, sizeof(int32_t) * nk);
-    if (e == hipSuccess && out_dist) e = hipMalloc(&d_dist, sizeof(float) * nk);
+    float *d_out, *d_pos, *d_dist;
+    int32_t *d_tri, *d_vol;
+    rt::HostFrame f(0, 0, W, H);
+    f.out(&d_out, out_rgb, sizeof(float) * 3 * np);
+    f.out(&d_tri, out_tri, sizeof(int32_t) * np);
+    f.out(&d_pos, out_pos, sizeof(float) * 3 * np);
+    f.out(&d_vol, out_vol, sizeof(int32_t) * nk);
+    f.out(&d_dist, out_dist, sizeof(float) * nk);
+    const hipError_t e = f.begin();
     if (e == hipSuccess)
-        e = hipMemcpy(d_blocks, blocks.data(), sizeof(rt::BlockDesc) * blocks.size(), hipMemcpyHostToDevice);
-    rc = RT_OK;
-    if (e == hipSuccess)
-        rc = irr_frame(sa, scene, cam, params, opts, first_sample, d_blocks, (int)blocks.size(), W, d_out, d_tri, d_pos,
-                       d_vol, d_dist, 0);
-    if (rc == RT_OK && e == hipSuccess) e = hipDeviceSynchronize();
-    if (rc == RT_OK && e == hipSuccess) e = hipMemcpy(out_rgb, d_out, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_tri)
-        e = hipMemcpy(out_tri, d_tri, sizeof(int32_t) * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_pos)
-        e = hipMemcpy(out_pos, d_pos, sizeof(float) * 3 * np, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_vol)
-        e = hipMemcpy(out_vol, d_vol, sizeof(int32_t) * nk, hipMemcpyDeviceToHost);
-    if (rc == RT_OK && e == hipSuccess && out_dist)
-        e = hipMemcpy(out_dist, d_dist, sizeof(float) * nk, hipMemcpyDeviceToHost);
-    (void)hipFree(d_blocks);
-    (void)hipFree(d_out);
-    (void)hipFree(d_tri);
-    (void)hipFree(d_pos);
-    (void)hipFree(d_vol);
-    (void)hipFree(d_dist);
-    if (rc != RT_OK) return rc;
-    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_render_irradiance: ") + hipGetErrorString(e));
-    return RT_OK;
+        rc = irr_frame(sa, scene, cam, params, opts, first_sample, f.blocks(), f.n_blocks(), W, d_out, d_tri, d_pos, d_vol,
+                       d_dist, 0);
+    return f.finish(rc, e, "rt_render_irradiance");
 }
 
 int rt_render_irradiance_tiles_device(rt_ctx* ctx, const rt_scene* scene, rt_sarsa* sa, const rt_camera* cam,

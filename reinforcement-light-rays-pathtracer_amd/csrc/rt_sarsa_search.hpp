@@ -2,7 +2,8 @@
 // reference's k-d walk (sarsa_nearest), its exact shortcut through the per-normal grid
 // (sarsa_nearest_grid*) and the wave-cooperative walk of the queries the grid leaves open
 // (sarsa_nearest_wave, sarsa_resolve_walks).  Included by the kernels that search as the
-// render does: rt_sarsa.hip (render, views, queries) and rt_sweep.hip (k_sweep).
+// render does: rt_sarsa.hip (the learning render), rt_views.hip (views, queries) and rt_sweep.hip
+// (k_sweep).
 #pragma once
 
 #include <float.h>
@@ -29,6 +30,10 @@
 namespace rt {
 
 namespace {
+
+// get_irradiance_estimate: a volume's irradiance estimate is accum * kIrrScale (the render's TD
+// target, the sweep's, the irradiance render)
+constexpr float kIrrScale = (2.f * kPi) / ((float)(kGridRes * kGridRes));
 
 __device__ __forceinline__ float len3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 

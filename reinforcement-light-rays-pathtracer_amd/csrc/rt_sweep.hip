@@ -45,7 +45,6 @@ namespace {
 
 static_assert(kSarsaSectors == kDqnActions && kSarsaSectors == kDqnGrid * kDqnGrid && kDqnGrid == kGridRes,
               "the map's sectors are the sampler's 12 x 12 cells");
-constexpr float kIrrScale = (2.f * kPi) / ((float)(kGridRes * kGridRes));  // get_irradiance_estimate (rt_sarsa.hip)
 
 // Waves per SIMD the launch bounds ask for.  The stack block (30 KB per workgroup) lets five
 // workgroups share a CU; the BVH traversal's state wants the registers of four (k_sarsa_render_pq).

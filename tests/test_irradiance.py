@@ -46,7 +46,7 @@ def reach_of(max_dist=0.003):
 
 
 def len3(dx, dy, dz):
-    """rt_sarsa.hip's len3: sqrtf((x x + y y) + z z), every operation rounded on its own."""
+    """rt_sarsa_search.hpp's len3: sqrtf((x x + y y) + z z), every operation rounded on its own."""
     assert dx.dtype == dy.dtype == dz.dtype == F
     return np.sqrt((dx * dx + dy * dy) + dz * dz)
 
@@ -389,7 +389,7 @@ ENV = 0.25
 
 
 def irr_scale():
-    """rt_sarsa.hip's kIrrScale: (2.f * pi_f) / 144.f"""
+    """rt_sarsa_search.hpp's kIrrScale: (2.f * pi_f) / 144.f"""
     return (F(2) * F(math.pi)) / F(144)
 
 
