@@ -38,12 +38,6 @@
 #include "rt_paths.hpp"
 
 namespace rt {
-int sarsa_bake_view(rt_sarsa* sa, size_t floats, SarsaBakeView* out);
-int sarsa_n_volumes(const rt_sarsa* sa);
-int sarsa_device(const rt_sarsa* sa);
-}  // namespace rt
-
-namespace rt {
 namespace {
 
 static_assert(kSarsaSectors == kDqnActions && kSarsaSectors == kDqnGrid * kDqnGrid && kDqnGrid == kGridRes, "the map's sectors are the sampler's 12 x 12 cells");

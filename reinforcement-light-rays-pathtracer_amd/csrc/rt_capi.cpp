@@ -430,8 +430,6 @@ bool ctab_wanted(const rt_scene* sc, const rt_camera* cam, const rt_params* p, i
             return cam_in && t_ok && pitch0;
         case kCtabForDqn:  // launch_dqn_bounce: dqn_mf > 0
             return cam_in && t_ok;
-        case kCtabForSarsa:  // k_sarsa_render_pq<.., CT> (built, off by default: RT_SARSA_CTAB)
-            return sarsa_ctab_compiled() && t_ok;
     }
     return false;
 }

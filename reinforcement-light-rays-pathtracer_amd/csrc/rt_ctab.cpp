@@ -64,9 +64,6 @@ namespace rt {
 namespace {
 
 constexpr double kK = kBvhK;
-#ifndef RT_CTAB_GFOLD
-#define RT_CTAB_GFOLD 1  // 0: no grazing fold (A/B builds)
-#endif
 constexpr int kNc = kCtabBins;    // coarse direction bins per face edge
 constexpr int kNg = kCtabGraze;   // grazing bins per face edge
 using Bins = std::bitset<kNc * kNc>;  // the coarse bins of one face, bit iu * kNc + iv
@@ -696,7 +693,7 @@ bool ctab_build(const float4* isect, int n, int n_surf, double B, int rule, doub
         // look the grazing mask up.  A ray in a folded bin then needs one dependent memory access
         // (its entry), not two.
         h.gflag = 0;
-        if (RT_CTAB_GFOLD && n < 64 * W && kNg % kNc == 0) {
+        if (n < 64 * W && kNg % kNc == 0) {
             const int sh = kNg / kNc;
             size_t folded = 0;
             std::vector<int32_t> fold(6 * kNc * kNc, -1);

@@ -11,8 +11,8 @@
 //    4 waves; each wave owns every M-tile and a quarter of the N-tiles, so each
 //    weight byte is fetched once per workgroup (from L2; 0.4-0.7 MB per net).
 //    v_mfma_f32_16x16x32_bf16 with fp32 accumulation; bias + ReLU fused in the
-//    epilogue; activations stay in LDS (bf16) between the four layers, so
-//    nothing but Q touches HBM.  The input x = vertices - ray_position is built
+//    epilogue; activations stay in LDS (bf16) between the four layers, in one buffer
+//    that each layer reads and then overwrites, so nothing but Q touches HBM.  The input x = vertices - ray_position is built
 //    in registers straight into the A fragments (never materialised; the
 //    reference writes W*H*n_in floats per bounce and ships them to DyNet on the
 //    host).  Features are ordered coordinate-major so a 32-deep K step needs
@@ -36,7 +36,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #ifndef RT_MLP_MT
-#define RT_MLP_MT 6  // 16-row M-tiles per MLP workgroup (96 rays; 4 with the two-buffer layout)
+#define RT_MLP_MT 6  // 16-row M-tiles per MLP workgroup (96 rays)
 #endif
 constexpr int kTileM = RT_MLP_MT * 16;  // rays per MLP workgroup
 #ifndef RT_MLP_WAVES
@@ -51,70 +51,32 @@ constexpr int slots(int tiles) { return (tiles + kMlpWaves - 1) / kMlpWaves; }
 // stream over layers 1-3 with a 2-4 deep register ring was 2x slower (round-1 A/B,
 // DESIGN.md §4).
 // LDS activation rows (bf16) are XOR-swizzled at 16-B granularity, slot ^ ((row >> 2) & 7),
-// on strides of 336 / 272 elements: the B-operand ds_read_b128 of each 16-lane group then
-// hits 16 distinct 16-B slots (conflict-free; the padded 328 / 232 rows were 2-way) and
+// on a stride of 336 elements: the B-operand ds_read_b128 of each 16-lane group then
+// hits 16 distinct 16-B slots (conflict-free; the padded 328 rows were 2-way) and
 // the 8-B epilogue stores are 2-way (bank rule of MI355X_MICROARCH.md §LDS, brute-forced
 // over strides and swizzles)
 #ifndef RT_MLP_RING_VGPRS
 #define RT_MLP_RING_VGPRS 60  // VGPRs of the weight-fragment ring (60: 3 K steps of layer 1's 5 fragments)
 #endif
 constexpr int kMlpRingVgprs = RT_MLP_RING_VGPRS;
-#ifndef RT_MLP_XPF
-// 1: each layer's first weight fragments prefetched during the previous layer (archway
-// 512^2 x 16 with MT = 4: 110.4 vs 111.2 ms; with MT = 6 it spills: 119.8 ms, profiles/r4p)
-#define RT_MLP_XPF 0
-#endif
-#ifndef RT_MLP_A_DB
-#define RT_MLP_A_DB 0  // 1: the next K step's activations double-buffered in registers (MT = 4: 234 VGPRs)
-#endif
-#ifndef RT_DQN_NT_LOAD
-#define RT_DQN_NT_LOAD 1  // the sampler's reads of the bf16 Q non-temporal (read once: archway 512^2 x 16 with the NT stores: 104.6 vs 106.4 ms, profiles/r4af)
-#endif
-#ifndef RT_MLP_NT_STORE
-#define RT_MLP_NT_STORE 1  // the renderer's bf16 Q stored non-temporally (106.4 vs 107.4 ms, profiles/r4af)
-#endif
-#ifndef RT_MLP_EPI2
-#define RT_MLP_EPI2 1  // packed epilogue (bias pairs, ReLU on bf16 pairs; archway 1024^2 x 16: 409.7 vs 417.0 ms, profiles/r4ao)
-#endif
-#ifndef RT_MLP_T_NOEPI  // timing-only knobs (wrong Q): the layers' epilogues, the ray loads, the Q stores
-#define RT_MLP_T_NOEPI 0
-#endif
-#ifndef RT_MLP_T_NOLOC
-#define RT_MLP_T_NOLOC 0
-#endif
-#ifndef RT_MLP_T_NOSTORE
-#define RT_MLP_T_NOSTORE 0
-#endif
-#ifndef RT_MLP_SKIP_PAD
-#define RT_MLP_SKIP_PAD 0
-#endif
-#ifndef RT_MLP_PROLOGUE_GROUP
-#define RT_MLP_PROLOGUE_GROUP 1
-#endif
 typedef float mlp_f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 mlp_bf16x2 __attribute__((ext_vector_type(2)));
 constexpr int kStrideA = 336;
-constexpr int kStrideB = 272;
-#ifndef RT_MLP_INPLACE
-// 1: one activation buffer (stride 336) that every layer reads and then overwrites (a
-// barrier between the K loop and the epilogue; the accumulators hold the layer's outputs
-// meanwhile): 2 * 336 * 2 B per row instead of (336 + 272) * 2, so MT = 7 (112 rays, 75 KB)
-// still fits two workgroups per CU, and each weight fragment feeds 7 MFMAs instead of 4
-#define RT_MLP_INPLACE 1  // archway 512^2 x 16: 107.4 (MT = 6) vs 110.5 ms (two buffers, MT = 4), profiles/r4o
-#endif
+// One activation buffer (stride 336) that every layer reads and then overwrites (a barrier
+// between the K loop and the epilogue; the accumulators hold the layer's outputs meanwhile):
+// 2 * 336 * 2 B per row, so MT = 7 (112 rays, 75 KB) still fits two workgroups per CU, and each
+// weight fragment feeds MT MFMAs
 __device__ __forceinline__ int swz(int row, int k, int stride) {
     return row * stride + (((k >> 3) ^ ((row >> 2) & 7)) << 3) + (k & 7);
 }
 constexpr int kStageStride = kDqnActions + 1;  // fp32 Q staging rows (in bufA)
-// bf16 Q staging (RT_MLP_EPI2, the renderer's QB forward): [72 cell pairs][kQPairStride rows]
+// bf16 Q staging (the packed epilogue of the renderer's QB forward): [72 cell pairs][kQPairStride rows]
 // dwords; 2 * 104 = 16 mod 64 banks, so a wave's pair-row writes hit 64 distinct banks
 constexpr int kQPairStride = kTileM <= 104 ? 104 : kTileM + 8;
 // the sampler's fixed sum order: kSampBlocks blocks of kSampCells cells (sample_from_q)
 constexpr int kSampBlocks = 4;
 constexpr int kSampCells = kDqnActions / kSampBlocks;  // 36 = 9 Philox draws
 static_assert(kTileM * kStageStride * 4 <= kTileM * kStrideA * 2, "Q staging tile exceeds bufA");
-// the fused sampler maps a thread to a (ray, block): 64 rays on kSampBlocks waves
-constexpr bool kFusedFits = kTileM == 64 && kMlpThreads == 64 * kSampBlocks && !RT_MLP_INPLACE;
 constexpr float kGridRho = 1.0f / ((float)kDqnGrid * (float)kDqnGrid);  // GRID_RHO
 
 __device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
@@ -187,30 +149,9 @@ __device__ __forceinline__ void mlp_layer0(const DqnNet& net, const float* __res
 // the weight-fragment ring depth of a layer with NT N-tile slots per wave
 constexpr int mlp_ring(int nt) { return (kMlpRingVgprs / (4 * nt)) < 2 ? 2 : (kMlpRingVgprs / (4 * nt)); }
 
-// wave's weight fragments of layer L, K steps 0 .. PS-1 (the layer's ring prologue), into
-// pre[s * NT + j]: issued ahead (the previous layer's tail, or layer 0 for layer 1) so a
-// layer starts with its first fragments in registers instead of an L2 round trip
-template <int NT, int PS>
-__device__ __forceinline__ void mlp_prefetch(const DqnNet& net, int L, bf16x8* pre) {
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int n_tiles = net.N[L] >> 4;
-    const uint16_t* __restrict__ W = net.W[L];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const uint16_t* wr = W + ((size_t)min(wave + kMlpWaves * j, n_tiles - 1) * (net.K[L] >> 5) * 64 + lane) * 8;
-#pragma unroll
-        for (int s = 0; s < PS; ++s) pre[s * NT + j] = *reinterpret_cast<const bf16x8*>(wr + s * 32 * 16);
-    }
-}
-
-// PRE_IN: the ring prologue (mlp_ring(NT) - 1 steps) arrives in pre_in (mlp_prefetch);
-// NTN > 0: the next layer's prologue (NTN slots, mlp_ring(NTN) - 1 steps) is issued into
-// pre_out once this layer's own weight loads are done (KS > 0 only)
-template <int NT, bool LAST, int MT, int KS = 0, bool INPLACE = false, bool PRE_IN = false, int NTN = 0>
+template <int NT, bool LAST, int MT, int KS = 0>
 __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16* in_lds, int in_stride,
-                                          __bf16* out_lds, int out_stride, const bf16x8* pre_in = nullptr,
-                                          bf16x8* pre_out = nullptr) {
+                                          __bf16* out_lds, int out_stride) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int K = net.K[L];
@@ -224,9 +165,8 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
     for (int j = 0; j < NT; ++j)
         wrow[j] = W + ((size_t)min(wave + kMlpWaves * j, n_tiles - 1) * (K >> 5) * 64 + lane) * 8;
     f32x4 acc[MT][NT];
-    // (RT_MLP_EPI2 with K known: the first K step's MFMAs take C = 0 as an inline constant,
-    // no zeroing moves)
-    if (!(RT_MLP_EPI2 && KS > 0)) {
+    // (with K known the first K step's MFMAs take C = 0 as an inline constant, no zeroing moves)
+    if (KS == 0) {
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -240,31 +180,25 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
         // SIMD by its LDS anyway, so VGPRs up to 256 are free, and an L2 fragment load
         // (~1 us under load) needs several K steps of MFMAs (NT*MT*16 clk each) to hide.
         constexpr int R = mlp_ring(NT);
-        // the activations of step k + 1 in flight during step k's MFMAs (RT_MLP_A_DB), or
-        // read at the top of their own step (MT * 4 fewer VGPRs: the wider tiles)
-        constexpr int AB = RT_MLP_A_DB ? 2 : 1;
-        bf16x8 bw[R][NT], a[AB][MT];
+        // the activations are read at the top of their own step (MT * 4 fewer VGPRs than a
+        // second set in flight: the wider tiles)
+        bf16x8 bw[R][NT], a[MT];
 #pragma unroll
         for (int s = 0; s < R - 1; ++s) {
             if (s < KS) {
 #pragma unroll
                 for (int j = 0; j < NT; ++j)
-                    bw[s][j] = PRE_IN ? pre_in[s * NT + j] : *reinterpret_cast<const bf16x8*>(wrow[j] + s * 32 * 16);
+                    bw[s][j] = *reinterpret_cast<const bf16x8*>(wrow[j] + s * 32 * 16);
             }
         }
 #pragma unroll
         for (int m = 0; m < MT; ++m)
-            a[0][m] = *reinterpret_cast<const bf16x8*>(in_lds + swz(m * 16 + r16, kg, in_stride));
-#if RT_MLP_PROLOGUE_GROUP
+            a[m] = *reinterpret_cast<const bf16x8*>(in_lds + swz(m * 16 + r16, kg, in_stride));
         // the prologue's loads as their own groups: each step's groups below then claim
         // that step's own loads (without this the scheduler pairs step k's MFMAs with the
         // prologue's second step, and the ring is one step shallower than written)
-        if (!PRE_IN) __builtin_amdgcn_sched_group_barrier(0x020, (R - 1 < KS ? R - 1 : KS) * NT, 0);
+        __builtin_amdgcn_sched_group_barrier(0x020, (R - 1 < KS ? R - 1 : KS) * NT, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, MT, 0);
-#endif
-        constexpr int PN = NTN > 0 ? mlp_ring(NTN) - 1 : 0;  // next layer's prologue steps
-        const bool last_valid = __builtin_amdgcn_readfirstlane(wave) + kMlpWaves * (NT - 1) < n_tiles;
-        constexpr int KP = KS - R + 1 > 0 ? KS - R + 1 : 0;  // first step without own loads
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             if (ks + R - 1 < KS) {
@@ -272,37 +206,20 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
                 for (int j = 0; j < NT; ++j)
                     bw[(ks + R - 1) % R][j] = *reinterpret_cast<const bf16x8*>(wrow[j] + (ks + R - 1) * 32 * 16);
             }
-            if (AB == 2 && ks + 1 < KS) {
+            if (ks > 0) {
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
-                    a[(ks + 1) % AB][m] =
-                        *reinterpret_cast<const bf16x8*>(in_lds + swz(m * 16 + r16, (ks + 1) * 32 + kg, in_stride));
+                    a[m] = *reinterpret_cast<const bf16x8*>(in_lds + swz(m * 16 + r16, ks * 32 + kg, in_stride));
             }
-            if (AB == 1 && ks > 0) {
-#pragma unroll
-                for (int m = 0; m < MT; ++m)
-                    a[0][m] = *reinterpret_cast<const bf16x8*>(in_lds + swz(m * 16 + r16, ks * 32 + kg, in_stride));
-            }
-            if (PN > 0 && ks == KP) mlp_prefetch<(NTN > 0 ? NTN : 1), PN>(net, L + 1, pre_out);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                // (RT_MLP_SKIP_PAD: the wave's last slot, past the layer's tiles for some waves,
-                // skipped by a wave-uniform branch instead of recomputing the last tile)
-                if (RT_MLP_SKIP_PAD && j == NT - 1 && !last_valid) continue;
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
                     acc[m][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        bw[ks % R][j], a[ks % AB][m], (RT_MLP_EPI2 && ks == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[m][j],
-                        0, 0, 0);
+                        bw[ks % R][j], a[m], ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[m][j], 0, 0, 0);
             }
-#if RT_MLP_PROLOGUE_GROUP
             if (ks + R - 1 < KS) __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);  // VMEM reads
-            if (PN > 0 && ks == KP) __builtin_amdgcn_sched_group_barrier(0x020, PN * (NTN > 0 ? NTN : 1), 0);
-            if (AB == 2 ? ks + 1 < KS : ks > 0) __builtin_amdgcn_sched_group_barrier(0x100, MT, 0);  // LDS reads
-#else
-            __builtin_amdgcn_sched_group_barrier(0x020, NT, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, MT, 0);
-#endif
+            if (ks > 0) __builtin_amdgcn_sched_group_barrier(0x100, MT, 0);  // LDS reads
             __builtin_amdgcn_sched_group_barrier(0x008, NT * MT, 0);  // MFMA
         }
     } else {
@@ -342,11 +259,8 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
     }
     if (k0 < K) step(k0, b0);  // odd number of K steps
     }
-    if constexpr (INPLACE) __syncthreads();  // every wave has read the layer's input
+    __syncthreads();  // every wave has read the layer's input
     // epilogue: bias + ReLU (fc_layer.cu:40-72, dynet::rectify)
-#if RT_MLP_T_NOEPI  // timing only: no epilogue (wrong Q)
-    if (acc[0][0][0] != 12345.0f) return;
-#endif
     // (the weights are the MFMA's A operand, the activations its B operand, so a lane
     // holds 4 consecutive features of one ray: one 8-B (bf16) or 16-B (fp32) LDS store)
 #pragma unroll
@@ -359,7 +273,6 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
             const int row = m * 16 + r16;
-#if RT_MLP_EPI2
             if (!LAST || out_stride != 0) {
                 // bias in packed adds (the same IEEE sums), then RNE to bf16 and the ReLU on the
                 // bf16 pairs as a signed 16-bit max with 0: RN is monotone with RN(0) = 0, so
@@ -385,7 +298,6 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
                 *reinterpret_cast<uint2*>(out_lds + swz(row, col, out_stride)) = w;
                 continue;
             }
-#endif
             float v[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -409,14 +321,6 @@ __device__ __forceinline__ void mlp_layer(const DqnNet& net, int L, const __bf16
     }
 }
 
-
-// The fused Q.cos sampler's per-ray inputs (k_dqn_mlp<MT, true>): the rays' pixel keys and
-// sample (ray id = slot * n_pix + pixel slot, as k_dqn_bounce), the Philox event and key.
-struct MlpSample {
-    const uint32_t* pix = nullptr;
-    int n_pix = 0, s0 = 0;
-    uint32_t ev = 0, k0 = 0, k1 = 0;
-};
 
 __device__ __forceinline__ float chiu_cos_cell(int a, float r1, float r2) {
     const int gxi = a / kDqnGrid;
@@ -487,39 +391,26 @@ __device__ __forceinline__ void view_merge(const float* bsum, const float* best,
 // q[i] = S, q[ldq + i] = action bits (i the list row): 8 B instead of 576 B per ray.  The
 // block results live in bufA's slack behind the stage; consecutive lanes read consecutive
 // rows at the odd kStageStride, so a 32-lane group's ds_read_b32 hits 32 distinct banks.
-// FUSED: instead of writing Q out, the workgroup runs importance_sample_direction's
-// selection (nn_rendering_helpers.cu:391-489) on its LDS tile in sample_from_q's blocked
-// order, one thread per (ray, block of 36 cells): Q*cos and the block sums, then the total,
-// the block prefixes and the walks of the reached blocks, the first block's cell winning -- and
-// writes the chosen cell and its normalised Q*cos per ray (q[i] = action bits,
-// q[ldq + i] = qd), 8 B instead of 576 B of Q per ray; k_dqn_bounce<MF, true> finishes the
-// direction.  Q never leaves the chip.
-template <int MT, bool FUSED = false, bool QB = false, bool VIEW = false>
+template <int MT, bool QB = false, bool VIEW = false>
 #ifndef RT_MLP_MIN_WAVES
 #define RT_MLP_MIN_WAVES 2  // waves per SIMD: the workgroups per CU that its LDS admits (3: MT = 4 in place)
 #endif
 __global__ __launch_bounds__(kMlpThreads, RT_MLP_MIN_WAVES) void k_dqn_mlp(const DqnNet net, const float* __restrict__ loc,
                                                  const int32_t* __restrict__ list,
                                                  const int32_t* __restrict__ count, int max_rows,
-                                                 float* __restrict__ q, int ldq, const MlpSample smp) {
+                                                 float* __restrict__ q, int ldq) {
     constexpr int kRows = MT * 16;
     __shared__ __attribute__((aligned(16))) __bf16 bufA[kRows * kStrideA];
-    __shared__ __attribute__((aligned(16))) __bf16 bufB[RT_MLP_INPLACE ? 8 : kRows * kStrideB];
     __shared__ float locs[kRows * 3];
     const int n_rows = (count != nullptr) ? min(*count, max_rows) : max_rows;
     const int row0 = blockIdx.x * kRows;
     if (row0 >= n_rows) return;
     const int rows_valid = min(kRows, n_rows - row0);
-    // layer 1's first weight fragments in flight during the ray loads and layer 0
     const bool ref_net = net.K[1] == 224 && net.K[2] == 320 && net.K[3] == 224;
-    bf16x8 p1[RT_MLP_XPF ? (mlp_ring(slots(20)) - 1) * slots(20) : 1];
-    if constexpr (RT_MLP_XPF != 0) {
-        if (ref_net) mlp_prefetch<slots(20), mlp_ring(slots(20)) - 1>(net, 1, p1);
-    }
     if (threadIdx.x < kRows) {
         const int row = threadIdx.x;
         float x = 0.0f, y = 0.0f, z = 0.0f;
-        if (row < rows_valid && !RT_MLP_T_NOLOC) {  // (RT_MLP_T_NOLOC: timing only, positions 0)
+        if (row < rows_valid) {
             const int rid = (list != nullptr) ? list[row0 + row] : (row0 + row);
             x = loc[(size_t)rid * 3 + 0];
             y = loc[(size_t)rid * 3 + 1];
@@ -530,54 +421,24 @@ __global__ __launch_bounds__(kMlpThreads, RT_MLP_MIN_WAVES) void k_dqn_mlp(const
         locs[row * 3 + 2] = z;
     }
     __syncthreads();
-#if RT_MLP_INPLACE
     mlp_layer0<MT>(net, locs, bufA, kStrideA);
     __syncthreads();
     if (ref_net) {  // the reference's 200-300-200 net
-        bf16x8 p2[RT_MLP_XPF ? (mlp_ring(slots(14)) - 1) * slots(14) : 1];
-        bf16x8 p3[RT_MLP_XPF ? (mlp_ring(slots(9)) - 1) * slots(9) : 1];
-        mlp_layer<slots(20), false, MT, 7, true, RT_MLP_XPF, RT_MLP_XPF ? slots(14) : 0>(net, 1, bufA, kStrideA, bufA,
-                                                                                      kStrideA, p1, p2);
+        mlp_layer<slots(20), false, MT, 7>(net, 1, bufA, kStrideA, bufA, kStrideA);
         __syncthreads();
-        mlp_layer<slots(14), false, MT, 10, true, RT_MLP_XPF, RT_MLP_XPF ? slots(9) : 0>(net, 2, bufA, kStrideA, bufA,
-                                                                                      kStrideA, p2, p3);
+        mlp_layer<slots(14), false, MT, 10>(net, 2, bufA, kStrideA, bufA, kStrideA);
         __syncthreads();
-        mlp_layer<slots(9), true, MT, 7, true, RT_MLP_XPF>(net, 3, bufA, kStrideA, bufA, (RT_MLP_EPI2 && QB) ? kQPairStride : 0,
-                                                          p3);
+        mlp_layer<slots(9), true, MT, 7>(net, 3, bufA, kStrideA, bufA, QB ? kQPairStride : 0);
     } else {
-        mlp_layer<slots(20), false, MT, 0, true>(net, 1, bufA, kStrideA, bufA, kStrideA);  // N <= 320
+        mlp_layer<slots(20), false, MT>(net, 1, bufA, kStrideA, bufA, kStrideA);  // N <= 320
         __syncthreads();
-        mlp_layer<slots(14), false, MT, 0, true>(net, 2, bufA, kStrideA, bufA, kStrideA);  // N <= 224
+        mlp_layer<slots(14), false, MT>(net, 2, bufA, kStrideA, bufA, kStrideA);  // N <= 224
         __syncthreads();
-        mlp_layer<slots(9), true, MT, 0, true>(net, 3, bufA, kStrideA, bufA, (RT_MLP_EPI2 && QB) ? kQPairStride : 0);
+        mlp_layer<slots(9), true, MT>(net, 3, bufA, kStrideA, bufA, QB ? kQPairStride : 0);
     }
-    (void)bufB;
-#else
-#ifndef RT_MLP_SKIP_L0  // timing only: layer 0 not evaluated (wrong Q)
-    mlp_layer0<MT>(net, locs, bufB, kStrideB);
-#endif
-    __syncthreads();
-    if (ref_net) {  // the reference's 200-300-200 net
-        bf16x8 p2[RT_MLP_XPF ? (mlp_ring(slots(14)) - 1) * slots(14) : 1];
-        bf16x8 p3[RT_MLP_XPF ? (mlp_ring(slots(9)) - 1) * slots(9) : 1];
-        mlp_layer<slots(20), false, MT, 7, false, RT_MLP_XPF, RT_MLP_XPF ? slots(14) : 0>(net, 1, bufB, kStrideB, bufA,
-                                                                                       kStrideA, p1, p2);
-        __syncthreads();
-        mlp_layer<slots(14), false, MT, 10, false, RT_MLP_XPF, RT_MLP_XPF ? slots(9) : 0>(net, 2, bufA, kStrideA, bufB,
-                                                                                       kStrideB, p2, p3);
-        __syncthreads();
-        mlp_layer<slots(9), true, MT, 7, false, RT_MLP_XPF>(net, 3, bufB, kStrideB, bufA, 0, p3);
-    } else {
-        mlp_layer<slots(20), false, MT>(net, 1, bufB, kStrideB, bufA, kStrideA);  // N <= 320
-        __syncthreads();
-        mlp_layer<slots(14), false, MT>(net, 2, bufA, kStrideA, bufB, kStrideB);  // N <= 224
-        __syncthreads();
-        mlp_layer<slots(9), true, MT>(net, 3, bufB, kStrideB, bufA, 0);           // N = 144
-    }
-#endif
     __syncthreads();
     if constexpr (VIEW) {
-        static_assert(!FUSED && !QB, "the view reduces the fp32 stage");
+        static_assert(!QB, "the view reduces the fp32 stage");
         // [block][row] behind the stage (no LDS of its own)
         static_assert(kRows * kStageStride * 4 + 3 * kSampBlocks * kRows * 4 <= kRows * kStrideA * 2,
                       "the view's block results fit bufA's slack");
@@ -602,102 +463,10 @@ __global__ __launch_bounds__(kMlpThreads, RT_MLP_MIN_WAVES) void k_dqn_mlp(const
         }
         return;
     }
-    if constexpr (FUSED && kFusedFits) {
-        static_assert(kRows == 64 && kMlpThreads == 64 * kSampBlocks, "the fused sampler maps a thread to a block");
-        float* const stage = reinterpret_cast<float*>(bufA);  // [row][kStageStride]: Q -> Q*cos
-        float* const bsum = reinterpret_cast<float*>(bufB);   // [row][block] B_w (bufB is free after layer 3)
-        const int r = threadIdx.x & 63, w = threadIdx.x >> 6;  // ray, block (sample_from_q's order)
-        const bool live = r < rows_valid;
-        uint32_t pixid = 0, sample = 0;
-        if (live) {
-            const int rid = list[row0 + r];
-            const int slot = rid / smp.n_pix;
-            pixid = smp.pix[rid - slot * smp.n_pix];
-            sample = (uint32_t)(smp.s0 + slot);
-        }
-        float* const srow = stage + r * kStageStride;
-        // (1) Q*cos of the block's cells (one Philox draw per four cells, counter 1 + a/4), B_w
-        const PhiloxShared ph = philox_shared(pixid, sample, smp.ev, smp.k0, smp.k1);
-        if (live) {
-            const int c0 = w * kSampCells;
-            float b = 0.0f;
-#pragma unroll 3
-            for (int a = c0; a < c0 + kSampCells; a += 4) {
-                uint32_t o[4];
-                philox_from(ph, 1u + (uint32_t)(a >> 2), o);
-#pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    const float qc = srow[a + h] * chiu_cos_cell_w(a + h, o[h]);
-                    srow[a + h] = qc;
-                    b = b + qc;
-                }
-            }
-            bsum[r * kSampBlocks + w] = b;
-        }
-        __syncthreads();
-        // (2) every (ray, block) thread: the total and its block's prefixes; the block is walked
-        // iff it is reached (P_{w+1} > rv) -- in parallel, the first reached block that finds
-        // a cell winning (sample_from_q walks them in order and stops there: the same cell)
-        int* const hit = reinterpret_cast<int*>(bsum + kRows * kSampBlocks);  // [row][block]
-        float* const hq = reinterpret_cast<float*>(hit + kRows * kSampBlocks);
-        if (live) {
-            uint32_t o[4];
-            philox_from(ph, 0u, o);
-            const float rv = u01(o[0]);
-            float bs[kSampBlocks];
-            float total = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kSampBlocks; ++k) {
-                bs[k] = bsum[r * kSampBlocks + k];
-                total = total + bs[k];
-            }
-            float P = 0.0f, Pn = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kSampBlocks; ++k) {
-                Pn = P + bs[k] / total;
-                if (k == w) break;
-                P = Pn;
-            }
-            int act = -1;
-            float qsel = 0.0f;
-            if (Pn > rv) {
-                float cum = P;
-                for (int a = w * kSampCells; a < (w + 1) * kSampCells && act < 0; ++a) {
-                    const float qd = srow[a] / total;
-                    cum = cum + qd;
-                    if (cum > rv && qd > 0.0f) {
-                        act = a;
-                        qsel = qd;
-                    }
-                }
-            }
-            hit[r * kSampBlocks + w] = act;
-            hq[r * kSampBlocks + w] = qsel;
-        }
-        __syncthreads();
-        if (w == 0 && live) {
-            int act = -1;
-            float qsel = 0.0f;
-#pragma unroll
-            for (int k = 0; k < kSampBlocks; ++k) {
-                const int h = hit[r * kSampBlocks + k];
-                if (act < 0 && h >= 0) {
-                    act = h;
-                    qsel = hq[r * kSampBlocks + k];
-                }
-            }
-            q[row0 + r] = __int_as_float(act);
-            q[(size_t)ldq + row0 + r] = qsel;
-        }
-        return;
-    }
     // Q tile [kRows][144] from LDS (odd row stride: conflict-free column reads) in
     // 16-B stores: row-major rows are one contiguous run, action-major columns runs
     // of kRows rows (ldq covers every launched row, so padding rows may be written).
     const float* stage = reinterpret_cast<const float*>(bufA);
-#if RT_MLP_T_NOSTORE  // timing only: Q not written
-    if (stage[threadIdx.x] != 12345.0f) return;
-#endif
     if (ldq == 0) {
         float* dst = q + (size_t)row0 * kDqnActions;
         for (int t = threadIdx.x; t < rows_valid * (kDqnActions / 4); t += kMlpThreads) {
@@ -709,40 +478,16 @@ __global__ __launch_bounds__(kMlpThreads, RT_MLP_MIN_WAVES) void k_dqn_mlp(const
         // the renderer's Q in bf16 (RNE), cells 2j and 2j + 1 of a ray in one dword (low,
         // high): q2[j * ldq + ray], 16-B runs of four rays -- half the bytes of the fp32 tile
         uint32_t* const q2 = reinterpret_cast<uint32_t*>(q);
-#if RT_MLP_EPI2 && RT_MLP_INPLACE
         static_assert(kRows <= kQPairStride && (kDqnActions / 2) * kQPairStride * 4 <= kRows * kStrideA * 2,
                       "the bf16 Q staging fits bufA");
         const uint32_t* const st2 = reinterpret_cast<const uint32_t*>(bufA);
         for (int t = threadIdx.x; t < (kDqnActions / 2) * (kRows / 4); t += kMlpThreads) {
             const int j = t / (kRows / 4), r = (t - j * (kRows / 4)) * 4;
             const uint4 v = *reinterpret_cast<const uint4*>(st2 + j * kQPairStride + r);
-#if RT_MLP_NT_STORE
+            // streamed past the caches: the weights the other workgroups re-read stay in L2
             typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
             const u32x4v wv = {v.x, v.y, v.z, v.w};
             __builtin_nontemporal_store(wv, reinterpret_cast<u32x4v*>(q2 + (size_t)j * ldq + row0 + r));
-#else
-            *reinterpret_cast<uint4*>(q2 + (size_t)j * ldq + row0 + r) = v;
-#endif
-        }
-        if (true) return;
-#endif
-        for (int t = threadIdx.x; t < (kDqnActions / 2) * (kRows / 4); t += kMlpThreads) {
-            const int j = t / (kRows / 4), r = (t - j * (kRows / 4)) * 4;
-            const float* sp = stage + r * kStageStride + 2 * j;
-            uint32_t w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const mlp_f32x2 v = {sp[k * kStageStride], sp[k * kStageStride + 1]};
-                w[k] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, mlp_bf16x2));
-            }
-#if RT_MLP_NT_STORE
-            // streamed past the caches: the weights the other workgroups re-read stay in L2
-            typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
-            const u32x4v wv = {w[0], w[1], w[2], w[3]};
-            __builtin_nontemporal_store(wv, reinterpret_cast<u32x4v*>(q2 + (size_t)j * ldq + row0 + r));
-#else
-            *reinterpret_cast<uint4*>(q2 + (size_t)j * ldq + row0 + r) = make_uint4(w[0], w[1], w[2], w[3]);
-#endif
         }
     } else {
         for (int t = threadIdx.x; t < kDqnActions * (kRows / 4); t += kMlpThreads) {
@@ -786,8 +531,7 @@ __device__ __forceinline__ SampleOut sample_finish(int action, float qd_sel, f3 
 // importance_sample_direction (nn_rendering_helpers.cu:391-489) for one ray, on its 144 Q
 // values q[a * qs] (qs = 1 for a [row][144] buffer, ldq for the action-major one).
 // The sums run in a fixed blocked order (kSampBlocks blocks of kSampCells consecutive
-// cells; the fused k_dqn_mlp<.., true> gives each block its own thread, the oracle's
-// dqn_sample adds the same way):
+// cells; the oracle's dqn_sample adds the same way):
 //   qc = Q * cos (the cell's jittered direction), B_w = sum of qc over block w in cell
 //   order, total = ((B_0 + B_1) + B_2) + B_3, P_0 = 0, P_{w+1} = P_w + B_w / total;
 //   the walk starts in the first block w with P_{w+1} > rv: cum = P_w, then cell by cell
@@ -819,12 +563,9 @@ __device__ __forceinline__ SampleOut sample_from_q(float* __restrict__ q, size_t
             const uint32_t* q2 = reinterpret_cast<const uint32_t*>(q);
 #pragma unroll
             for (int u = 0; u < kQGroup; u += 2) {
-#if RT_DQN_NT_LOAD
+                // (read once: non-temporal, as the forward's stores)
                 const uint32_t w = stored ? q2[(size_t)((g + u) >> 1) * qs]
                                           : __builtin_nontemporal_load(q2 + (size_t)((g + u) >> 1) * qs);
-#else
-                const uint32_t w = q2[(size_t)((g + u) >> 1) * qs];
-#endif
                 qv[u] = __uint_as_float(w << 16);
                 qv[u + 1] = __uint_as_float(w & 0xffff0000u);
             }
@@ -894,9 +635,6 @@ __device__ __forceinline__ SampleOut sample_from_q(float* __restrict__ q, size_t
 // MF < 0: the exact BVH (large scenes, closest_hit_bvh), wl = the lane's LDS stack column.
 // BOUNCE (MF > 0): a bounce ray leaving surface `surf`, its candidates from the scene's rule-1
 // candidate table when it has one (closest_hit_ctab, rt_ctab.cpp; wave-uniform choice)
-#ifndef RT_DQN_CTAB
-#define RT_DQN_CTAB 1  // 0: the bounce casts on the matrix-core image even with a candidate table (A/B)
-#endif
 template <int MF, bool BOUNCE = false, bool CT = false>
 __device__ __forceinline__ bool dqn_trace(const DqnLaunch& a, f3 pos, f3 dir, bool active, float* wl, f3* loc_out,
                                           int* tri_out, f3* tp, int surf = -1, int* hit_out = nullptr) {
@@ -907,7 +645,7 @@ __device__ __forceinline__ bool dqn_trace(const DqnLaunch& a, f3 pos, f3 dir, bo
         // CT: the launcher checked the table serves this launch (no matrix-core path compiled in)
         if constexpr (CT)
             h = closest_hit_ctab<1, MF>(a.scene, a.scene.ctab[1], surf, o, d, a.t_scale, active, wl);
-        else if (BOUNCE && RT_DQN_CTAB && ctab_usable(a.scene.ctab[1], a.t_scale) && a.scene.ctab[1].words <= MF)
+        else if (BOUNCE && ctab_usable(a.scene.ctab[1], a.t_scale) && a.scene.ctab[1].words <= MF)
             h = closest_hit_ctab<1, MF>(a.scene, a.scene.ctab[1], surf, o, d, a.t_scale, active, wl);
         else
             h = closest_hit_mf<1, false, MF>(a.scene, o, d, a.t_scale, active, wl);
@@ -936,27 +674,13 @@ __device__ __forceinline__ bool dqn_trace(const DqnLaunch& a, f3 pos, f3 dir, bo
     return true;
 }
 
-#ifndef RT_DQN_NT_STATE
-#define RT_DQN_NT_STATE 0  // 1: the per-ray state (position, throughput) loaded and stored non-temporally (A/B)
-#endif
 __device__ __forceinline__ f3 ld3(const float* p, int i) {
-#if RT_DQN_NT_STATE
-    return make3(__builtin_nontemporal_load(p + (size_t)i * 3), __builtin_nontemporal_load(p + (size_t)i * 3 + 1),
-                 __builtin_nontemporal_load(p + (size_t)i * 3 + 2));
-#else
     return make3(p[(size_t)i * 3], p[(size_t)i * 3 + 1], p[(size_t)i * 3 + 2]);
-#endif
 }
 __device__ __forceinline__ void st3(float* p, int i, f3 v) {
-#if RT_DQN_NT_STATE
-    __builtin_nontemporal_store(v.x, p + (size_t)i * 3);
-    __builtin_nontemporal_store(v.y, p + (size_t)i * 3 + 1);
-    __builtin_nontemporal_store(v.z, p + (size_t)i * 3 + 2);
-#else
     p[(size_t)i * 3] = v.x;
     p[(size_t)i * 3 + 1] = v.y;
     p[(size_t)i * 3 + 2] = v.z;
-#endif
 }
 
 // ray id -> pixel of the tile list
@@ -1049,11 +773,10 @@ __global__ __launch_bounds__(256, MF > 0 ? RT_MF_DQN_WAVES : 1) void k_dqn_camer
 }
 
 // one bounce >= 1 for the rays of list[cur]: sample (Q already in a.rays.q), trace
-// FUSED: the cell was chosen by k_dqn_mlp<MT, true> (q[i] = its index bits, q[ldq + i] = qd)
 #ifndef RT_DQN_CT_WAVES
 #define RT_DQN_CT_WAVES 4  // occupancy floor of the table-route bounce kernel (archway 1024^2 x 16: 4 / 6 / 8 waves 375.5 / 417.7 / 416.3 ms per frame)
 #endif
-template <int MF, bool FUSED = false, bool QB = false, bool CT = false>
+template <int MF, bool QB = false, bool CT = false>
 __global__ __launch_bounds__(256, CT ? RT_DQN_CT_WAVES : (MF > 0 ? RT_MF_DQN_WAVES : 1)) void k_dqn_bounce(const DqnLaunch a, int bounce) {
     __shared__ float s_mfw[dqn_lds_floats(MF)];
     const int cur = (bounce - 1) & 1, nxt = bounce & 1;
@@ -1079,13 +802,9 @@ __global__ __launch_bounds__(256, CT ? RT_DQN_CT_WAVES : (MF > 0 ? RT_MF_DQN_WAV
         const float4 T4 = a.scene.shade[tri * kShadeF4 + 1];
         const float4 B4 = a.scene.shade[tri * kShadeF4 + 2];
         const SampleOut so =
-            FUSED ? sample_finish(__float_as_int(a.rays.q[i]), a.rays.q[(size_t)a.rays.ldq + i], make3(N4.x, N4.y, N4.z),
-                                  make3(T4.x, T4.y, T4.z), make3(B4.x, B4.y, B4.z), pos,
-                                  philox_shared(pixid, (uint32_t)sample, 1u + (uint32_t)bounce, a.seed_lo, a.seed_hi),
-                                  &tp, true)
-                  : sample_from_q<false, QB>(a.rays.q + i, (size_t)a.rays.ldq, make3(N4.x, N4.y, N4.z), make3(T4.x, T4.y, T4.z),
-                                  make3(B4.x, B4.y, B4.z), pos, pixid, (uint32_t)sample,
-                                  1u + (uint32_t)bounce, a.seed_lo, a.seed_hi, &tp, true);
+            sample_from_q<false, QB>(a.rays.q + i, (size_t)a.rays.ldq, make3(N4.x, N4.y, N4.z), make3(T4.x, T4.y, T4.z),
+                                     make3(B4.x, B4.y, B4.z), pos, pixid, (uint32_t)sample,
+                                     1u + (uint32_t)bounce, a.seed_lo, a.seed_hi, &tp, true);
         casts = 1;
         loc = pos;
         ntri = tri;
@@ -1446,18 +1165,9 @@ __global__ __launch_bounds__(256) void k_nq_image(const DqnLaunch a, const NqRay
 
 }  // namespace
 
-static hipError_t launch_dqn_mlp_fused(const DqnNet& net, const float* loc, const int32_t* list,
-                                       const int32_t* count, int max_rows, float* q, int ldq, const MlpSample* smp,
-                                       bool qb, hipStream_t stream);
-
-hipError_t launch_dqn_mlp(const DqnNet& net, const float* loc, const int32_t* list, const int32_t* count,
-                          int max_rows, float* q, int ldq, hipStream_t stream) {
-    return launch_dqn_mlp_fused(net, loc, list, count, max_rows, q, ldq, nullptr, false, stream);
-}
-
-// fused (smp != nullptr): the sampler runs in the forward kernel (k_dqn_mlp<MT, true>)
-static hipError_t launch_dqn_mlp_fused(const DqnNet& net, const float* loc, const int32_t* list, const int32_t* count,
-                                int max_rows, float* q, int ldq, const MlpSample* smp, bool qb, hipStream_t stream) {
+// qb: the renderer's bf16 Q (action-major only)
+static hipError_t launch_dqn_mlp_q(const DqnNet& net, const float* loc, const int32_t* list, const int32_t* count,
+                                   int max_rows, float* q, int ldq, bool qb, hipStream_t stream) {
     if (max_rows <= 0) return hipSuccess;
     KernelTimer kt(KT_DQN_MLP, stream);
     // this file's weight-streaming kernel; the weight-stationary one (rt_dqn_ws.hip) when
@@ -1471,19 +1181,18 @@ static hipError_t launch_dqn_mlp_fused(const DqnNet& net, const float* loc, cons
     }
     const int blocks = (max_rows + kTileM - 1) / kTileM;
     if (ldq != 0 && (ldq < blocks * kTileM || ldq % 4 != 0)) return hipErrorInvalidValue;
-    if (smp != nullptr) {
-        if constexpr (kFusedFits)
-            hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0, stream, net,
-                               loc, list, count, max_rows, q, ldq, *smp);
-        else
-            return hipErrorInvalidValue;
-    } else if (qb && ldq != 0)
-        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, false, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0, stream, net,
-                           loc, list, count, max_rows, q, ldq, MlpSample());
+    if (qb && ldq != 0)
+        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0, stream, net,
+                           loc, list, count, max_rows, q, ldq);
     else
-        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, false>), dim3((unsigned)blocks), dim3(kMlpThreads), 0, stream, net, loc,
-                           list, count, max_rows, q, ldq, MlpSample());
+        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT>), dim3((unsigned)blocks), dim3(kMlpThreads), 0, stream, net, loc,
+                           list, count, max_rows, q, ldq);
     return hipGetLastError();
+}
+
+hipError_t launch_dqn_mlp(const DqnNet& net, const float* loc, const int32_t* list, const int32_t* count,
+                          int max_rows, float* q, int ldq, hipStream_t stream) {
+    return launch_dqn_mlp_q(net, loc, list, count, max_rows, q, ldq, false, stream);
 }
 
 int dqn_mlp_tile_rows() { return kTileM; }
@@ -1496,16 +1205,13 @@ hipError_t launch_dqn_frame_begin(const DqnLaunch& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#ifndef RT_MF_DQN
-#define RT_MF_DQN 1  // 0: the casts on the fp32 filter (archway 512^2 x 16: 125.2 vs 120.9 ms, profiles/r3q)
-#endif
 // 64-triangle blocks of the matrix-core filter for this launch (0: the fp32 filter): the
 // image present and the camera inside its origin bound (as launch_render_t); -1: the
 // scene's exact BVH (large scenes, the launch view carries it)
 static int dqn_mf(const DqnLaunch& a) {
     if (a.scene.bvh_nodes != nullptr) return -1;
     const float cb = a.scene.mf_bound;
-    const bool mf = RT_MF_DQN && a.use_filter && a.scene.mf_frag != nullptr && a.t_scale > 0.0f &&
+    const bool mf = a.use_filter && a.scene.mf_frag != nullptr && a.t_scale > 0.0f &&
                     a.t_scale <= kFiltMaxTScale && fabsf(a.cam_x) <= cb && fabsf(a.cam_y) <= cb &&
                     fabsf(a.cam_z) <= cb;
     return mf ? (a.scene.n_tri <= 64 ? 1 : 4) : 0;
@@ -1522,61 +1228,40 @@ hipError_t launch_dqn_camera(const DqnLaunch& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#ifndef RT_DQN_QBF16
-#define RT_DQN_QBF16 1  // the renderer's Q between the forward and the sampler in bf16 (0: fp32; archway 512^2 x 16: 110.7 vs 121.0 ms, profiles/r4c)
-#endif
-#ifndef RT_DQN_FUSED
-#define RT_DQN_FUSED 0  // 1: the sampler inside k_dqn_mlp (measured slower: 143.9 vs 131.8 ms, archway 512^2 x 16)
-#endif
-
 hipError_t launch_dqn_bounce(const DqnLaunch& a, int bounce, hipStream_t stream) {
     const int cur = (bounce - 1) & 1;
-    // the fused sampler: the streaming forward (the weight-stationary A/B kernel writes Q)
-    const bool fused = RT_DQN_FUSED && kFusedFits && !(a.net.mlp_mode == kMlpStationary && dqn_mlp_ws_fits(a.net)) &&
-                       a.net.N[3] == kDqnActions && a.rays.ldq >= 2;
-    MlpSample smp;
-    smp.pix = a.rays.pix;
-    smp.n_pix = a.rays.n_pix;
-    smp.s0 = a.rays.s0;
-    smp.ev = 1u + (uint32_t)bounce;
-    smp.k0 = a.seed_lo;
-    smp.k1 = a.seed_hi;
     // the renderer's Q in bf16 (either forward kernel writes it)
-    const bool qb = RT_DQN_QBF16 && !fused && a.net.N[3] == kDqnActions;
-    hipError_t e = launch_dqn_mlp_fused(a.net, a.rays.loc, a.rays.list[cur], a.rays.count + cur, a.rays.n,
-                                        a.rays.q, a.rays.ldq, fused ? &smp : nullptr, qb, stream);
+    const bool qb = a.net.N[3] == kDqnActions;
+    hipError_t e = launch_dqn_mlp_q(a.net, a.rays.loc, a.rays.list[cur], a.rays.count + cur, a.rays.n, a.rays.q,
+                                    a.rays.ldq, qb, stream);
     if (e != hipSuccess) return e;
     KernelTimer kt(KT_DQN_BOUNCE, stream);
     const dim3 grid(ray_blocks(a));
     const CtabDev& T = a.scene.ctab[1];
     const int mf = dqn_mf(a);
-    const bool ct = RT_DQN_CTAB && qb && mf > 0 && T.masks != nullptr && T.bins == kCtabBins &&
+    const bool ct = qb && mf > 0 && T.masks != nullptr && T.bins == kCtabBins &&
                     T.graze_n == kCtabGraze && a.t_scale >= T.ts_min && T.words <= mf;
     if (ct) {
         if (mf == 1)
-            hipLaunchKernelGGL((k_dqn_bounce<1, false, true, true>), grid, dim3(256), 0, stream, a, bounce);
+            hipLaunchKernelGGL((k_dqn_bounce<1, true, true>), grid, dim3(256), 0, stream, a, bounce);
         else
-            hipLaunchKernelGGL((k_dqn_bounce<4, false, true, true>), grid, dim3(256), 0, stream, a, bounce);
+            hipLaunchKernelGGL((k_dqn_bounce<4, true, true>), grid, dim3(256), 0, stream, a, bounce);
         return hipGetLastError();
     }
     if (qb) {
         switch (dqn_mf(a)) {
-            case 1: hipLaunchKernelGGL((k_dqn_bounce<1, false, true>), grid, dim3(256), 0, stream, a, bounce); break;
-            case 4: hipLaunchKernelGGL((k_dqn_bounce<4, false, true>), grid, dim3(256), 0, stream, a, bounce); break;
-            case -1: hipLaunchKernelGGL((k_dqn_bounce<-1, false, true>), grid, dim3(256), 0, stream, a, bounce); break;
-            default: hipLaunchKernelGGL((k_dqn_bounce<0, false, true>), grid, dim3(256), 0, stream, a, bounce); break;
+            case 1: hipLaunchKernelGGL((k_dqn_bounce<1, true>), grid, dim3(256), 0, stream, a, bounce); break;
+            case 4: hipLaunchKernelGGL((k_dqn_bounce<4, true>), grid, dim3(256), 0, stream, a, bounce); break;
+            case -1: hipLaunchKernelGGL((k_dqn_bounce<-1, true>), grid, dim3(256), 0, stream, a, bounce); break;
+            default: hipLaunchKernelGGL((k_dqn_bounce<0, true>), grid, dim3(256), 0, stream, a, bounce); break;
         }
         return hipGetLastError();
     }
-    switch (dqn_mf(a) * 2 + (fused ? 1 : 0)) {
-        case 2: hipLaunchKernelGGL((k_dqn_bounce<1, false>), grid, dim3(256), 0, stream, a, bounce); break;
-        case 3: hipLaunchKernelGGL((k_dqn_bounce<1, true>), grid, dim3(256), 0, stream, a, bounce); break;
-        case 8: hipLaunchKernelGGL((k_dqn_bounce<4, false>), grid, dim3(256), 0, stream, a, bounce); break;
-        case 9: hipLaunchKernelGGL((k_dqn_bounce<4, true>), grid, dim3(256), 0, stream, a, bounce); break;
-        case -2: hipLaunchKernelGGL((k_dqn_bounce<-1, false>), grid, dim3(256), 0, stream, a, bounce); break;
-        case -1: hipLaunchKernelGGL((k_dqn_bounce<-1, true>), grid, dim3(256), 0, stream, a, bounce); break;
-        case 1: hipLaunchKernelGGL((k_dqn_bounce<0, true>), grid, dim3(256), 0, stream, a, bounce); break;
-        default: hipLaunchKernelGGL((k_dqn_bounce<0, false>), grid, dim3(256), 0, stream, a, bounce); break;
+    switch (dqn_mf(a)) {
+        case 1: hipLaunchKernelGGL((k_dqn_bounce<1>), grid, dim3(256), 0, stream, a, bounce); break;
+        case 4: hipLaunchKernelGGL((k_dqn_bounce<4>), grid, dim3(256), 0, stream, a, bounce); break;
+        case -1: hipLaunchKernelGGL((k_dqn_bounce<-1>), grid, dim3(256), 0, stream, a, bounce); break;
+        default: hipLaunchKernelGGL((k_dqn_bounce<0>), grid, dim3(256), 0, stream, a, bounce); break;
     }
     return hipGetLastError();
 }
@@ -1614,9 +1299,8 @@ hipError_t launch_dqn_view_pass(const DqnLaunch& a, const DqnView& v, bool fused
         if (!dqn_view_can_fuse(a.net) || v.out_q != nullptr) return hipErrorInvalidValue;
         KernelTimer kt(KT_DQN_MLP, stream);
         const int blocks = (a.rays.n + kTileM - 1) / kTileM;
-        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, false, false, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0,
-                           stream, a.net, a.rays.loc, a.rays.list[0], a.rays.count + 0, a.rays.n, a.rays.dir, a.rays.n,
-                           MlpSample());
+        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, false, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0,
+                           stream, a.net, a.rays.loc, a.rays.list[0], a.rays.count + 0, a.rays.n, a.rays.dir, a.rays.n);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     } else {

@@ -19,18 +19,6 @@
 #include "../../include/rtmi.h"
 #include "rt_hostframe.hpp"
 
-namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
-const DeviceScene& scene_device(const rt_scene* s);
-DeviceScene scene_launch_view(const rt_scene* s);
-int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
-bool ctab_wanted(const rt_scene* sc, const rt_camera* cam, const rt_params* p, int user);
-int ctx_blocks(rt_ctx* ctx, const int32_t* tiles, int n_tiles, int tile_size, int width, int height,
-               const BlockDesc** d_blocks, int* n_blocks);
-void surface_brdf_table(const rt_scene* scene, std::vector<float>* out);  // rt_sarsa_host.cpp
-}  // namespace rt
-
 namespace {
 
 int err(int code, const std::string& m) { return rt::set_error(code, m.c_str()); }
@@ -509,11 +497,6 @@ int check_dqn_view_params(const rt_params* p, const rt_dqn_view_opts* o) {
     return RT_OK;
 }
 
-#ifndef RT_DQN_VIEW_FUSED
-// the view's default route: 1 = the reduction inside k_dqn_mlp (DESIGN.md section 7 holds the A/B)
-#define RT_DQN_VIEW_FUSED 1
-#endif
-
 // The Q-network view: run_dqn's workspace, frame begin and passes over sample slots; a pass is
 // the camera, the forward over list[0], the reduction and the accumulation -- no bounce loop,
 // no host synchronisation.  aov: the per-pixel outputs of sample first_sample (each optional).
@@ -571,9 +554,10 @@ int run_dqn_view(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt
     rt::DqnView v = aov;
     v.surf = ws->surf;
     v.tint = opts->tint != 0;
-    // the route: the fused reduction unless asked otherwise (RTMI_DQN_VIEW_FUSED, read per call:
-    // tests and the A/B), the Q rows are wanted, or the network is pinned to the stationary kernel
-    bool fused = RT_DQN_VIEW_FUSED != 0;
+    // the route: the fused reduction, inside k_dqn_mlp (DESIGN.md section 7 holds the A/B), unless
+    // asked otherwise (RTMI_DQN_VIEW_FUSED, read per call: tests and the A/B), the Q rows are
+    // wanted, or the network is pinned to the stationary kernel
+    bool fused = true;
     if (const char* env = getenv("RTMI_DQN_VIEW_FUSED")) fused = atoi(env) != 0;
     fused = fused && v.out_q == nullptr && rt::dqn_view_can_fuse(a.net);
     a.rays.n_pix = n_pix;

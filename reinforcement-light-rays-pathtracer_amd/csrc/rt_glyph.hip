@@ -40,13 +40,6 @@
 #include "rt_view.hpp"
 
 namespace rt {
-const DeviceScene& scene_device(const rt_scene* s);
-int ctx_blocks(rt_ctx* ctx, const int32_t* tiles, int n_tiles, int tile_size, int width, int height,
-               const BlockDesc** d_blocks, int* n_blocks);
-RenderLaunch render_launch(const rt_scene* scene, const rt_camera* cam, const rt_params* p);
-}  // namespace rt
-
-namespace rt {
 namespace {
 
 static_assert(kGlyphSectors == RT_GLYPH_SECTORS && kGlyphTris == RT_GLYPH_TRIS && kGlyphSectors == kGridRes * kGridRes,

@@ -157,7 +157,7 @@ constexpr float kCtabHemi = 2e-6f;    // directions with d.N_s < -kCtabHemi (off
 constexpr int kCtabMaxWords = 4;  // mask words per entry: scenes of at most 256 triangles
 constexpr uint64_t kCtabGflagBit = 1ull << 63;  // (gflag tables: scenes of at most 63 triangles)
 // the render paths that may take the table (rt_capi.cpp ctab_wanted)
-constexpr int kCtabForRender = 0, kCtabForDqn = 1, kCtabForSarsa = 2;
+constexpr int kCtabForRender = 0, kCtabForDqn = 1;
 struct CtabHost {
     int n_tri = 0, n_surf = 0, n_patch = 0;
     int words = 1;        // ceil(n_tri / 64): masks, graze and cop hold that many words per entry
@@ -490,7 +490,7 @@ struct SarsaMap {
     unsigned long long* stats = nullptr;   // [2] launch: sum of per-pixel int(mean path length), zero paths
     unsigned long long* prof = nullptr;    // [8] RT_SARSA_PROF builds: per-phase s_memtime cycles (rt_sarsa.hip)
     // 1 = RT_SARSA_TD_OFF: the render samples the map as it stands and changes nothing in it
-    // (k_sarsa_render<.., TD = 2>: the TD event compiled out); takes precedence over td_inframe.  Host
+    // (k_sarsa_render_pq<.., TD = 2>: the TD event compiled out); takes precedence over td_inframe.  Host
     // only, and last: the kernels' argument layout of every older field is as it was
     int td_off = 0;
 };
@@ -505,7 +505,6 @@ constexpr int kKdStack = RT_KD_STACK;  // traversal stack entries per lane (LDS)
 hipError_t launch_sarsa_render(const RenderLaunch& r, const SarsaMap& m, hipStream_t stream);
 hipError_t launch_sarsa_apply(const SarsaMap& m, hipStream_t stream);
 bool sarsa_prof_compiled();  // rt_sarsa.hip was built with RT_SARSA_PROF=1 (per-phase cycle counters)
-bool sarsa_ctab_compiled();  // rt_sarsa.hip was built with RT_SARSA_CTAB=1 (the table route of its persistent kernel)
 hipError_t launch_sarsa_rebuild(const SarsaMap& m, hipStream_t stream);  // CDF + argmax from Q
 hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStream_t stream);  // of [v0, v0 + n)
 // ---- what the entries that cast from surface points share on the host (rt_capi.cpp): ----
@@ -513,8 +512,19 @@ hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStrea
 int set_error(int code, const char* msg);         // the thread's rt_last_error text; returns code
 int errorf(int code, const char* fmt, ...);       // set_error of the formatted text
 int ctx_device(const rt_ctx* ctx);
+const DeviceScene& scene_device(const rt_scene* s);
 DeviceScene scene_launch_view(const rt_scene* s);
+// the scene's host arrays: triangles [n][9], normals, albedo and emission [n][3]
+void scene_host(const rt_scene* s, const float** tri, const float** normals, const float** albedo,
+                const float** emission, int* n_surf, int* n_light);
+// the context's cached device copy of a tile list's 16x16 blocks
+int ctx_blocks(rt_ctx* ctx, const int32_t* tiles, int n_tiles, int tile_size, int width, int height,
+               const BlockDesc** d_blocks, int* n_blocks);
+RenderLaunch render_launch(const rt_scene* scene, const rt_camera* cam, const rt_params* p);
 int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
+bool ctab_wanted(const rt_scene* sc, const rt_camera* cam, const rt_params* p, int user);  // user: kCtabFor*
+// luminance / pi and luminance of each surface, [n_surf][2] (rt_sarsa_host.cpp)
+void surface_brdf_table(const rt_scene* scene, std::vector<float>* out);
 // ctx, scene, params, n, spp and hit_rule as all three entries want them, or RT_E_INVALID
 int check_leaving_args(const rt_ctx* ctx, const rt_scene* scene, const rt_params* p, int n);
 // The cast route of rays that leave known surfaces of the scene (closest_hit_route, rt_paths.hpp):
@@ -539,6 +549,10 @@ struct SarsaSweepView {
     const int32_t* vol_surf = nullptr;    // [n_vol] the surface each volume lies on
     unsigned long long* casts = nullptr;  // [1] the casts
 };
+int sarsa_bake_view(rt_sarsa* sa, size_t floats, SarsaBakeView* out);
+int sarsa_sweep_view(rt_sarsa* sa, SarsaSweepView* out);
+int sarsa_n_volumes(const rt_sarsa* sa);
+int sarsa_device(const rt_sarsa* sa);
 hipError_t launch_sarsa_nearest(const SarsaMap& m, const float* pos, const float* nrm, int n, int32_t* out,
                                 hipStream_t stream);
 // the radiance-map view (k_sarsa_view): r.sample_base = the first sample index, colours [n_vol] rgb (w unused);

@@ -10,10 +10,6 @@
 #include "../../include/rtmi.h"
 #include "rt_internal.hpp"
 
-namespace rt {
-int set_error(int code, const char* msg);
-}
-
 namespace {
 
 struct Rec {

@@ -18,14 +18,10 @@
 #include <float.h>
 
 #include "rt_trace.hpp"
-// the nearest-volume search (sarsa_nearest*, sarsa_resolve_walks) and its A/B knobs, shared with
+// the nearest-volume search (sarsa_nearest*, sarsa_resolve_walks), shared with
 // rt_views.hip (the read-only views and queries of the map) and rt_sweep.hip
 #include "rt_sarsa_search.hpp"
 
-// A/B knobs (timing builds only): RT_SARSA_NO_TD drops the TD atomics
-#ifndef RT_SARSA_NO_TD
-#define RT_SARSA_NO_TD 0
-#endif
 #ifndef RT_SARSA_PROF
 #define RT_SARSA_PROF 0  // 1: k_sarsa_render_pq sums per-phase s_memtime cycles into SarsaMap::prof (timing builds)
 #endif
@@ -203,7 +199,6 @@ __device__ __forceinline__ void td_event_inframe(const SarsaMap& m, int rv, int 
 
 template <int TD>
 __device__ __forceinline__ void td_event(const SarsaMap& m, int rv, int sector, float target) {
-    if (RT_SARSA_NO_TD) return;
     if constexpr (TD == 2) return;  // RT_SARSA_TD_OFF: the map is read-only
     if constexpr (TD == 1) {
         td_event_inframe(m, rv, sector, target);
@@ -215,7 +210,7 @@ __device__ __forceinline__ void td_event(const SarsaMap& m, int rv, int sector, 
     atomicAdd(&m.acc_cnt[k], 1u);
 }
 
-// The path's state between casts (k_sarsa_render, k_sarsa_render_pq)
+// The path's state between casts (k_sarsa_render_pq)
 struct SarsaPath {
     f3 o, d, tp;
     int depth, cur_rv, cur_sector;
@@ -314,150 +309,11 @@ __device__ __forceinline__ bool sarsa_step(const RenderLaunch& a, const SarsaMap
     return terminal;
 }
 
-// path_trace_reinforcement_iterative (reinforcement_path_tracing.cu:50-120), GPU preset
-// MF > 0: every cast on the matrix-core filter (closest_hit_mf, wave-level; the launcher
-// picks it as launch_render_t does for k_render: image present, camera inside its bound)
-// MF: the exact phase's LDS is the wave's own block of the k-d stack (free between searches;
-// wave_lds_sync orders the two uses), so the workgroup needs the stack's 32 KB only; scenes
-// of <= 64 triangles held to 4 waves per SIMD (<= 128 VGPRs without spills; the 4-block
-// variant would spill there and keeps the compiler's 3 waves).
-#ifndef RT_MF_SARSA_WAVES
-#define RT_MF_SARSA_WAVES 4
-#endif
-template <int RULE, int MF, int TD>
-__global__ __launch_bounds__(256, MF == 1 ? RT_MF_SARSA_WAVES : 1) void k_sarsa_render(const RenderLaunch a,
-                                                                                     const SarsaMap m) {
-    const int lg = a.split_log2;
-    const BlockDesc blk = a.blocks[blockIdx.x >> lg];
-    const int part = blockIdx.x & (a.split - 1);
-    const int q = (part << (8 - lg)) + ((int)threadIdx.x >> lg);
-    const int chunk = threadIdx.x & (a.split - 1);
-    const int lane = threadIdx.x & 63;
-    const int lx = q & 15, ly = q >> 4;
-    const int px = blk.px0 + lx, py = blk.py0 + ly;
-    const bool valid = (px < a.clip_x1) && (py < a.clip_y1);
-    const uint32_t pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
-    const float4* __restrict__ shade = a.scene.shade;
-    const int n_surf = a.scene.n_surf;
-    const int s_end = (chunk + 1) * a.per_chunk;
-    __shared__ int kd_stack[kKdStack * 256];
-    int* const st = kd_stack_of(kd_stack);
-    static_assert(kKdStack * 64 >= kMfWaveFloats, "the exact phase's LDS fits a wave's stack block");
-    float* const wl = reinterpret_cast<float*>(kd_stack + ((int)threadIdx.x >> 6) * (kKdStack * 64));
-
-    int s = valid ? chunk * a.per_chunk : s_end;
-    int depth = 0;
-    int cur_rv = -1, cur_sector = -1;
-    float cur_brdf = 0.0f;
-    f3 o = make3(a.cam_x, a.cam_y, a.cam_z), d = make3(0.f, 0.f, 1.f);
-    f3 tp = make3(1.f, 1.f, 1.f), acc = make3(0.f, 0.f, 0.f);
-    unsigned n_casts = 0, n_zero = 0;
-    if (s < s_end) {
-        float r1, r2;
-        draw2(pix, a.sample_base + (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
-        camera_ray<1>(a, px, py, r1, r2, &d);
-    }
-    for (;;) {
-        const bool active = s < s_end;
-        if (__ballot(active) == 0ull) break;
-        Hit h;
-        h.t = 0.0f;
-        h.tri = -1;
-        if constexpr (MF > 0) {
-            wave_lds_sync();  // the previous search's stack accesses stay before the exact phase
-            h = closest_hit_mf<RULE, false, MF>(a.scene, o, d, a.t_scale, active, wl);
-            wave_lds_sync();  // and its LDS traffic before the next search
-        } else if (active) {
-            h = closest_hit_sel<RULE>(a.scene, a.use_filter, o, d, a.t_scale);
-        }
-        // (inactive lanes go on to the volume search, which the whole wave runs, with no query)
-        if (active) ++n_casts;
-        const bool is_surf = active && (h.tri >= 0) && (h.tri < n_surf);
-        f3 pos = o;
-        f3 nrm = make3(0.f, 0.f, 0.f);
-        if (is_surf) {
-            const float Dx = d.x * a.t_scale, Dy = d.y * a.t_scale, Dz = d.z * a.t_scale;
-            pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
-            const float4 N4 = shade[h.tri * kShadeF4 + 0];
-            nrm = make3(N4.x, N4.y, N4.z);
-        }
-        // temporal_difference_update_radiance_volume_sector at every bounce after a
-        // sampled sector; the volume at a surface hit serves both the TD target and
-        // the next sampling step (one search call site: the search is divergent)
-        const bool td = active && depth > 0 && cur_rv >= 0 && cur_sector >= 0;
-        int rv = -1;
-        if (is_surf && (depth == 0 || td))
-            rv = m.use_grid ? sarsa_nearest_grid_tri(m, h.tri, pos, nrm) : kNeedWalk;
-        if (m.use_grid)  // the grid's few undecided queries: walked by the whole wave
-            sarsa_resolve_walks(m, pos, nrm, &rv, kd_stack + ((int)threadIdx.x >> 6) * (kKdStack * 64), st, lane);
-        else if (rv == kNeedWalk)
-            rv = sarsa_nearest(m, pos, nrm, st);
-        if (!active) continue;
-        SarsaPath P{o, d, tp, depth, cur_rv, cur_sector, cur_brdf, false};
-        f3 L;
-        const bool terminal = sarsa_step<TD>(a, m, h, is_surf, pos, nrm, rv, td, pix, s, P, n_casts, &L);
-        o = P.o;
-        d = P.d;
-        tp = P.tp;
-        depth = P.depth;
-        cur_rv = P.cur_rv;
-        cur_sector = P.cur_sector;
-        cur_brdf = P.cur_brdf;
-        if (terminal) {
-            acc.x = acc.x + L.x;
-            acc.y = acc.y + L.y;
-            acc.z = acc.z + L.z;
-            // a zero-contribution light path (reinforcement_path_tracing.cu:36-40)
-            n_zero += (!P.null_ray && (L.x + L.y + L.z) / 3.f < kThroughputThreshold) ? 1u : 0u;
-            ++s;
-            depth = 0;
-            cur_rv = -1;
-            cur_sector = -1;
-            tp = make3(1.f, 1.f, 1.f);
-            o = make3(a.cam_x, a.cam_y, a.cam_z);
-            if (s < s_end) {
-                float r1, r2;
-                draw2(pix, a.sample_base + (uint32_t)s, 0u, a.seed_lo, a.seed_hi, &r1, &r2);
-                camera_ray<1>(a, px, py, r1, r2, &d);
-            }
-        }
-    }
-    const int base = lane & ~(a.split - 1);
-    f3 tot = acc;
-    unsigned pix_casts = n_casts;  // a sample's path length is its ray casts
-    for (int k = 1; k < a.split; ++k) {
-        const float vx = __shfl(acc.x, base + k, 64);
-        const float vy = __shfl(acc.y, base + k, 64);
-        const float vz = __shfl(acc.z, base + k, 64);
-        pix_casts += (unsigned)__shfl((int)n_casts, base + k, 64);
-        tot.x = tot.x + vx;
-        tot.y = tot.y + vy;
-        tot.z = tot.z + vz;
-    }
-    if (m.stats != nullptr) {
-        // main.cu:321-339 statistics: int(total_path_lengths / SAMPLES_PER_PIXEL) per pixel
-        const unsigned pf = (valid && chunk == 0) ? pix_casts / (unsigned)a.spp : 0u;
-        const unsigned sp = wave_sum(pf), sz = wave_sum(n_zero);
-        if (lane == 0) {
-            atomicAdd(&m.stats[0], (unsigned long long)sp);
-            atomicAdd(&m.stats[1], (unsigned long long)sz);
-        }
-    }
-    if (valid && chunk == 0) {
-        const float fs = (float)a.spp;
-        float* dst = a.out + ((size_t)(blk.oy0 + ly) * (size_t)a.out_pitch + (size_t)(blk.ox0 + lx)) * 3;
-        store_rgb(dst, tot.x / fs, tot.y / fs, tot.z / fs);
-    }
-    if (a.casts != nullptr) {
-        const unsigned total = wave_sum(n_casts);
-        if (lane == 0) atomicAdd(a.casts, (unsigned long long)total);
-    }
-}
-
-// k_sarsa_render on a persistent grid over a launch-wide (pixel, chunk) queue, as
-// k_render_pq does for the GPU preset (rt_kernels.hip): a lane claims a chunk (the samples
-// [c m, (c + 1) m) of pixel p), traces them one after another with k_sarsa_render's
-// per-cast work (sarsa_step) and its fixed-chunk sum, stores the chunk's value sum and ray
+// path_trace_reinforcement_iterative (reinforcement_path_tracing.cu:50-120), GPU preset, on a
+// persistent grid over a launch-wide (pixel, chunk) queue, as k_render_pq does for the GPU
+// preset (rt_kernels.hip): a lane claims a chunk (the samples [c m, (c + 1) m) of pixel p),
+// traces them one after another (per cast: the closest hit, the volume search at a surface
+// hit, sarsa_step), sums their values in sample order, stores the chunk's value sum and ray
 // casts, and claims the next, so lanes idle only at the end of the frame instead of at
 // each wave's longest path (frame 0: 41 casts per path on door_room, up to 80).
 // k_sarsa_fold adds each pixel's chunks in chunk order and takes its path-length statistic.
@@ -468,20 +324,15 @@ __global__ __launch_bounds__(256, MF == 1 ? RT_MF_SARSA_WAVES : 1) void k_sarsa_
 #endif
 // BVH: scenes with the exact BVH (large models, rt_scene_set_accel): the casts through
 // closest_hit_bvh, its stack in the lane's k-d stack column (free until the volume search)
-// CT > 0: the casts take their candidates from tables (CT mask words; k_render_pq's CT route:
-// a camera ray the cull of its pixel's 16x4 rectangle in a.cull, a bounce ray the candidate
-// table of the surface it leaves) and closest_hit_cand tests them in index order
-template <int RULE, int MF, int TD, bool BVH = false, int CT = 0>
+template <int RULE, int TD, bool BVH = false>
 #ifndef RT_SARSA_BVH_WAVES
 #define RT_SARSA_BVH_WAVES 4  // the BVH variant's traversal state: 128 VGPRs, no spills (96 at 5 waves spilled)
 #endif
-__global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : (MF == 1 ? RT_MF_SARSA_WAVES : RT_SARSA_WAVES)) void k_sarsa_render_pq(const RenderLaunch a,
+__global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : RT_SARSA_WAVES) void k_sarsa_render_pq(const RenderLaunch a,
                                                                                         const SarsaMap m) {
     __shared__ __attribute__((aligned(16))) int kd_stack[kKdStack * 256];
-    static_assert(kKdStack * 64 >= kMfWaveFloats, "the exact phase's LDS fits a wave's stack block");
     int* const st = kd_stack_of(kd_stack);
     int* const blk_ws = kd_stack + ((int)threadIdx.x >> 6) * (kKdStack * 64);  // the wave's block
-    float* const wl = reinterpret_cast<float*>(blk_ws);
     const int lane = threadIdx.x & 63;
     const float4* __restrict__ shade = a.scene.shade;
     const int n_surf = a.scene.n_surf;
@@ -493,7 +344,6 @@ __global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : (MF == 1 ? RT_MF_SA
     long long item = 0;
     int s = 0, s_end = 0, px = 0, py = 0;
     uint32_t pix = 0;
-    int surf = -1, cidx = 0;  // CT: the surface the ray leaves; the pixel's rectangle in a.cull
     SarsaPath P{cam, make3(0.f, 0.f, 1.f), make3(1.f, 1.f, 1.f), 0, -1, -1, 0.0f, false};
     f3 acc = make3(0.f, 0.f, 0.f);
     unsigned n_casts = 0, n_zero = 0, casts0 = 0;
@@ -539,7 +389,6 @@ __global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : (MF == 1 ? RT_MF_SA
                         py = blk.py0 + (q >> 4);
                         if (px < a.clip_x1 && py < a.clip_y1) {
                             pix = (uint32_t)py * (uint32_t)a.width + (uint32_t)px;
-                            cidx = (int)(p >> 8) * 4 + (q >> 6);
                             s = c * a.per_chunk;
                             s_end = s + a.per_chunk;
                             acc = make3(0.f, 0.f, 0.f);
@@ -573,24 +422,6 @@ __global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : (MF == 1 ? RT_MF_SA
         if constexpr (BVH) {
             static_assert(kKdStack >= kBvhMaxDepth, "the BVH stack fits the k-d stack column");
             if (active) h = closest_hit_bvh<RULE, 64>(a.scene, P.o, P.d, a.t_scale, st);
-        } else if constexpr (CT > 0) {
-            uint64_t F[CT];
-#pragma unroll
-            for (int k = 0; k < CT; ++k) F[k] = 0ull;
-            if (active && P.depth == 0) {
-#pragma unroll
-                for (int k = 0; k < CT; ++k)
-                    F[k] = (k < kRenderCullWords) ? a.cull[(size_t)cidx * kRenderCullWords + k] : 0ull;
-            } else if (active) {
-                ctab_candidates<CT>(a.scene.ctab[RULE], a.scene.n_tri, n_surf, surf, P.o, P.d, F);
-            }
-            wave_lds_sync();
-            h = closest_hit_cand<RULE, CT>(a.scene, F, P.o, P.d, a.t_scale, wl);
-            wave_lds_sync();
-        } else if constexpr (MF > 0) {
-            wave_lds_sync();
-            h = closest_hit_mf<RULE, false, MF>(a.scene, P.o, P.d, a.t_scale, active, wl);
-            wave_lds_sync();
         } else if (active) {
             h = closest_hit_sel<RULE>(a.scene, a.use_filter, P.o, P.d, a.t_scale);
         }
@@ -622,7 +453,6 @@ __global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : (MF == 1 ? RT_MF_SA
         const uint64_t pt3 = __builtin_amdgcn_s_memtime();
         f3 L;
         const bool term = active && sarsa_step<TD>(a, m, h, is_surf, pos, nrm, rv, td, pix, s, P, n_casts, &L);
-        surf = h.tri;
         const uint64_t pt4 = __builtin_amdgcn_s_memtime();
         pr[0] += pt1 - pt0;
         pr[1] += pt2 - pt1;
@@ -635,7 +465,6 @@ __global__ __launch_bounds__(256, BVH ? RT_SARSA_BVH_WAVES : (MF == 1 ? RT_MF_SA
         if (!active) continue;
         f3 L;
         const bool term = sarsa_step<TD>(a, m, h, is_surf, pos, nrm, rv, td, pix, s, P, n_casts, &L);
-        surf = h.tri;  // (a continuing path leaves the surface it hit)
         if (term) {
 #endif
             acc.x = acc.x + L.x;
@@ -775,107 +604,32 @@ __global__ __launch_bounds__(256) void k_sarsa_rebuild_range(const SarsaMap m, i
 
 }  // namespace
 
-#ifndef RT_MF_SARSA
-#define RT_MF_SARSA 0  // 1: the casts on the matrix-core filter (measured slower: DESIGN.md §4)
-#endif
-
-#ifndef RT_SARSA_CTAB
-#define RT_SARSA_CTAB 0  // 1: k_sarsa_render_pq's casts from the candidate tables (door_room 512^2 x 256: 110.3 vs 92.1 ms per frame)
-#endif
-
-#ifndef RT_SARSA_PQ
-#define RT_SARSA_PQ 1  // 0: the per-pixel k_sarsa_render (A/B builds)
-#endif
-
 namespace {
 
-// the render launch of one TD rule (TD: k_sarsa_render's template argument, so the default
+// the render launch of one TD rule (TD: k_sarsa_render_pq's template argument, so the default
 // frame-synchronous kernel carries no in-frame branch)
 template <int TD>
 hipError_t launch_sarsa_render_t(const RenderLaunch& a, const SarsaMap& m, hipStream_t stream) {
-    const float cb = a.scene.mf_bound;
-    const bool mf = RT_MF_SARSA && a.scene.bvh_nodes == nullptr && a.use_filter && a.scene.mf_frag != nullptr && a.t_scale > 0.0f &&
-                    a.t_scale <= kFiltMaxTScale && fabsf(a.cam_x) <= cb && fabsf(a.cam_y) <= cb &&
-                    fabsf(a.cam_z) <= cb;
-    const bool one = a.scene.n_tri <= 64;
-    // the table route (k_sarsa_render_pq CT): as k_render_pq's -- the scene's candidate table for
-    // this hit rule and t_scale, the camera rays' rectangle cull (pitch 0, filter records valid
-    // for the camera)
-    const CtabDev& T = a.scene.ctab[a.hit_rule == 0 ? 0 : 1];
-    const bool ct = !mf && RT_SARSA_CTAB && a.scene.bvh_nodes == nullptr && a.cull != nullptr && view_cull_wanted(a) &&
-                    T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze && a.t_scale >= T.ts_min &&
-                    T.words <= (one ? 1 : 4);
-    if constexpr (RT_SARSA_PQ) {
-        if (a.csum == nullptr || a.work == nullptr) return hipErrorInvalidValue;
-        (void)hipMemsetAsync(a.work, 0, sizeof(unsigned long long), stream);
-        // as many workgroups as fit: RT_SARSA_WAVES per CU (registers and the k-d stack's LDS)
-        const int per_cu = a.scene.bvh_nodes != nullptr ? RT_SARSA_BVH_WAVES : (mf ? RT_MF_SARSA_WAVES : RT_SARSA_WAVES);
-        int wgs = min(a.n_blocks * a.split, per_cu * device_cu_count());
-        if (m.max_wgs > 0) wgs = min(wgs, m.max_wgs);  // rt_sarsa_set_inframe_lanes
-        const dim3 grid((unsigned)wgs);
-        if constexpr (RT_MF_SARSA) {
-            if (mf) {
-                if (a.hit_rule == 0 && one)
-                    hipLaunchKernelGGL((k_sarsa_render_pq<0, 1, TD>), grid, dim3(256), 0, stream, a, m);
-                else if (a.hit_rule == 0)
-                    hipLaunchKernelGGL((k_sarsa_render_pq<0, 4, TD>), grid, dim3(256), 0, stream, a, m);
-                else if (one)
-                    hipLaunchKernelGGL((k_sarsa_render_pq<1, 1, TD>), grid, dim3(256), 0, stream, a, m);
-                else
-                    hipLaunchKernelGGL((k_sarsa_render_pq<1, 4, TD>), grid, dim3(256), 0, stream, a, m);
-            }
-        }
-        if (a.scene.bvh_nodes != nullptr) {  // the exact BVH (large scenes)
-            if (a.hit_rule == 0)
-                hipLaunchKernelGGL((k_sarsa_render_pq<0, 0, TD, true>), grid, dim3(256), 0, stream, a, m);
-            else
-                hipLaunchKernelGGL((k_sarsa_render_pq<1, 0, TD, true>), grid, dim3(256), 0, stream, a, m);
-        } else if (ct) {
-            RenderLaunch c = a;  // one workgroup per 16x16 block: the masks of its four 16x4 rectangles
-            c.split = 1;
-            c.split_log2 = 0;
-            (void)launch_cull(c, stream);
-            if (a.hit_rule == 0) {
-                if (one)
-                    hipLaunchKernelGGL((k_sarsa_render_pq<0, 0, TD, false, 1>), grid, dim3(256), 0, stream, a, m);
-                else
-                    hipLaunchKernelGGL((k_sarsa_render_pq<0, 0, TD, false, 4>), grid, dim3(256), 0, stream, a, m);
-            } else {
-                if (one)
-                    hipLaunchKernelGGL((k_sarsa_render_pq<1, 0, TD, false, 1>), grid, dim3(256), 0, stream, a, m);
-                else
-                    hipLaunchKernelGGL((k_sarsa_render_pq<1, 0, TD, false, 4>), grid, dim3(256), 0, stream, a, m);
-            }
-        } else if (!mf) {
-            if (a.hit_rule == 0)
-                hipLaunchKernelGGL((k_sarsa_render_pq<0, 0, TD>), grid, dim3(256), 0, stream, a, m);
-            else
-                hipLaunchKernelGGL((k_sarsa_render_pq<1, 0, TD>), grid, dim3(256), 0, stream, a, m);
-        }
-        hipLaunchKernelGGL(k_sarsa_fold, dim3((unsigned)a.n_blocks), dim3(256), 0, stream, a, m);
-        return hipGetLastError();
+    if (a.csum == nullptr || a.work == nullptr) return hipErrorInvalidValue;
+    (void)hipMemsetAsync(a.work, 0, sizeof(unsigned long long), stream);
+    // as many workgroups as fit: RT_SARSA_WAVES per CU (registers and the k-d stack's LDS)
+    const int per_cu = a.scene.bvh_nodes != nullptr ? RT_SARSA_BVH_WAVES : RT_SARSA_WAVES;
+    int wgs = min(a.n_blocks * a.split, per_cu * device_cu_count());
+    if (m.max_wgs > 0) wgs = min(wgs, m.max_wgs);  // rt_sarsa_set_inframe_lanes
+    const dim3 grid((unsigned)wgs);
+    if (a.scene.bvh_nodes != nullptr) {  // the exact BVH (large scenes)
+        if (a.hit_rule == 0)
+            hipLaunchKernelGGL((k_sarsa_render_pq<0, TD, true>), grid, dim3(256), 0, stream, a, m);
+        else
+            hipLaunchKernelGGL((k_sarsa_render_pq<1, TD, true>), grid, dim3(256), 0, stream, a, m);
     } else {
-        const dim3 grid((unsigned)(a.n_blocks * a.split));
-        if constexpr (RT_MF_SARSA) {
-            if (mf) {
-                if (a.hit_rule == 0 && one)
-                    hipLaunchKernelGGL((k_sarsa_render<0, 1, TD>), grid, dim3(256), 0, stream, a, m);
-                else if (a.hit_rule == 0)
-                    hipLaunchKernelGGL((k_sarsa_render<0, 4, TD>), grid, dim3(256), 0, stream, a, m);
-                else if (one)
-                    hipLaunchKernelGGL((k_sarsa_render<1, 1, TD>), grid, dim3(256), 0, stream, a, m);
-                else
-                    hipLaunchKernelGGL((k_sarsa_render<1, 4, TD>), grid, dim3(256), 0, stream, a, m);
-            }
-        }
-        if (!mf) {
-            if (a.hit_rule == 0)
-                hipLaunchKernelGGL((k_sarsa_render<0, 0, TD>), grid, dim3(256), 0, stream, a, m);
-            else
-                hipLaunchKernelGGL((k_sarsa_render<1, 0, TD>), grid, dim3(256), 0, stream, a, m);
-        }
-        return hipGetLastError();
+        if (a.hit_rule == 0)
+            hipLaunchKernelGGL((k_sarsa_render_pq<0, TD>), grid, dim3(256), 0, stream, a, m);
+        else
+            hipLaunchKernelGGL((k_sarsa_render_pq<1, TD>), grid, dim3(256), 0, stream, a, m);
     }
+    hipLaunchKernelGGL(k_sarsa_fold, dim3((unsigned)a.n_blocks), dim3(256), 0, stream, a, m);
+    return hipGetLastError();
 }
 
 }  // namespace
@@ -901,7 +655,6 @@ hipError_t launch_sarsa_rebuild_range(const SarsaMap& m, int v0, int n, hipStrea
 }
 
 bool sarsa_prof_compiled() { return RT_SARSA_PROF != 0; }
-bool sarsa_ctab_compiled() { return RT_SARSA_CTAB != 0; }
 
 hipError_t launch_sarsa_apply(const SarsaMap& m, hipStream_t stream) {
     if (m.n_vol <= 0) return hipSuccess;

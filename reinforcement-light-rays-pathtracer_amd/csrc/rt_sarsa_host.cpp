@@ -24,17 +24,6 @@
 #include "rt_hostframe.hpp"
 
 namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
-const DeviceScene& scene_device(const rt_scene* s);
-void scene_host(const rt_scene* s, const float** tri, const float** normals, const float** albedo,
-                const float** emission, int* n_surf, int* n_light);
-int ctx_blocks(rt_ctx* ctx, const int32_t* tiles, int n_tiles, int tile_size, int width, int height,
-               const BlockDesc** d_blocks, int* n_blocks);
-RenderLaunch render_launch(const rt_scene* scene, const rt_camera* cam, const rt_params* p);
-int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wanted);
-bool ctab_wanted(const rt_scene* sc, const rt_camera* cam, const rt_params* p, int user);
-
 // read_hemisphere_locations_and_normals (GPU/utils/hemisphere_helpers.cu:230-278): one
 // "x y z nx ny nz" per line, tokens split on ' ' and read with std::stof, the first
 // three the location, the rest the normal
@@ -385,9 +374,6 @@ struct rt_sarsa {
     float* d_csum = nullptr;
     size_t csum_cap = 0;
     unsigned long long* d_work = nullptr;
-    // the camera rays' rectangle masks of its table route (four 16x4 rectangles per block)
-    unsigned long long* d_cull = nullptr;
-    size_t cull_cap = 0;
     // the views' per-volume colour table, rgb in a float4 (rt_sarsa_set_view_colours; in allocs)
     float4* d_view = nullptr;
     // rt_sarsa_bake: the volumes' surfaces (in allocs), its chunk sums (grown up to its batch
@@ -400,7 +386,6 @@ struct rt_sarsa {
         (void)hipSetDevice(device);
         for (void* p : allocs) (void)hipFree(p);
         if (d_csum) (void)hipFree(d_csum);
-        if (d_cull) (void)hipFree(d_cull);
         if (d_work) (void)hipFree(d_work);
         if (d_bake_csum) (void)hipFree(d_bake_csum);
         if (d_bake_work) (void)hipFree(d_bake_work);
@@ -442,8 +427,6 @@ int check_sarsa_params(const rt_params* p, bool view = false) {
 int render_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, const rt_params* p,
                  const rt::BlockDesc* d_blocks, int n_blocks, int clip_x1, int clip_y1, int out_pitch,
                  float* d_out, unsigned long long* d_casts, hipStream_t stream, bool apply) {
-    const int rc = rt::scene_ensure_ctab(scene, p->hit_rule, p->t_scale, rt::ctab_wanted(scene, cam, p, rt::kCtabForSarsa));
-    if (rc != RT_OK) return rc;
     rt::RenderLaunch a = rt::render_launch(scene, cam, p);
     a.blocks = d_blocks;
     a.n_blocks = n_blocks;
@@ -465,15 +448,6 @@ int render_frame(rt_sarsa* sa, const rt_scene* scene, const rt_camera* cam, cons
     if (!sa->d_work) RT_HIPE(hipMalloc(&sa->d_work, sizeof(unsigned long long)));
     a.csum = sa->d_csum;
     a.work = sa->d_work;
-    const size_t ncull = (size_t)n_blocks * 4 * rt::kRenderCullWords;
-    if (ncull > sa->cull_cap) {
-        if (sa->d_cull) (void)hipFree(sa->d_cull);
-        sa->d_cull = nullptr;
-        sa->cull_cap = 0;
-        RT_HIPE(hipMalloc(&sa->d_cull, sizeof(unsigned long long) * ncull));
-        sa->cull_cap = ncull;
-    }
-    a.cull = sa->d_cull;
     RT_HIPE(hipMemsetAsync(sa->m.stats, 0, 2 * sizeof(unsigned long long), stream));
     // RT_SARSA_PROF (with an RT_SARSA_PROF=1 kernel build): the render's per-phase cycles to stderr.
     // On a default build the counters are never written: warn once, and do not synchronise.

@@ -10,23 +10,6 @@
 
 #include "rt_trace.hpp"
 
-// A/B knobs of the search (timing / statistics builds only; all but SCAN_STATS change results):
-// RT_SARSA_NO_KD replaces the nearest-volume search by volume 0, RT_SARSA_FIRST_ONLY takes the
-// first candidate of the grid list (same normal class: frame-0 paths keep their statistics),
-// RT_SARSA_SCAN_STATS counts the grid scan steps (4 candidates each) in grid_fallbacks
-#ifndef RT_SARSA_NO_KD
-#define RT_SARSA_NO_KD 0
-#endif
-#ifndef RT_SARSA_SCAN_STATS
-#define RT_SARSA_SCAN_STATS 0
-#endif
-#ifndef RT_SARSA_FIRST_ONLY
-#define RT_SARSA_FIRST_ONLY 0
-#endif
-#ifndef RT_SARSA_NO_FALLBACK  // grid answer even where the KD walk is needed (timing only)
-#define RT_SARSA_NO_FALLBACK 0
-#endif
-
 namespace rt {
 
 namespace {
@@ -44,13 +27,12 @@ __device__ __forceinline__ float len3(float x, float y, float z) { return sqrtf(
 // lane of the wave's own block (st[k * 64], kd_stack_of); its depth is bounded by the
 // tree depth (host-checked).
 // the k-d stack column of this lane: each wave owns a contiguous kKdStack x 64 block (the
-// exact phase of the matrix-core filter reuses it between searches: k_sarsa_render<MF>)
+// wave-cooperative walk's frontier reuses it between searches: sarsa_nearest_wave)
 __device__ __forceinline__ int* kd_stack_of(int* kd_stack) {
     return kd_stack + ((int)threadIdx.x >> 6) * (kKdStack * 64) + ((int)threadIdx.x & 63);
 }
 
 __device__ int sarsa_nearest(const SarsaMap& m, f3 pos, f3 nrm, int* st) {
-    if (RT_SARSA_NO_KD) return 0;
     const uint4* __restrict__ kd = m.kd4;
     int best = 0;
     float best_d = len3(pos.x - m.root_x, pos.y - m.root_y, pos.z - m.root_z);
@@ -91,12 +73,6 @@ __device__ int sarsa_nearest(const SarsaMap& m, f3 pos, f3 nrm, int* st) {
 // (sarsa_resolve_walks).
 constexpr int kNeedWalk = -2;  // sarsa_nearest_grid: only the KD walk decides this query
 
-#ifndef RT_SARSA_HEAD
-#define RT_SARSA_HEAD 1  // the cell's range and first three candidates as one 64-B record (0: range, then leaves)
-#endif
-#ifndef RT_SARSA_TRIREC
-#define RT_SARSA_TRIREC 1  // 0: class -> grid descriptor -> cell start / end as four dependent loads (A/B)
-#endif
 // G, D: the class grid's origin (w: first cell, bits) and cells per axis
 __device__ int sarsa_nearest_grid_gd(const SarsaMap& m, float4 G, int4 D, f3 pos) {
     {
@@ -108,22 +84,12 @@ __device__ int sarsa_nearest_grid_gd(const SarsaMap& m, float4 G, int4 D, f3 pos
         const int iz = (int)floorf(fminf(fmaxf((pos.z - G.z) * ic, 0.0f), (float)(D.z - 1)));
         const uint32_t c = __float_as_uint(G.w) + (uint32_t)((iz * D.y + iy) * D.x + ix);
         uint32_t k0, e;
-#if RT_SARSA_HEAD
+        // the cell's range and first three candidates as one 64-B record
         const float4* hp = m.cell_head + (size_t)c * 4;
         const float4 h0 = hp[0];
         const float4 H[3] = {hp[1], hp[2], hp[3]};
         k0 = __float_as_uint(h0.x);
         e = __float_as_uint(h0.y);
-#else
-        if (RT_SARSA_TRIREC) {
-            const uint2 r = m.cell_range[c];
-            k0 = r.x;
-            e = r.y;
-        } else {
-            k0 = m.cell_start[c];
-            e = m.cell_start[c + 1];
-        }
-#endif
         // The list is sorted by distance to the cell centre C: d(q, L) >= d(C, L) - d(q, C),
         // so once d(C, L) exceeds best + d(q, C) (with a 2^-12 margin: such a candidate's
         // float distance is strictly above the best, no tie either) no later one can win.
@@ -134,14 +100,7 @@ __device__ int sarsa_nearest_grid_gd(const SarsaMap& m, float4 G, int4 D, f3 pos
         const float dq = __builtin_sqrtf((qx * qx + qy * qy) + qz * qz);
         float b1 = INFINITY, b2 = INFINITY;
         int bv = -1;
-#if RT_SARSA_SCAN_STATS  // statistics builds only: grid_fallbacks counts scan steps instead
-        uint32_t steps = 0;
-#endif
-#if RT_SARSA_FIRST_ONLY  // timing only: the first listed candidate (wrong volumes)
-        if (k0 < e) return __float_as_int(m.grid_leaf[k0].w);
-#endif
         uint32_t kb = k0;
-#if RT_SARSA_HEAD
         // the cell record's own first three candidates (no break test before the first
         // candidates: the limit is infinite there); the scan goes on from the fourth.  Where
         // the scan's batches start does not change its answer: the break only skips
@@ -161,11 +120,7 @@ __device__ int sarsa_nearest_grid_gd(const SarsaMap& m, float4 G, int4 D, f3 pos
             }
         }
         kb = k0 + 3;
-#endif
         for (uint32_t k = kb; k < e; k += 4) {  // 4 candidate loads in flight
-#if RT_SARSA_SCAN_STATS
-            ++steps;
-#endif
             float4 L[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) L[u] = m.grid_leaf[min(k + (uint32_t)u, e - 1u)];
@@ -189,16 +144,12 @@ __device__ int sarsa_nearest_grid_gd(const SarsaMap& m, float4 G, int4 D, f3 pos
                 }
             }
         }
-#if RT_SARSA_SCAN_STATS
-        atomicAdd(m.grid_fallbacks, (unsigned long long)steps);
-#endif
         const float d = sqrtf(b1);
         if (bv >= 0 && d < m.grid_h && sqrtf(b2) != d) {
             const float d0 = len3(pos.x - m.root_x, pos.y - m.root_y, pos.z - m.root_z);
             return d < d0 ? bv : 0;
         }
         if (m.grid_fallbacks != nullptr) atomicAdd(m.grid_fallbacks, 1ull);
-        if (RT_SARSA_NO_FALLBACK) return bv >= 0 ? bv : 0;
     }
     return kNeedWalk;
 }
@@ -206,7 +157,6 @@ __device__ int sarsa_nearest_grid_gd(const SarsaMap& m, float4 G, int4 D, f3 pos
 // cls: normal class of the query (-1: no volume has its normal -- the KD walk keeps volume 0)
 __device__ int sarsa_nearest_grid(const SarsaMap& m, int cls, f3 pos, f3 nrm) {
     (void)nrm;
-    if (RT_SARSA_NO_KD) return 0;
     if (cls < 0) return 0;
     return sarsa_nearest_grid_gd(m, m.class_org[cls], m.class_dim[cls], pos);
 }
@@ -214,8 +164,6 @@ __device__ int sarsa_nearest_grid(const SarsaMap& m, int cls, f3 pos, f3 nrm) {
 // the same for a hit on surface tri: its class's grid descriptor in one per-surface record
 // (two independent loads instead of the class, then its descriptor)
 __device__ int sarsa_nearest_grid_tri(const SarsaMap& m, int tri, f3 pos, f3 nrm) {
-    if (RT_SARSA_NO_KD) return 0;
-    if (!RT_SARSA_TRIREC) return sarsa_nearest_grid(m, m.tri_class[tri], pos, nrm);
     const float4 G = m.tri_grid[2 * tri];
     const float4 Df = m.tri_grid[2 * tri + 1];
     const int4 D = make_int4(__float_as_int(Df.x), __float_as_int(Df.y), __float_as_int(Df.z), __float_as_int(Df.w));
@@ -223,9 +171,6 @@ __device__ int sarsa_nearest_grid_tri(const SarsaMap& m, int tri, f3 pos, f3 nrm
     return sarsa_nearest_grid_gd(m, G, D, pos);
 }
 
-#ifndef RT_SARSA_COOP_KD
-#define RT_SARSA_COOP_KD 1  // 0: a grid miss walks the k-d tree on its own lane (A/B builds)
-#endif
 constexpr int kKdFront = kKdStack * 32;  // frontier entries per buffer: two fill a wave's stack block
 
 // sarsa_nearest for ONE query (pos, nrm: wave-uniform values) walked by the whole wave.
@@ -321,7 +266,6 @@ __device__ int sarsa_nearest_wave(const SarsaMap& m, f3 pos, f3 nrm, int* blk, i
 // one after another (sarsa_nearest_wave), a lane whose query it cannot settle walks alone.
 // All lanes take part.
 __device__ void sarsa_resolve_walks(const SarsaMap& m, f3 pos, f3 nrm, int* rv, int* blk, int* st, int lane) {
-#if RT_SARSA_COOP_KD
     uint64_t need = __ballot(*rv == kNeedWalk);
     while (need != 0ull) {
         const int L = __builtin_ctzll(need);
@@ -332,10 +276,6 @@ __device__ void sarsa_resolve_walks(const SarsaMap& m, f3 pos, f3 nrm, int* rv, 
         const int v = sarsa_nearest_wave(m, q, qn, blk, lane, &ok);
         if (lane == L && ok) *rv = v;
     }
-#else
-    (void)blk;
-    (void)lane;
-#endif
     if (*rv == kNeedWalk) *rv = sarsa_nearest(m, pos, nrm, st);
 }
 

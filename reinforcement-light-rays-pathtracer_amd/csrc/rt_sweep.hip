@@ -35,12 +35,6 @@
 #include "rt_sarsa_search.hpp"
 
 namespace rt {
-int sarsa_sweep_view(rt_sarsa* sa, SarsaSweepView* out);
-int sarsa_n_volumes(const rt_sarsa* sa);
-int sarsa_device(const rt_sarsa* sa);
-}  // namespace rt
-
-namespace rt {
 namespace {
 
 static_assert(kSarsaSectors == kDqnActions && kSarsaSectors == kDqnGrid * kDqnGrid && kDqnGrid == kGridRes,

@@ -1285,21 +1285,10 @@ __device__ Hit closest_hit_bvh(const DeviceScene& s, f3 o, f3 d, float t_scale, 
     // grazing pairs (rt_bvh.cpp): the list of the ray's cube-map cell of directions, each
     // triangle tested for |d.N~| <= alpha B + beta and, with a window lambda, for its plane
     // within PA B + PB + (alpha B + beta) lambda of the origin (N units)
-#ifdef RT_BVH_TIMING_TRAVERSAL_ONLY
-    {  // timing-only build (wrong hits): the traversal alone
-        Hit hh;
-        hh.t = (RULE == 0) ? c.tmin : c.bt;
-        hh.tri = (RULE == 0) ? (c.nc ? c.ci[0] : -1) : c.bi;
-        return hh;
-    }
-#endif
     {
         const float cut = (RULE == 0) ? c.cut : c.bt;
         const float lam_cut = cut * t_scale * 1.0000002f;
         const bool bounded = lam_cut <= 3.0e38f;
-#ifdef RT_BVH_TIMING_SKIP_UNBOUNDED
-        if (!bounded) goto resolve;  // timing-only build (wrong hits)
-#endif
         const float B = om * 1.000001f;
         // the cube-map cell of d (the host lists hold for any direction of the cell, plus
         // the rounding of this choice)
@@ -1339,9 +1328,6 @@ __device__ Hit closest_hit_bvh(const DeviceScene& s, f3 o, f3 d, float t_scale, 
             }
         }
     }
-#ifdef RT_BVH_TIMING_SKIP_UNBOUNDED
-resolve:
-#endif
     Hit h;
     if (RULE == 1) {
         h.t = c.bt;

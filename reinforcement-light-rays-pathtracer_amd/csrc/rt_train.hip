@@ -45,15 +45,6 @@
 #include "../../include/rtmi.h"
 #include "rt_internal.hpp"
 
-namespace rt {
-int set_error(int code, const char* msg);
-int ctx_device(const rt_ctx* ctx);
-const DeviceScene& scene_device(const rt_scene* s);
-DeviceScene scene_launch_view(const rt_scene* s);
-void scene_host(const rt_scene* s, const float** tri, const float** normals, const float** albedo,
-                const float** emission, int* n_surf, int* n_light);
-}  // namespace rt
-
 namespace {
 
 using rt::f3;

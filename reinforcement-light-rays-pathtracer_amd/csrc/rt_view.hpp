@@ -1,5 +1,5 @@
 // rt_view.hpp — the frame of a camera-hit view: what k_sarsa_view, k_sarsa_irr (rt_views.hip) and
-// k_glyph_view (rt_glyph.hip) share.  One lane per (pixel, chunk) in k_sarsa_render's layout -- a
+// k_glyph_view (rt_glyph.hip) share.  One lane per (pixel, chunk) in k_render's layout -- a
 // wave covers 16 x 4 pixels at split 1 -- per trip the camera ray of sample a.sample_base + s and
 // its closest hit, the view's own colour of that hit (the kernel's body), and the fold of the
 // chunk sums in chunk order.  Every lane of a wave that has a pixel runs all per_chunk trips and

@@ -32,8 +32,8 @@ __global__ __launch_bounds__(256) void k_sarsa_nearest(const SarsaMap m, const f
     const f3 p = in ? make3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]) : make3(0.f, 0.f, 0.f);
     const f3 nr = in ? make3(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]) : make3(0.f, 0.f, 0.f);
     int v = -1;
-    if (m.use_grid) {  // as k_sarsa_render searches
-        if (in) v = RT_SARSA_NO_KD ? 0 : sarsa_nearest_grid(m, sarsa_class_of(m, nr), p, nr);
+    if (m.use_grid) {  // as k_sarsa_render_pq searches
+        if (in) v = sarsa_nearest_grid(m, sarsa_class_of(m, nr), p, nr);
         sarsa_resolve_walks(m, p, nr, &v, kd_stack + ((int)threadIdx.x >> 6) * (kKdStack * 64), kd_stack_of(kd_stack),
                             threadIdx.x & 63);
     } else if (in) {
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void k_sarsa_nearest(const SarsaMap m, const f
 
 // The radiance-map view (the reference's PATH_TRACING_METHOD 2: GPU/path_tracing/
 // voronoi_trace.cu:6-41, RadianceMap::get_voronoi_colour, radiance_map.cu:218-225): per
-// sample the camera ray of k_sarsa_render (sample index a.sample_base + s), its closest hit,
+// sample the camera ray of k_sarsa_render_pq (sample index a.sample_base + s), its closest hit,
 // the nearest volume of a surface hit as the render searches it, and that volume's entry of
 // the colour table; (1, 1, 1) for a light or a miss.  The lane layout, the cull, the trips and
 // the chunk fold are rt_view.hpp's; the k-d walks of the grid's undecided queries are shared by

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Which kernels of two gfx950 assembly listings of the same source (make asm) differ.
 
-    python tools/asm_kernel_diff.py before/rt_kernels.s after/rt_kernels.s
+    python tools/asm_kernel_diff.py [--rename OLD=NEW ...] before/rt_kernels.s after/rt_kernels.s
 
 Each kernel's instructions are compared with the label numbers (.LBBn_m) and the
 __hip_cuid_ symbol normalised, so that a change to one kernel does not show in the others.
 Prints one line per kernel that differs or exists on one side only, with its static
 instruction counts by unit (VALU, SALU, LDS, VMEM/SMEM, branches), then the number of
-identical kernels.
+identical kernels.  --rename OLD=NEW (repeatable) replaces the substring OLD of the mangled
+names of the "before" listing by NEW, for kernels whose template or function parameters changed.
 """
 import re
 import sys
@@ -54,7 +55,13 @@ def counts(body):
 
 
 def main():
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    args, renames = sys.argv[1:], []
+    while args and args[0] == "--rename":
+        renames.append(args[1].split("=", 1))
+        args = args[2:]
+    a, b = kernels(args[0]), kernels(args[1])
+    for old, new in renames:
+        a = {k.replace(old, new): v for k, v in a.items()}
     same = 0
     for k in sorted(set(a) | set(b)):
         if k not in a or k not in b:

@@ -79,8 +79,6 @@ void scene_host(const rt_scene*, const float** tri, const float** normals, const
 }
 int ctx_blocks(rt_ctx*, const int32_t*, int, int, int, int, const BlockDesc**, int*) { return RT_E_UNSUPPORTED; }
 RenderLaunch render_launch(const rt_scene*, const rt_camera*, const rt_params*) { return RenderLaunch(); }
-int scene_ensure_ctab(const rt_scene*, int, float, bool) { return RT_OK; }
-bool ctab_wanted(const rt_scene*, const rt_camera*, const rt_params*, int) { return false; }
 bool sarsa_prof_compiled() { return false; }
 hipError_t launch_sarsa_render(const RenderLaunch&, const SarsaMap&, hipStream_t) { return hipErrorNotSupported; }
 hipError_t launch_sarsa_apply(const SarsaMap&, hipStream_t) { return hipErrorNotSupported; }
