@@ -307,6 +307,65 @@ int rt_render_dqn_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn*
                                int n_tiles, int tile_size, float* d_out, uint64_t* d_casts,
                                void* stream);
 
+/* Direction sampling of rt_render_dqn / rt_render_dqn_tiles_device, a property of the network
+ * handle (as rt_dqn_set_mlp; rt_sarsa_set_sampling is the map's):
+ * RT_DQN_SAMPLE_CDF (default) importance_sample_direction, rt_dqn_sample's sampler on the bf16 Q;
+ * RT_DQN_SAMPLE_MAX the reference's sample_max_direction (nn_rendering_helpers.cu:491-553), the
+ *   sampler of the thesis's fig:1_spp_max_dir (4_critical_evaluation.tex): every bounce leaves
+ *   through the cell of highest estimated radiance.  For a ray at bounce b >= 1 on surface `tri`
+ *   (shading frame N, T, B) at position pos, with Q[0..143] the fp32 forward at pos,
+ *   rt_dqn_forward's value bit for bit (the view's rule; not the bf16 copy the CDF renderer keeps):
+ *     action   max_idx = 0, max_q = 0.0f; for k = 0..143: if (Q[k] > max_q) take k (:513-522).
+ *              The first cell of the largest positive Q; a row with nothing above zero, or all
+ *              NaN, gives 0; a NaN never wins, +inf wins, -0.0f does not beat 0.0f.  The scan
+ *              runs on raw Q, not Q x cos, as the reference's.  There is always an action, so
+ *              there is always a cast.
+ *     dir      what the CDF sampler gives for that cell: Philox counter (pix, sample, 1 + b, 73)
+ *              under the params' seed, words o; gx = action / 12, gy = action % 12;
+ *              dir = grid_direction(gx + u01(o[0]), gy + u01(o[1]), N, T, B, pos).
+ *     tp       c = dot(N, dir), pdf = RHO * 2.0f, tp = (tp * c) / pdf per channel, the multiply
+ *              and the divide each rounded once.  The constant pdf is the reference's (:547): it
+ *              is not the density the direction was drawn with, so the estimator is biased on
+ *              purpose -- the mode shows where the network points, it does not converge to
+ *              the reference image.
+ *   The reference also draws rv = curand_uniform (:508) and never uses it; with a counter-based
+ *   generator an unused draw consumes nothing, so none is made.
+ *   The frame is otherwise rt_render_dqn's: the camera pass, the bounce loop with its early
+ *   stop, the accumulation.  A pixel does not depend on the tile list,
+ *   RTMI_DQN_RAYS_IN_FLIGHT, the forward kernel (rt_dqn_set_mlp), the cast route, or the route
+ *   of the action: inside the streaming forward's epilogue on its LDS tile (4 B per ray leave
+ *   the kernel), or (RT_DQN_MLP_STATIONARY networks, RTMI_DQN_MAX_FUSED=0 in the environment,
+ *   read per call) k_dqn_argmax on the fp32 Q the forward wrote.
+ * Another mode, or a NULL handle: RT_E_INVALID. */
+#define RT_DQN_SAMPLE_CDF 0
+#define RT_DQN_SAMPLE_MAX 1
+int rt_dqn_set_sampling(rt_dqn* dqn, int mode);
+int rt_dqn_get_sampling(const rt_dqn* dqn, int* mode);
+/* RT_DQN_SAMPLE_MAX's sampler alone for n rays given their Q values (host arrays, rt_dqn_sample's
+ * arguments and checks): action, direction and throughput as defined above; q is read and not
+ * modified; the action comes from k_dqn_argmax. */
+int rt_dqn_sample_max(rt_ctx* ctx, const rt_scene* scene, uint64_t seed, const float* q, const float* loc,
+                      const int32_t* tri, const uint32_t* pix, int n, int sample, int bounce, float* tp,
+                      float* dir_out, int32_t* action);
+/* Statistics of the last rt_render_dqn or rt_render_dqn_tiles_device on this context, in either
+ * sampling mode -- how the thesis reads fig:1_spp_max_dir: paths = the call's valid rays
+ * (its pixels x spp); zero_paths = those whose final throughput, the value added to the pixel,
+ * has every channel < 1e-4f (THROUGHPUT_THRESHOLD of sum_zero_contribution_light_paths,
+ * nn_rendering_helpers.cu:555-568; a NaN channel is not below it, so such a ray is not
+ * counted).  The sum of path lengths is the cast count the render already returns (a path's
+ * length is its ray casts), so there is no third counter.  A blocking copy: after the
+ * stream-ordered entry synchronise the stream first.  Either pointer may be NULL.  Before any
+ * counted render on the context: RT_E_INVALID.  A tile render's sums cover the call's tiles (add
+ * them over ranks).  Counted by one small kernel per pass that reads the throughputs; it
+ * changes no pixel and no cast count.
+ * rt_dqn_enable_stats(ctx, on): the kernel is launched only by renders after on != 0 (default
+ * off; a property of the context).  Measured on BASELINE config 4's frame the counting cost more
+ * than the run-to-run spread of the frame itself, so a frame that does not
+ * ask for the statistics runs exactly the launches it ran before they existed; after a render
+ * with the statistics off rt_dqn_render_stats returns RT_E_INVALID. */
+int rt_dqn_enable_stats(rt_ctx* ctx, int on);
+int rt_dqn_render_stats(const rt_ctx* ctx, uint64_t* paths, uint64_t* zero_paths);
+
 /* The Q-network view: the network's irradiance estimate at every camera hit, the network's
  * side of the thesis's comparison (Images/neural_q_visualisation.png beside
  * expected_sarsa_visualisation.png, 4_critical_evaluation.tex); it replaces no reference

@@ -21,6 +21,10 @@
 //    one Philox draw per two cells), CDF walk, jittered direction, throughput,
 //    then the closest hit of the new ray; surviving rays are appended to the
 //    next active list (stream compaction with one atomic per wave).
+//  * RT_DQN_SAMPLE_MAX (sample_max_direction, nn_rendering_helpers.cu:491-553): the first cell
+//    of the largest positive Q instead of the CDF walk.  k_dqn_mlp<.., AMAX> reduces its staged
+//    fp32 tile to one int32 per ray (or k_dqn_argmax scans fp32 Q written out), and
+//    k_dqn_bounce_max reads that action, draws one Philox block and casts (end of this file).
 //  * rays that end are dropped from the list, so later bounces (mean path
 //    length ~24 in the thesis renders) only pay for live rays.
 
@@ -78,6 +82,8 @@ constexpr int kSampBlocks = 4;
 constexpr int kSampCells = kDqnActions / kSampBlocks;  // 36 = 9 Philox draws
 static_assert(kTileM * kStageStride * 4 <= kTileM * kStrideA * 2, "Q staging tile exceeds bufA");
 constexpr float kGridRho = 1.0f / ((float)kDqnGrid * (float)kDqnGrid);  // GRID_RHO
+constexpr float kThroughputThreshold = 0.0001f;  // THROUGHPUT_THRESHOLD (constants/monte_carlo_settings.h:11)
+constexpr int kAmaxRays = 256 / kSampBlocks;  // rays per k_dqn_argmax workgroup
 
 __device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
 #pragma unroll
@@ -385,13 +391,67 @@ __device__ __forceinline__ void view_merge(const float* bsum, const float* best,
     *action = a;
 }
 
+// ---------------------------------------------------------------------------
+// The max-direction sampler's action (RT_DQN_SAMPLE_MAX, rtmi.h; the reference's
+// sample_max_direction, nn_rendering_helpers.cu:513-522): the sequential scan
+//   max_idx = 0, max_q = 0; for k = 0..143: if (Q_k > max_q) { max_idx = k; max_q = Q_k; }
+// on raw Q, in the view's blocking -- one thread per (ray, block w of kSampCells cells):
+// amax_block runs the scan over the block's cells from (0, 0.0f), amax_merge the same scan over
+// the kSampBlocks block results in block order.  ld(k) returns Q_k.
+//
+// Equal to the sequential scan.  `>` is false for a NaN on either side and max_q starts at 0
+// and is only replaced by a larger value, so max_q is never NaN and never decreases: after any
+// prefix it is M = max(0, the prefix's non-NaN values), and max_idx is the first k with
+// Q_k = M if M > 0 (a later equal value does not replace it), else 0.  So the scan's result is
+// a function of the cells' values alone: the first cell of the largest positive Q, or 0.
+// Block w gives best_w = max(0, its non-NaN cells) and act_w = its first cell of that value
+// (when best_w > 0).  The merge keeps M' = max(0, best_0 .. best_w) and replaces only when
+// best_w > M', i.e. at the first block whose best equals the global M > 0: that block holds
+// the first cell with Q_k = M (no earlier block reaches M), and act_w is that cell.  If no
+// cell is positive every best_w is 0, nothing replaces and the action is 0, as the scan's.
+// -0.0f > 0.0f is false, +inf > x is true for every finite x, so both behave as in the scan.
+// ---------------------------------------------------------------------------
+template <class LoadQ>
+__device__ __forceinline__ void amax_block(int w, LoadQ ld, float* best, int* act) {
+    float bq = 0.0f;
+    int ba = 0;
+#pragma unroll
+    for (int j = 0; j < kSampCells; ++j) {
+        const int k = w * kSampCells + j;
+        const float v = ld(k);
+        if (v > bq) {
+            bq = v;
+            ba = k;
+        }
+    }
+    *best = bq;
+    *act = ba;
+}
+
+// best / act: the ray's kSampBlocks block results, `stride` apart
+__device__ __forceinline__ int amax_merge(const float* best, const int* act, int stride) {
+    float mq = 0.0f;
+    int a = 0;
+#pragma unroll
+    for (int w = 0; w < kSampBlocks; ++w) {
+        if (best[w * stride] > mq) {
+            mq = best[w * stride];
+            a = act[w * stride];
+        }
+    }
+    return a;
+}
+
 // One workgroup = MT*16 rays (LDS: MT = 6 in place -> 66 KB, two workgroups per CU).
+// AMAX: as VIEW, the reduction being the max-direction sampler's action (amax_block /
+// amax_merge): one int32 per list row, reinterpret_cast<int32_t*>(q)[i] = action -- 4 B
+// instead of 576 B per ray; ldq is unused.
 // VIEW: instead of writing Q out, the workgroup runs the Q-network view's reduction
 // (view_block / view_merge) on its staged fp32 tile and writes the ray's S and action,
 // q[i] = S, q[ldq + i] = action bits (i the list row): 8 B instead of 576 B per ray.  The
 // block results live in bufA's slack behind the stage; consecutive lanes read consecutive
 // rows at the odd kStageStride, so a 32-lane group's ds_read_b32 hits 32 distinct banks.
-template <int MT, bool QB = false, bool VIEW = false>
+template <int MT, bool QB = false, bool VIEW = false, bool AMAX = false>
 #ifndef RT_MLP_MIN_WAVES
 #define RT_MLP_MIN_WAVES 2  // waves per SIMD: the workgroups per CU that its LDS admits (3: MT = 4 in place)
 #endif
@@ -461,6 +521,25 @@ __global__ __launch_bounds__(kMlpThreads, RT_MLP_MIN_WAVES) void k_dqn_mlp(const
             q[row0 + r] = S;
             q[(size_t)ldq + row0 + r] = __int_as_float(action);
         }
+        return;
+    }
+    if constexpr (AMAX) {
+        static_assert(!QB && !VIEW, "the argmax reduces the fp32 stage");
+        // [block][row] behind the stage (no LDS of its own)
+        static_assert(kRows * kStageStride * 4 + 2 * kSampBlocks * kRows * 4 <= kRows * kStrideA * 2,
+                      "the argmax's block results fit bufA's slack");
+        const float* const stage = reinterpret_cast<const float*>(bufA);
+        float* const best = reinterpret_cast<float*>(bufA) + kRows * kStageStride;
+        int* const bact = reinterpret_cast<int*>(best + kSampBlocks * kRows);
+        for (int u = threadIdx.x; u < kSampBlocks * kRows; u += kMlpThreads) {
+            const int w = u / kRows, r = u - w * kRows;  // 32-lane groups share w (kRows = 96)
+            if (r >= rows_valid) continue;
+            const float* const srow = stage + r * kStageStride;
+            amax_block(w, [&](int k) { return srow[k]; }, best + u, bact + u);
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < rows_valid)
+            reinterpret_cast<int32_t*>(q)[row0 + threadIdx.x] = amax_merge(best + threadIdx.x, bact + threadIdx.x, kRows);
         return;
     }
     // Q tile [kRows][144] from LDS (odd row stride: conflict-free column reads) in
@@ -969,7 +1048,6 @@ __global__ __launch_bounds__(256) void k_dqn_sample_only(const DeviceScene s, fl
 // kNqEvRestart + b and kNqEvRestartPos + b a restart's surface and position.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kNqEvGreedy = 0x1000u, kNqEvRestart = 0x2000u, kNqEvRestartPos = 0x3000u;
-constexpr float kThroughputThreshold = 0.0001f;  // THROUGHPUT_THRESHOLD (constants/monte_carlo_settings.h:11)
 
 // initialise_ray (neural_q_pathtracer.cu:604-643)
 __global__ __launch_bounds__(256) void k_nq_init(const DqnLaunch a, const NqRays r, int sample) {
@@ -1361,6 +1439,225 @@ hipError_t launch_nq_end_sample(const DqnLaunch& a, const NqRays& r, hipStream_t
 }
 hipError_t launch_nq_image(const DqnLaunch& a, const NqRays& r, float* out, int spp, hipStream_t stream) {
     hipLaunchKernelGGL(k_nq_image, dim3(nq_blocks(r)), dim3(256), 0, stream, a, r, out, spp);
+    return hipGetLastError();
+}
+
+// ===========================================================================
+// The max-direction render mode and the frame statistics (rtmi.h rt_dqn_set_sampling,
+// rt_dqn_render_stats).  Kept behind everything else in this file: the kernels above keep
+// their place in the code object.
+// ===========================================================================
+namespace {
+
+// ---------------------------------------------------------------------------
+// RT_DQN_SAMPLE_MAX (rtmi.h; sample_max_direction, nn_rendering_helpers.cu:491-553): the
+// jittered direction of cell `action` -- the CDF sampler's for that cell (sample_finish: Philox
+// counter 1 + 72 of the ray's (pixel, sample, 1 + bounce) block) -- and the throughput update
+// (tp * cos) / (RHO * 2), the reference's constant pdf.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ f3 sample_max_dir(int action, f3 N, f3 T, f3 B, f3 pos, uint32_t pix, uint32_t smp,
+                                             uint32_t ev, uint32_t k0, uint32_t k1, f3* tp) {
+    const PhiloxShared ph = philox_shared(pix, smp, ev, k0, k1);
+    uint32_t o[4];
+    philox_from(ph, 1u + kDqnActions / 2, o);
+    const int gxi = action / kDqnGrid;
+    const int gyi = action - gxi * kDqnGrid;
+    const f3 dir = grid_direction((float)gxi + u01(o[0]), (float)gyi + u01(o[1]), N, T, B, pos);
+    const float c = dot(N, dir);
+    const float pdf = kRho * 2.0f;
+    tp->x = (tp->x * c) / pdf;
+    tp->y = (tp->y * c) / pdf;
+    tp->z = (tp->z * c) / pdf;
+    return dir;
+}
+
+// The written-out route of the action: one thread per (row, block of 36 cells) on fp32 Q,
+// Q_k of row i at q[i * row_stride + k * cell_stride] (the renderer's action-major buffer:
+// 1, ldq; a [row][144] buffer: 144, 1); action[i] for the rows i < min(*count, max_rows)
+// (count NULL: max_rows)
+__global__ __launch_bounds__(256) void k_dqn_argmax(const float* __restrict__ q, size_t row_stride,
+                                                    size_t cell_stride, const int32_t* __restrict__ count,
+                                                    int max_rows, int32_t* __restrict__ action) {
+    __shared__ float s_best[kSampBlocks * kAmaxRays];
+    __shared__ int s_act[kSampBlocks * kAmaxRays];
+    const int n_rows = (count != nullptr) ? min(*count, max_rows) : max_rows;
+    if ((int)(blockIdx.x * kAmaxRays) >= n_rows) return;  // uniform
+    const int r = threadIdx.x & (kAmaxRays - 1), w = threadIdx.x / kAmaxRays;
+    const int i = blockIdx.x * kAmaxRays + r;
+    if (i < n_rows) {
+        const float* const qi = q + (size_t)i * row_stride;
+        amax_block(w, [&](int k) { return qi[(size_t)k * cell_stride]; }, s_best + threadIdx.x, s_act + threadIdx.x);
+    }
+    __syncthreads();
+    if (w == 0 && i < n_rows) action[i] = amax_merge(s_best + r, s_act + r, kAmaxRays);
+}
+
+// one bounce >= 1 for the rays of list[cur] in RT_DQN_SAMPLE_MAX: k_dqn_bounce with the sampler
+// replaced.  act[i]: the action of list row i (k_dqn_mlp<.., AMAX> or k_dqn_argmax); Q is not
+// read, and every listed ray casts.
+template <int MF, bool CT = false>
+__global__ __launch_bounds__(256, CT ? RT_DQN_CT_WAVES : (MF > 0 ? RT_MF_DQN_WAVES : 1)) void k_dqn_bounce_max(
+    const DqnLaunch a, const int32_t* __restrict__ act, int bounce) {
+    __shared__ float s_mfw[dqn_lds_floats(MF)];
+    const int cur = (bounce - 1) & 1, nxt = bounce & 1;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int n_act = a.rays.count[cur];
+    if ((int)(blockIdx.x * 256) >= n_act) return;  // uniform
+    bool keep = false;
+    unsigned casts = 0;
+    int rid = 0;
+    const bool want = i < n_act;
+    f3 pos = make3(0.0f, 0.0f, 0.0f), dir = make3(0.0f, 0.0f, 1.0f), tp = make3(0.0f, 0.0f, 0.0f);
+    f3 loc = pos;
+    int ntri = 0;
+    if (want) {
+        rid = a.rays.list[cur][i];
+        const int slot = rid / a.rays.n_pix;
+        const int sample = a.rays.s0 + slot;
+        const uint32_t pixid = a.rays.pix[rid - slot * a.rays.n_pix];
+        const int tri = a.rays.tri[rid];
+        int action = act[i];
+        action = action < 0 ? 0 : (action > kDqnActions - 1 ? kDqnActions - 1 : action);  // (always in range)
+        pos = ld3(a.rays.loc, rid);
+        tp = ld3(a.rays.tp, rid);
+        const float4 N4 = a.scene.shade[tri * kShadeF4 + 0];
+        const float4 T4 = a.scene.shade[tri * kShadeF4 + 1];
+        const float4 B4 = a.scene.shade[tri * kShadeF4 + 2];
+        dir = sample_max_dir(action, make3(N4.x, N4.y, N4.z), make3(T4.x, T4.y, T4.z), make3(B4.x, B4.y, B4.z), pos,
+                             pixid, (uint32_t)sample, 1u + (uint32_t)bounce, a.seed_lo, a.seed_hi, &tp);
+        casts = 1;
+        loc = pos;
+        ntri = tri;
+    }
+    keep = dqn_trace<MF, true, CT>(a, pos, dir, want, dqn_lane_ws<MF>(s_mfw), &loc, &ntri, &tp, want ? ntri : -1);
+    if (want) {
+        if (keep) {
+            st3(a.rays.loc, rid, loc);
+            a.rays.tri[rid] = ntri;
+        }
+        st3(a.rays.tp, rid, tp);
+    }
+    list_append(keep, rid, a.rays.list[nxt], a.rays.count + nxt);
+    const unsigned tot = wave_sum_u(casts);
+    if ((threadIdx.x & 63) == 0 && tot) atomicAdd(a.rays.casts, (unsigned long long)tot);
+}
+
+// rt_dqn_sample_max: the sampler alone, rows i < n, action[i] from k_dqn_argmax
+__global__ __launch_bounds__(256) void k_dqn_sample_max_only(const DeviceScene s, const int32_t* action,
+                                                             const float* loc, const int32_t* tri,
+                                                             const uint32_t* pix, int n, int sample, int bounce,
+                                                             uint32_t k0, uint32_t k1, float* tp, float* dir_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int t = tri[i];
+    const float4 N4 = s.shade[t * kShadeF4 + 0];
+    const float4 T4 = s.shade[t * kShadeF4 + 1];
+    const float4 B4 = s.shade[t * kShadeF4 + 2];
+    f3 tpv = ld3(tp, i);
+    const f3 d = sample_max_dir(action[i], make3(N4.x, N4.y, N4.z), make3(T4.x, T4.y, T4.z), make3(B4.x, B4.y, B4.z),
+                                ld3(loc, i), pix[i], (uint32_t)sample, 1u + (uint32_t)bounce, k0, k1, &tpv);
+    st3(tp, i, tpv);
+    st3(dir_out, i, d);
+}
+
+// rt_dqn_render_stats: the pass's valid rays whose final throughput -- the value
+// k_dqn_accumulate adds next -- has every channel below THROUGHPUT_THRESHOLD
+// (sum_zero_contribution_light_paths, nn_rendering_helpers.cu:555-568; a NaN channel is not
+// below it).  A grid of at most kZeroPathBlocks workgroups strides over the rays; a wave sum and
+// one atomic per wave at the end.  (One wave per 64 rays -- 65,536 atomics on one address for a
+// 4 M-ray pass, most waves holding a dark path -- took 0.7 ms per pass on the archway frame:
+// same-address atomics serialise in L2.)  Reads only.
+constexpr int kZeroPathBlocks = 1024;
+__global__ __launch_bounds__(256) void k_dqn_zero_paths(const DqnLaunch a, unsigned long long* __restrict__ zero_paths) {
+    unsigned z = 0;
+    for (int rid = blockIdx.x * 256 + threadIdx.x; rid < a.rays.n; rid += gridDim.x * 256) {
+        const int slot = rid / a.rays.n_pix;
+        int px, py;
+        if (ray_pixel(a, rid - slot * a.rays.n_pix, &px, &py)) {
+            const f3 tp = ld3(a.rays.tp, rid);
+            z += (tp.x < kThroughputThreshold && tp.y < kThroughputThreshold && tp.z < kThroughputThreshold) ? 1u : 0u;
+        }
+    }
+    const unsigned sz = wave_sum_u(z);
+    if ((threadIdx.x & 63) == 0 && sz) atomicAdd(zero_paths, (unsigned long long)sz);
+}
+
+}  // namespace
+
+// the cast route of a bounce launch, as launch_dqn_bounce chooses it: the candidate table
+// (ct), else dqn_mf's filter blocks / BVH / scan
+static bool dqn_bounce_ct(const DqnLaunch& a, int mf) {
+    const CtabDev& T = a.scene.ctab[1];
+    return mf > 0 && T.masks != nullptr && T.bins == kCtabBins && T.graze_n == kCtabGraze && a.t_scale >= T.ts_min &&
+           T.words <= mf;
+}
+
+// RT_DQN_SAMPLE_MAX's bounce: the forward over list[cur] with the action of every row into
+// rays.dir (free in this driver) as int32 -- fused: in the streaming forward's epilogue
+// (k_dqn_mlp<.., AMAX>); else the fp32 action-major Q written out and k_dqn_argmax on it -- then
+// k_dqn_bounce_max.  The reduction is timed as the view's: inside KT_DQN_MLP, or KT_DQN_BOUNCE.
+hipError_t launch_dqn_bounce_max(const DqnLaunch& a, int bounce, bool fused, hipStream_t stream) {
+    const int cur = (bounce - 1) & 1;
+    if (a.rays.n <= 0) return hipSuccess;
+    if (a.net.N[3] != kDqnActions) return hipErrorInvalidValue;
+    int32_t* const act = reinterpret_cast<int32_t*>(a.rays.dir);
+    if (fused) {
+        if (!dqn_view_can_fuse(a.net)) return hipErrorInvalidValue;
+        KernelTimer kt(KT_DQN_MLP, stream);
+        const int blocks = (a.rays.n + kTileM - 1) / kTileM;
+        hipLaunchKernelGGL((k_dqn_mlp<RT_MLP_MT, false, false, true>), dim3((unsigned)blocks), dim3(kMlpThreads), 0,
+                           stream, a.net, a.rays.loc, a.rays.list[cur], a.rays.count + cur, a.rays.n, a.rays.dir, 0);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else {
+        const hipError_t e = launch_dqn_mlp(a.net, a.rays.loc, a.rays.list[cur], a.rays.count + cur, a.rays.n,
+                                            a.rays.q, a.rays.ldq, stream);
+        if (e != hipSuccess) return e;
+    }
+    KernelTimer kt(KT_DQN_BOUNCE, stream);
+    if (!fused) {
+        hipLaunchKernelGGL(k_dqn_argmax, dim3((unsigned)((a.rays.n + kAmaxRays - 1) / kAmaxRays)), dim3(256), 0, stream,
+                           a.rays.q, (size_t)1, (size_t)a.rays.ldq, a.rays.count + cur, a.rays.n, act);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    const dim3 grid(ray_blocks(a));
+    const int mf = dqn_mf(a);
+    if (dqn_bounce_ct(a, mf)) {
+        if (mf == 1)
+            hipLaunchKernelGGL((k_dqn_bounce_max<1, true>), grid, dim3(256), 0, stream, a, act, bounce);
+        else
+            hipLaunchKernelGGL((k_dqn_bounce_max<4, true>), grid, dim3(256), 0, stream, a, act, bounce);
+        return hipGetLastError();
+    }
+    switch (mf) {
+        case 1: hipLaunchKernelGGL((k_dqn_bounce_max<1>), grid, dim3(256), 0, stream, a, act, bounce); break;
+        case 4: hipLaunchKernelGGL((k_dqn_bounce_max<4>), grid, dim3(256), 0, stream, a, act, bounce); break;
+        case -1: hipLaunchKernelGGL((k_dqn_bounce_max<-1>), grid, dim3(256), 0, stream, a, act, bounce); break;
+        default: hipLaunchKernelGGL((k_dqn_bounce_max<0>), grid, dim3(256), 0, stream, a, act, bounce); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_dqn_zero_paths(const DqnLaunch& a, unsigned long long* zero_paths, hipStream_t stream) {
+    if (a.rays.n <= 0) return hipSuccess;
+    const unsigned blocks = ray_blocks(a) < (unsigned)kZeroPathBlocks ? ray_blocks(a) : (unsigned)kZeroPathBlocks;
+    hipLaunchKernelGGL(k_dqn_zero_paths, dim3(blocks), dim3(256), 0, stream, a,
+                       zero_paths);
+    return hipGetLastError();
+}
+
+hipError_t launch_dqn_sample_max_only(const DeviceScene& s, const float* q, const float* loc, const int32_t* tri,
+                                      const uint32_t* pix, int n, int sample, int bounce, uint32_t seed_lo,
+                                      uint32_t seed_hi, float* tp, float* dir_out, int32_t* action,
+                                      hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_dqn_argmax, dim3((unsigned)((n + kAmaxRays - 1) / kAmaxRays)), dim3(256), 0, stream, q,
+                       (size_t)kDqnActions, (size_t)1, (const int32_t*)nullptr, n, action);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_dqn_sample_max_only, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, s, action, loc,
+                       tri, pix, n, sample, bounce, seed_lo, seed_hi, tp, dir_out);
     return hipGetLastError();
 }
 

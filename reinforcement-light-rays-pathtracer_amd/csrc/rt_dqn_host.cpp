@@ -45,6 +45,7 @@ struct rt_dqn {
     int device = 0;
     int n_in = 0, n_out = 0, h[3] = {0, 0, 0};
     rt::DqnNet net;
+    int sampling = RT_DQN_SAMPLE_CDF;  // rt_dqn_set_sampling
     std::vector<void*> allocs;
     ~rt_dqn() {
         (void)hipSetDevice(device);
@@ -253,6 +254,19 @@ int rt_dqn_set_mlp(rt_dqn* dqn, int mode) {
 
 int rt_dqn_mlp_rows(void) { return rt::dqn_mlp_tile_rows(); }
 
+int rt_dqn_set_sampling(rt_dqn* dqn, int mode) {
+    if (!dqn) return err(RT_E_INVALID, "NULL argument");
+    if (mode != RT_DQN_SAMPLE_CDF && mode != RT_DQN_SAMPLE_MAX) return err(RT_E_INVALID, "bad sampling mode");
+    dqn->sampling = mode;
+    return RT_OK;
+}
+
+int rt_dqn_get_sampling(const rt_dqn* dqn, int* mode) {
+    if (!dqn || !mode) return err(RT_E_INVALID, "NULL argument");
+    *mode = dqn->sampling;
+    return RT_OK;
+}
+
 int rt_dqn_forward(rt_ctx* ctx, const rt_dqn* dqn, const float* loc, int n, float* q) {
     if (!ctx || !dqn || (n > 0 && (!loc || !q))) return err(RT_E_INVALID, "NULL argument");
     if (n < 0) return err(RT_E_INVALID, "n < 0");
@@ -346,6 +360,44 @@ int rt_dqn_sample(rt_ctx* ctx, const rt_scene* scene, uint64_t seed, float* q, c
     return RT_OK;
 }
 
+int rt_dqn_sample_max(rt_ctx* ctx, const rt_scene* scene, uint64_t seed, const float* q, const float* loc,
+                      const int32_t* tri, const uint32_t* pix, int n, int sample, int bounce, float* tp,
+                      float* dir_out, int32_t* action) {
+    if (!ctx || !scene || (n > 0 && (!q || !loc || !tri || !pix || !tp || !dir_out || !action)))
+        return err(RT_E_INVALID, "NULL argument");
+    if (n <= 0) return n == 0 ? RT_OK : err(RT_E_INVALID, "n < 0");
+    const rt::DeviceScene& s = rt::scene_device(scene);
+    for (int i = 0; i < n; ++i)
+        if (tri[i] < 0 || tri[i] >= s.n_surf) return err(RT_E_INVALID, "tri must index a surface");
+    RT_HIPE(hipSetDevice(rt::ctx_device(ctx)));
+    const size_t nq = sizeof(float) * rt::kDqnActions * (size_t)n, n3 = sizeof(float) * 3 * (size_t)n;
+    float *d_q = nullptr, *d_loc = nullptr, *d_tp = nullptr, *d_dir = nullptr;
+    int32_t *d_tri = nullptr, *d_act = nullptr;
+    uint32_t* d_pix = nullptr;
+    hipError_t e = hipMalloc(&d_q, nq);
+    if (e == hipSuccess) e = hipMalloc(&d_loc, n3);
+    if (e == hipSuccess) e = hipMalloc(&d_tp, n3);
+    if (e == hipSuccess) e = hipMalloc(&d_dir, n3);
+    if (e == hipSuccess) e = hipMalloc(&d_tri, sizeof(int32_t) * n);
+    if (e == hipSuccess) e = hipMalloc(&d_act, sizeof(int32_t) * n);
+    if (e == hipSuccess) e = hipMalloc(&d_pix, sizeof(uint32_t) * n);
+    if (e == hipSuccess) e = hipMemcpy(d_q, q, nq, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_loc, loc, n3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_tp, tp, n3, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_tri, tri, sizeof(int32_t) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_pix, pix, sizeof(uint32_t) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = rt::launch_dqn_sample_max_only(s, d_q, d_loc, d_tri, d_pix, n, sample, bounce, (uint32_t)seed,
+                                           (uint32_t)(seed >> 32), d_tp, d_dir, d_act, 0);
+    if (e == hipSuccess) e = hipMemcpy(tp, d_tp, n3, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(dir_out, d_dir, n3, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(action, d_act, sizeof(int32_t) * n, hipMemcpyDeviceToHost);
+    for (void* p : {(void*)d_q, (void*)d_loc, (void*)d_tp, (void*)d_dir, (void*)d_tri, (void*)d_act, (void*)d_pix})
+        (void)hipFree(p);
+    if (e != hipSuccess) return err(RT_E_HIP, std::string("rt_dqn_sample_max: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -366,6 +418,12 @@ struct Workspace {
     std::vector<float> surf_host;
     float2* surf = nullptr;
     int surf_cap = 0;
+    // rt_dqn_render_stats: the last render's zero-contribution paths (device, next to r.casts;
+    // kept across ensure) and its valid rays
+    unsigned long long* zero_paths = nullptr;
+    uint64_t paths = 0;
+    bool stats_on = false;   // rt_dqn_enable_stats
+    bool rendered = false;   // the last render counted
     void release() {
         for (void* p : allocs) (void)hipFree(p);
         allocs.clear();
@@ -374,6 +432,7 @@ struct Workspace {
     ~Workspace() {
         release();
         if (surf) (void)hipFree(surf);
+        if (zero_paths) (void)hipFree(zero_paths);
     }
     int ensure(int n) {
         if (n <= cap) {
@@ -405,13 +464,23 @@ struct Workspace {
 };
 
 Workspace* g_ws_for(rt_ctx* ctx);
+Workspace* g_ws_find(const rt_ctx* ctx);
 
 constexpr int kRaysInFlight = 1 << 22;  // DQN wavefront size (q: 2.4 GB at 4 M rays)
 
 int run_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam, const rt_params* p,
             const rt::BlockDesc* d_blocks, int n_blocks, int clip_x1, int clip_y1, int out_pitch, float* d_out,
-            uint64_t* d_casts, hipStream_t stream) {
+            uint64_t* d_casts, uint64_t valid_pixels, hipStream_t stream) {
     Workspace* ws = g_ws_for(ctx);
+    // the statistics kernel runs only when asked for (rt_dqn_enable_stats; RTMI_DQN_STATS in the
+    // environment, read per call, overrides it: the A/B of DESIGN.md section 7)
+    bool stats = ws->stats_on;
+    if (const char* env = getenv("RTMI_DQN_STATS")) stats = atoi(env) != 0;
+    ws->rendered = false;
+    if (stats) {
+        if (!ws->zero_paths) RT_HIPE(hipMalloc((void**)&ws->zero_paths, sizeof(unsigned long long)));
+        RT_HIPE(hipMemsetAsync(ws->zero_paths, 0, sizeof(unsigned long long), stream));
+    }
     // samples in flight: about kRaysInFlight rays per pass (all of spp for small frames)
     const int n_pix = n_blocks * 256;
     int rays_in_flight = kRaysInFlight;
@@ -451,6 +520,13 @@ int run_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_came
     a.out_pitch = out_pitch;
     a.out = d_out;
     a.use_filter = rt::filter_usable(a.scene, a.cam_x, a.cam_y, a.cam_z, a.t_scale);
+    // RT_DQN_SAMPLE_MAX: the action in the streaming forward's epilogue, unless asked otherwise
+    // (RTMI_DQN_MAX_FUSED, read per call: tests and the A/B) or the network is pinned to the
+    // stationary kernel; DESIGN.md section 7 holds the A/B
+    const bool smax = dqn->sampling == RT_DQN_SAMPLE_MAX;
+    bool fused = true;
+    if (const char* env = getenv("RTMI_DQN_MAX_FUSED")) fused = atoi(env) != 0;
+    fused = fused && rt::dqn_view_can_fuse(a.net);
     int32_t* h_count = nullptr;
     RT_HIPE(hipHostMalloc((void**)&h_count, sizeof(int32_t), hipHostMallocDefault));
     a.rays.n_pix = n_pix;
@@ -463,18 +539,21 @@ int run_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_came
         if (e == hipSuccess) e = rt::launch_dqn_camera(a, stream);
         for (int b = 1; e == hipSuccess && b < p->max_bounces; ++b) {
             e = hipMemsetAsync(a.rays.count + (b & 1), 0, sizeof(int32_t), stream);
-            if (e == hipSuccess) e = rt::launch_dqn_bounce(a, b, stream);
+            if (e == hipSuccess) e = smax ? rt::launch_dqn_bounce_max(a, b, fused, stream) : rt::launch_dqn_bounce(a, b, stream);
             if (e == hipSuccess && (b % 4 == 0 || b == 1)) {  // stop once every path has ended
                 e = hipMemcpyAsync(h_count, a.rays.count + (b & 1), sizeof(int32_t), hipMemcpyDeviceToHost, stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(stream);
                 if (e == hipSuccess && *h_count == 0) break;
             }
         }
+        if (e == hipSuccess && stats) e = rt::launch_dqn_zero_paths(a, ws->zero_paths, stream);
         if (e == hipSuccess) e = rt::launch_dqn_accumulate(a, stream);
     }
     if (e == hipSuccess) e = rt::launch_dqn_finish(a, stream);
     (void)hipHostFree(h_count);
     if (e != hipSuccess) return err(RT_E_HIP, std::string("DQN render: ") + hipGetErrorString(e));
+    ws->paths = valid_pixels * (uint64_t)p->spp;
+    ws->rendered = stats;
     return RT_OK;
 }
 
@@ -635,8 +714,13 @@ int rt_render_dqn_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_dqn*
     int n_blocks = 0;
     rc = rt::ctx_blocks(ctx, tiles, n_tiles, tile_size, params->width, params->height, &d_blocks, &n_blocks);
     if (rc != RT_OK) return rc;
+    // the call's pixels: every tile clipped to the image (origins are inside it: ctx_blocks)
+    uint64_t valid = 0;
+    for (int k = 0; k < n_tiles; ++k)
+        valid += (uint64_t)std::min(tile_size, params->width - tiles[2 * k]) *
+                 (uint64_t)std::min(tile_size, params->height - tiles[2 * k + 1]);
     return run_dqn(ctx, scene, dqn, cam, params, d_blocks, n_blocks, params->width, params->height, tile_size,
-                   d_out, d_casts, (hipStream_t)stream);
+                   d_out, d_casts, valid, (hipStream_t)stream);
 }
 
 int rt_render_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const rt_camera* cam,
@@ -655,10 +739,30 @@ int rt_render_dqn(rt_ctx* ctx, const rt_scene* scene, const rt_dqn* dqn, const r
     f.out(&d_casts, &casts, sizeof(casts), 0);
     const hipError_t e = f.begin();
     if (e == hipSuccess)
-        rc = run_dqn(ctx, scene, dqn, cam, params, f.blocks(), f.n_blocks(), x0 + w, y0 + h, w, d_out, d_casts, 0);
+        rc = run_dqn(ctx, scene, dqn, cam, params, f.blocks(), f.n_blocks(), x0 + w, y0 + h, w, d_out, d_casts,
+                     (uint64_t)w * (uint64_t)h, 0);
     rc = f.finish(rc, e, "rt_render_dqn");
     if (rc == RT_OK && out_ray_casts) *out_ray_casts = casts;
     return rc;
+}
+
+int rt_dqn_enable_stats(rt_ctx* ctx, int on) {
+    if (!ctx) return err(RT_E_INVALID, "NULL argument");
+    g_ws_for(ctx)->stats_on = on != 0;
+    return RT_OK;
+}
+
+int rt_dqn_render_stats(const rt_ctx* ctx, uint64_t* paths, uint64_t* zero_paths) {
+    if (!ctx) return err(RT_E_INVALID, "NULL argument");
+    const Workspace* ws = g_ws_find(ctx);
+    if (!ws || !ws->rendered)
+        return err(RT_E_INVALID, "no DQN render with statistics on this context yet (rt_dqn_enable_stats)");
+    RT_HIPE(hipSetDevice(rt::ctx_device(ctx)));
+    unsigned long long z = 0;
+    RT_HIPE(hipMemcpy(&z, ws->zero_paths, sizeof(z), hipMemcpyDeviceToHost));
+    if (paths) *paths = ws->paths;
+    if (zero_paths) *zero_paths = (uint64_t)z;
+    return RT_OK;
 }
 
 }  // extern "C"
@@ -675,6 +779,11 @@ Workspace* g_ws_for(rt_ctx* ctx) {
     auto& w = g_ws[ctx];
     if (!w) w.reset(new Workspace());
     return w.get();
+}
+Workspace* g_ws_find(const rt_ctx* ctx) {
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    const auto it = g_ws.find(ctx);
+    return it == g_ws.end() ? nullptr : it->second.get();
 }
 }  // namespace
 

@@ -416,6 +416,12 @@ hipError_t launch_dqn_mlp_ws(const DqnNet& net, const float* loc, const int32_t*
 hipError_t launch_dqn_frame_begin(const DqnLaunch& a, hipStream_t stream);
 hipError_t launch_dqn_camera(const DqnLaunch& a, hipStream_t stream);  // samples s0 .. s0 + n/n_pix - 1
 hipError_t launch_dqn_bounce(const DqnLaunch& a, int bounce, hipStream_t stream);
+// RT_DQN_SAMPLE_MAX's bounce (rtmi.h rt_dqn_set_sampling): forward over list[cur], each row's
+// action (fused: in k_dqn_mlp's epilogue, needs dqn_view_can_fuse; else k_dqn_argmax on the fp32
+// rays.q), k_dqn_bounce_max
+hipError_t launch_dqn_bounce_max(const DqnLaunch& a, int bounce, bool fused, hipStream_t stream);
+// the pass's valid rays with every throughput channel < THROUGHPUT_THRESHOLD, added to *zero_paths
+hipError_t launch_dqn_zero_paths(const DqnLaunch& a, unsigned long long* zero_paths, hipStream_t stream);
 hipError_t launch_dqn_accumulate(const DqnLaunch& a, hipStream_t stream);
 hipError_t launch_dqn_finish(const DqnLaunch& a, hipStream_t stream);
 // sampler alone (parity): rows i < n, Q [n][144] (overwritten with Q*cos), pixel/tri/loc per row
@@ -423,6 +429,12 @@ hipError_t launch_dqn_sample_only(const DeviceScene& s, const float* q, const fl
                                   const int32_t* tri, const uint32_t* pix, int n, int sample,
                                   int bounce, uint32_t seed_lo, uint32_t seed_hi, float* tp,
                                   float* dir_out, int32_t* action, hipStream_t stream);
+// the max-direction sampler alone (rt_dqn_sample_max): k_dqn_argmax on Q [n][144] (read only), then
+// the direction and throughput per row
+hipError_t launch_dqn_sample_max_only(const DeviceScene& s, const float* q, const float* loc,
+                                      const int32_t* tri, const uint32_t* pix, int n, int sample,
+                                      int bounce, uint32_t seed_lo, uint32_t seed_hi, float* tp,
+                                      float* dir_out, int32_t* action, hipStream_t stream);
 
 // ---- Expected-SARSA radiance volumes (BASELINE config 3) ----
 // Flattened KD tree of GPU/radiance_volumes/radiance_tree.cuh:19-27 (48 B per node):

@@ -258,6 +258,7 @@ class PretrainedPathtracer {
         const DqnModel m(model_path);
         const std::vector<float>& v = ds.vertices();
         detail::check(rt_dqn_create(ds.ctx(), v.data(), (int)v.size(), m.hidden, m.n_out, m.W, m.b, &net_));
+        detail::check(rt_dqn_enable_stats(ds.ctx(), 1));  // zero_contribution_paths()
     }
     ~PretrainedPathtracer() {
         if (net_) rt_dqn_destroy(net_);
@@ -275,6 +276,19 @@ class PretrainedPathtracer {
                                     rgb.data(), &casts));
         screen.PutFrame(rgb.data());
         return casts;
+    }
+
+    // sample_max_direction (nn_rendering_helpers.cu:491-553) instead of the CDF: every bounce
+    // leaves through the cell of highest estimated radiance (the thesis's fig:1_spp_max_dir)
+    void set_sample_max_direction(bool on) {
+        detail::check(rt_dqn_set_sampling(net_, on ? RT_DQN_SAMPLE_MAX : RT_DQN_SAMPLE_CDF));
+    }
+    // sum_zero_contribution_light_paths (nn_rendering_helpers.cu:555-568) of the last frame
+    // rendered on this scene's context: paths whose throughput has every channel < 1e-4
+    uint64_t zero_contribution_paths() const {
+        uint64_t paths = 0, zero = 0;
+        detail::check(rt_dqn_render_stats(ds_.ctx(), &paths, &zero));
+        return zero;
     }
 
    private:

@@ -49,6 +49,8 @@ RT_SARSA_KNN_MAX = 8
 RT_IRR_MEAN = 0
 RT_IRR_CONE = 1
 RT_DQN_VIEW_IRRADIANCE = 0
+RT_DQN_SAMPLE_CDF = 0
+RT_DQN_SAMPLE_MAX = 1
 RT_GLYPH_MAX = 256
 RT_GLYPH_SECTORS = 144
 RT_GLYPH_TRIS = 288
@@ -64,7 +66,7 @@ EXPORTS = (
     "rt_pack_argb", "rt_save_bmp", "rt_save_png", "rt_selftest", "rt_filter_build", "rt_rect_candidates", "rt_cull_masks_device",
     "rt_ctab_candidates",
     "rt_dynet_read", "rt_dynet_write", "rt_dqn_create", "rt_dqn_destroy", "rt_dqn_set_mlp", "rt_dqn_mlp_rows", "rt_dqn_forward", "rt_dqn_forward_device",
-    "rt_dqn_sample",
+    "rt_dqn_sample", "rt_dqn_set_sampling", "rt_dqn_get_sampling", "rt_dqn_sample_max", "rt_dqn_render_stats", "rt_dqn_enable_stats",
     "rt_render_dqn", "rt_render_dqn_tiles_device", "rt_render_dqn_view", "rt_render_dqn_view_tiles_device",
     "rt_sarsa_create", "rt_sarsa_create_density", "rt_sarsa_destroy", "rt_sarsa_info", "rt_sarsa_volumes", "rt_sarsa_read",
     "rt_sarsa_nearest", "rt_render_sarsa", "rt_render_sarsa_tiles_device", "rt_sarsa_td_device",
@@ -192,6 +194,11 @@ def _declare(lib):
         "rt_dqn_forward": (i, [_P, _P, _FP, i, _FP]),
         "rt_dqn_forward_device": (i, [_P, _P, _P, i, _P, _P]),
         "rt_dqn_sample": (i, [_P, _P, ctypes.c_uint64, _FP, _FP, _IP, _UP, i, i, i, _FP, _FP, _IP]),
+        "rt_dqn_set_sampling": (i, [_P, i]),
+        "rt_dqn_get_sampling": (i, [_P, ctypes.POINTER(ctypes.c_int)]),
+        "rt_dqn_sample_max": (i, [_P, _P, ctypes.c_uint64, _FP, _FP, _IP, _UP, i, i, i, _FP, _FP, _IP]),
+        "rt_dqn_render_stats": (i, [_P, _U64P, _U64P]),
+        "rt_dqn_enable_stats": (i, [_P, i]),
         "rt_render_dqn": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams), i, i,
                               i, i, _FP, _U64P]),
         "rt_render_dqn_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera),

@@ -9,6 +9,9 @@
                           forward is exact, so the device's Q can be pinned bit for bit
   Dqn(ctx, nn_vertices, weights)   device network (rt_dqn_create)
   forward / sample / render / render_tiles_device
+  Dqn.set_sampling(SAMPLE_MAX)   the reference's sample_max_direction in render / render_tiles_device
+                          (rt_dqn_set_sampling); sample_max the sampler alone; enable_stats(ctx) then
+                          render_stats(ctx) the last render's (paths, zero-contribution paths)
   render_view / render_view_tiles_device   the Q-network view (rt_render_dqn_view): the network's
                           irradiance estimate at every camera hit, on rt_render_irradiance's scale
   DqnTrainer(ctx, nn_vertices, weights)   Neural-Q training (rt_dqn_trainer_*): TD targets,
@@ -29,11 +32,13 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import RT_DQN_VIEW_IRRADIANCE, RtDqnViewOpts, check, lib
+from ._lib import RT_DQN_SAMPLE_CDF, RT_DQN_SAMPLE_MAX, RT_DQN_VIEW_IRRADIANCE, RtDqnViewOpts, check, lib
 from .api import Context, Scene, _fp, _ip
 
 HIDDEN = (200, 300, 200)  # NN_Builders/dq_network.cu:14-17
 ACTIONS = 144             # GRID_RESOLUTION^2
+SAMPLE_CDF = RT_DQN_SAMPLE_CDF   # importance_sample_direction (default)
+SAMPLE_MAX = RT_DQN_SAMPLE_MAX   # sample_max_direction: the first cell of the largest positive Q
 
 
 def read_dynet(path: str) -> List[np.ndarray]:
@@ -226,6 +231,19 @@ class Dqn:
         """forward kernel: MLP_AUTO / MLP_STREAM (weight streaming) or MLP_STATIONARY"""
         check(lib().rt_dqn_set_mlp(self._h, mode))
 
+    SAMPLE_CDF, SAMPLE_MAX = RT_DQN_SAMPLE_CDF, RT_DQN_SAMPLE_MAX
+
+    def set_sampling(self, mode: int) -> None:
+        """direction sampling of render / render_tiles_device with this network: SAMPLE_CDF
+        (default) or SAMPLE_MAX, the reference's sample_max_direction (rt_dqn_set_sampling)"""
+        check(lib().rt_dqn_set_sampling(self._h, mode))
+
+    @property
+    def sampling(self) -> int:
+        m = ctypes.c_int(0)
+        check(lib().rt_dqn_get_sampling(self._h, ctypes.byref(m)))
+        return int(m.value)
+
     def forward(self, loc: np.ndarray) -> np.ndarray:
         x = np.ascontiguousarray(loc, np.float32).reshape(-1, 3)
         q = np.zeros((x.shape[0], ACTIONS), np.float32)
@@ -276,6 +294,41 @@ def sample(ctx: Context, scene: Scene, seed: int, q: np.ndarray, loc: np.ndarray
                               pix.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, sample_idx,
                               bounce, _fp(tp), _fp(d), _ip(a)))
     return q, tp, d, a
+
+
+def sample_max(ctx: Context, scene: Scene, seed: int, q: np.ndarray, loc: np.ndarray, tri: np.ndarray,
+               pix: np.ndarray, sample_idx: int, bounce: int, tp: np.ndarray):
+    """SAMPLE_MAX's sampler alone (rt_dqn_sample_max): the first cell of the largest positive Q
+    (0 if none), its jittered direction, tp * cos / (RHO * 2).  q is not modified.  Returns
+    (tp, dir, action)."""
+    q = np.ascontiguousarray(q, np.float32)
+    loc = np.ascontiguousarray(loc, np.float32)
+    tri = np.ascontiguousarray(tri, np.int32)
+    pix = np.ascontiguousarray(pix, np.uint32)
+    tp = np.ascontiguousarray(tp, np.float32).copy()
+    n = q.shape[0]
+    d = np.zeros((n, 3), np.float32)
+    a = np.zeros(n, np.int32)
+    check(lib().rt_dqn_sample_max(ctx.handle, scene.handle, seed, _fp(q), _fp(loc), _ip(tri),
+                                  pix.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n, sample_idx,
+                                  bounce, _fp(tp), _fp(d), _ip(a)))
+    return tp, d, a
+
+
+def enable_stats(ctx: Context, on: bool = True) -> None:
+    """count the zero-contribution paths of the renders on ctx from now on (rt_dqn_enable_stats;
+    default off: one small kernel per pass)"""
+    check(lib().rt_dqn_enable_stats(ctx.handle, int(bool(on))))
+
+
+def render_stats(ctx: Context) -> Tuple[int, int]:
+    """(paths, zero_paths) of the last render / render_tiles_device on ctx (rt_dqn_render_stats):
+    the call's valid rays, and those whose final throughput has every channel < 1e-4.  A blocking
+    copy (synchronise the stream of a tile render first); raises unless that render ran after
+    enable_stats(ctx)."""
+    a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(lib().rt_dqn_render_stats(ctx.handle, ctypes.byref(a), ctypes.byref(b)))
+    return int(a.value), int(b.value)
 
 
 def render(ctx: Context, scene: Scene, dqn: Dqn, cam, params, rect=None):
