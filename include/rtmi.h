@@ -233,6 +233,69 @@ int rt_render_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* 
                            const rt_params* params, const int32_t* tiles, int n_tiles,
                            int tile_size, float* d_out, uint64_t* d_casts, void* stream);
 
+/* ---- next-event estimation: direct light by shadow rays (GPU preset) ---------
+ * The reference's path tracer adds light only when a bounce ray happens to hit a light
+ * triangle.  This is the same renderer with the standard variance reduction
+ * beside it: at every surface hit one point of one light is sampled and tested with a shadow
+ * ray.  Its expectation is rt_render's at the same max_bounces, exactly (consequence (a) below);
+ * its indirect path is rt_render's path, ray for ray.  GPU preset only: RT_PRESET_CPU is
+ * RT_E_UNSUPPORTED.
+ *
+ * Definition (normative; every line in binary32, -ffp-contract=off semantics, IEEE / and sqrt,
+ * normalize(v) = v * (1 / sqrt(dot(v, v))), dot(a, b) = (ax bx + ay by) + az bz).
+ * Sample s of pixel pix = y W + x starts with tp = (1,1,1), L = (0,0,0), depth = 0; its camera
+ * ray is rt_render's (event 0).  Each cast ends in one of three ways:
+ *   miss:         L += tp * env_light; the path ends.
+ *   light hit:    at depth == 0, L += tp * Le (the camera sees the light); at depth > 0 nothing
+ *                 (that light was sampled at the previous surface).  The path ends.
+ *   surface hit   tri at pos = o + t D:
+ *     depth + 1 == max_bounces: the path ends with nothing (rt_render would have no next cast, so
+ *       no direct light is taken either);
+ *     else the direct term, then -- unless flag RT_NEE_DIRECT_ONLY ends the path here -- the
+ *       preset's own bounce unchanged (event 1 + depth, counter word 3 = 0), then ++depth.
+ * The direct term at (tri, pos, depth):
+ *   1. one Philox block w of counter (pix, s, 1 + depth, 0x4E454531) under the seed's key;
+ *   2. r = u01(w0); light l = the first with r < cdf[l] (a light that catches the rest -- the last
+ *      whose cdf exceeds its predecessor's -- exists only for a caller's own cdf: a built table ends at 1);
+ *   3. u = u01(w1), v = u01(w2); if u + v > 1: u = 1 - u, v = 1 - v;  y = (v0 + u e1) + v e2 with
+ *      the light's v0, e1 = v1 - v0, e2 = v2 - v0;
+ *   4. Lv = y - pos, d2 = dot(Lv, Lv), d = normalize(Lv), cx = dot(N_tri, d), cy = |dot(N_l, d)|
+ *      (lights emit from both faces: GPU/rays/ray.cu:78-112 has no facing test);
+ *   5. d2 == 0, cx <= 0 or cy == 0: no cast, no contribution;
+ *   6. else the ray o = pos + 1e-5f d along d, cast as a ray leaving tri like every other cast; the
+ *      sample is visible iff the closest hit is triangle n_surf + l;
+ *   7. visible: per channel L += ((tp brdf_tri) Le_l) (((cx cy) / d2) k_l), brdf_tri = albedo / pi
+ *      under both samplers.
+ * Visibility by the closest hit inherits the scan's tie rules (a surface coplanar with the light
+ * at the same t wins, as for a bounce ray), is bit-identical on every cast route and needs no
+ * second epsilon.  A point within rounding of an edge shared by two light triangles can land on
+ * the neighbour and count as occluded (probability of the order 2^-24 per sample).
+ * Light table (host, double, stored as float): w_l = area_l (Le.r + Le.g + Le.b), cdf[l] the
+ * normalised running sum, k_l = (sum w) / (Le.r + Le.g + Le.b) (the reciprocal of the area pdf;
+ * 0 for a light of weight 0, which is never chosen).  A scene without lights, or without
+ * weight, is valid: no direct term is ever taken.
+ * A sample's L takes its terms in path order; samples fold as everywhere (spp_split chunks in
+ * sample order, chunk sums in chunk order, / spp).  Every closest-hit call counts as a cast,
+ * shadow casts included.  Consequences: (a) the expectation equals rt_render's -- the direct term at
+ * the surface of cast i stands for a light hit at cast i + 1 <= max_bounces - 1; (b) with no light
+ * (or none of weight) image and casts equal rt_render's bit for bit.
+ * out_stats (may be NULL): [0] paths (samples), [1] zero-contribution paths, L == (0,0,0) exactly.
+ * flags: 0 or RT_NEE_DIRECT_ONLY, else RT_E_INVALID.  Other arguments, checks and texts: rt_render's
+ * and rt_render_tiles_device's (d_stats: device uint64[2], accumulated into, may be NULL). */
+#define RT_NEE_DIRECT_ONLY 1
+int rt_render_nee(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt_params* params, int flags,
+                  int x0, int y0, int w, int h, float* out_rgb, uint64_t* out_ray_casts, uint64_t* out_stats);
+int rt_render_nee_tiles_device(rt_ctx* ctx, const rt_scene* scene, const rt_camera* cam, const rt_params* params,
+                               int flags, const int32_t* tiles, int n_tiles, int tile_size, float* d_out,
+                               uint64_t* d_casts, uint64_t* d_stats, void* stream);
+/* Host only, no GPU.  The light table of light triangles light_v (n_light x 9) with emission
+ * (n_light x 3): cdf and k, n_light floats each. */
+int rt_nee_light_table(const float* light_v, const float* emission, int n_light, float* cdf, float* k);
+/* Host only: steps 1-3 of the direct term for n draws (pix, s, depth): the light (-1 where the cdf
+ * has no weight) and the point y (n x 3; zeros for no light), by the code the kernel runs. */
+int rt_nee_sample(const float* light_v, const float* cdf, int n_light, uint64_t seed, const uint32_t* pix,
+                  const uint32_t* s, const int32_t* depth, int n, int32_t* light, float* y);
+
 /* ---- DQN Q-value sampling (BASELINE config 4) ---------------------------- */
 typedef struct rt_dqn rt_dqn;
 

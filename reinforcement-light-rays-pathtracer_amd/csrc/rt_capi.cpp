@@ -19,6 +19,7 @@
 #include "../../include/rtmi.h"
 #include "rt_cull.hpp"
 #include "rt_hostframe.hpp"
+#include "rt_nee.hpp"
 
 namespace {
 
@@ -123,6 +124,10 @@ struct rt_scene {
     std::mutex ctab_mu;                    // (renders of one scene from several threads)
     double ctab_build_s[2] = {0.0, 0.0};   // host build + upload, seconds (rt_scene_ctab_info)
     uint64_t ctab_bytes[2] = {0, 0};       // device bytes of the table
+    // next-event estimation's light table (scene_nee_lights): cdf then k, n_light floats each
+    bool nee_tried = false;
+    float* d_nee = nullptr;
+    int nee_last = -1;
 };
 
 namespace {
@@ -499,6 +504,35 @@ int scene_ensure_ctab(const rt_scene* scene, int rule, float t_scale, bool wante
     return RT_OK;
 }
 
+int scene_nee_lights(const rt_scene* scene, NeeLights* out) {
+    rt_scene* sc = const_cast<rt_scene*>(scene);
+    std::lock_guard<std::mutex> lock(sc->ctab_mu);
+    if (!sc->nee_tried) {
+        const int n = sc->n_light;
+        std::vector<float> tab(2 * (size_t)n);
+        nee_light_table(sc->tri.data() + 9 * (size_t)sc->n_surf, sc->emission.data(), n, tab.data(), tab.data() + n);
+        const int last = nee_last_light(tab.data(), n);
+        if (last >= 0) {
+            const int rc = set_device(sc->ctx);
+            if (rc != RT_OK) return rc;
+            float* d = nullptr;
+            hipError_t e = hipMalloc(&d, sizeof(float) * tab.size());
+            if (e == hipSuccess) e = hipMemcpy(d, tab.data(), sizeof(float) * tab.size(), hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                if (d) (void)hipFree(d);
+                return errorf(RT_E_HIP, "light table upload failed: %s", hipGetErrorString(e));
+            }
+            sc->d_nee = d;
+        }
+        sc->nee_last = last;
+        sc->nee_tried = true;
+    }
+    out->cdf = sc->d_nee;
+    out->k = sc->d_nee ? sc->d_nee + sc->n_light : nullptr;
+    out->last = sc->nee_last;
+    return RT_OK;
+}
+
 int leaving_route(const rt_scene* scene, const rt_params* p, DeviceScene* launch_scene) {
     DeviceScene& d = *launch_scene;
     d = scene_launch_view(scene);
@@ -773,6 +807,7 @@ namespace rt {
 RenderLaunch render_launch(const rt_scene* scene, const rt_camera* cam, const rt_params* p) {
     return make_launch(scene, cam, p);
 }
+int check_render_params(const rt_params* p) { return check_params(p); }
 }  // namespace rt
 
 extern "C" {
@@ -974,6 +1009,7 @@ int rt_scene_destroy(rt_scene* scene) {
         if (t.cop) (void)hipFree(const_cast<unsigned long long*>(t.cop));
         if (t.tri) (void)hipFree(const_cast<float4*>(t.tri));
     }
+    if (scene->d_nee) (void)hipFree(scene->d_nee);
     scene_free_bvh(scene);
     delete scene;
     return RT_OK;

@@ -547,6 +547,19 @@ int check_leaving_args(const rt_ctx* ctx, const rt_scene* scene, const rt_params
 constexpr int kRouteSel = 0, kRouteTable = 1, kRouteBvh = 2;
 int leaving_route(const rt_scene* scene, const rt_params* p, DeviceScene* launch_scene);
 
+// ---- next-event estimation (rt_nee.hip; rtmi.h "next-event estimation") ----
+// The scene's light table on the device (rt_nee.hpp nee_light_table over the scene's lights), built
+// and uploaded on the first render that takes it and kept by the scene, as the candidate table is.
+struct NeeLights {
+    const float* cdf = nullptr;  // [n_light]
+    const float* k = nullptr;    // [n_light]
+    int last = -1;               // nee_last_light: -1 = no light has weight, no direct term is taken
+};
+int scene_nee_lights(const rt_scene* scene, NeeLights* out);  // RT_OK, or the upload's error
+// rt_render's parameter checks and texts, and its chunk-queue workspace (rt_capi.cpp)
+int check_render_params(const rt_params* p);
+int ctx_chunks(rt_ctx* ctx, RenderLaunch* a);
+
 // rt_sarsa_bake (rt_bake.hip) works on a map through this view (rt_sarsa_host.cpp: sarsa_bake_view)
 struct SarsaBakeView {
     SarsaMap m;

@@ -9,17 +9,14 @@
 namespace rt {
 
 // ---- the GPU preset's surface step ----
-// The hit position and the direction sampled in the hit surface's shading frame, by event
-// 1 + depth of Philox counter (pix, s); returns cos(theta) of the direction.
+// The direction sampled in surface tri's shading frame by event 1 + depth of Philox counter
+// (pix, s); returns cos(theta) of the direction.
 template <int SAMPLER>
-__device__ __forceinline__ float bounce_direction(const Hit& h, f3 o, f3 d, float t_scale,
-                                                  const float4* __restrict__ shade, uint32_t pix, uint32_t s,
-                                                  int depth, uint32_t seed_lo, uint32_t seed_hi, f3* pos, f3* sd) {
-    const float Dx = d.x * t_scale, Dy = d.y * t_scale, Dz = d.z * t_scale;
-    *pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
-    const float4 N = shade[h.tri * kShadeF4 + 0];
-    const float4 T = shade[h.tri * kShadeF4 + 1];
-    const float4 B = shade[h.tri * kShadeF4 + 2];
+__device__ __forceinline__ float bounce_direction_at(int tri, const float4* __restrict__ shade, uint32_t pix,
+                                                     uint32_t s, int depth, uint32_t seed_lo, uint32_t seed_hi, f3* sd) {
+    const float4 N = shade[tri * kShadeF4 + 0];
+    const float4 T = shade[tri * kShadeF4 + 1];
+    const float4 B = shade[tri * kShadeF4 + 2];
     float r1, r2;
     draw2(pix, s, 1u + (uint32_t)depth, seed_lo, seed_hi, &r1, &r2);
     float cos_theta, sin_theta;
@@ -36,6 +33,15 @@ __device__ __forceinline__ float bounce_direction(const Hit& h, f3 o, f3 d, floa
     *sd = make3((sx * B.x + cos_theta * N.x) + sz * T.x, (sx * B.y + cos_theta * N.y) + sz * T.y,
                 (sx * B.z + cos_theta * N.z) + sz * T.z);
     return cos_theta;
+}
+// The hit position, and bounce_direction_at of the hit surface.
+template <int SAMPLER>
+__device__ __forceinline__ float bounce_direction(const Hit& h, f3 o, f3 d, float t_scale,
+                                                  const float4* __restrict__ shade, uint32_t pix, uint32_t s,
+                                                  int depth, uint32_t seed_lo, uint32_t seed_hi, f3* pos, f3* sd) {
+    const float Dx = d.x * t_scale, Dy = d.y * t_scale, Dz = d.z * t_scale;
+    *pos = make3(o.x + h.t * Dx, o.y + h.t * Dy, o.z + h.t * Dz);
+    return bounce_direction_at<SAMPLER>(h.tri, shade, pix, s, depth, seed_lo, seed_hi, sd);
 }
 // the throughput past surface tri, left along a direction of cos_theta
 template <int SAMPLER>
@@ -60,6 +66,18 @@ __device__ __forceinline__ int surface_step(const Hit& h, f3& o, f3& d, f3& tp, 
     o = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
     d = normalize(sd);
     return h.tri;
+}
+
+// surface_step for a caller that holds the hit position pos on surface tri (k_render_nee, whose
+// shadow cast lies between the hit and the bounce): the same ray and throughput.
+template <int SAMPLER>
+__device__ __forceinline__ void surface_step_at(f3 pos, int tri, f3& o, f3& d, f3& tp, const float4* __restrict__ shade,
+                                                uint32_t pix, uint32_t s, int depth, uint32_t seed_lo, uint32_t seed_hi) {
+    f3 sd;
+    const float cos_theta = bounce_direction_at<SAMPLER>(tri, shade, pix, s, depth, seed_lo, seed_hi, &sd);
+    tp = bounce_throughput<SAMPLER>(tp, shade, tri, cos_theta);
+    o = make3(pos.x + kEps * sd.x, pos.y + kEps * sd.y, pos.z + kEps * sd.z);
+    d = normalize(sd);
 }
 
 // ---- the first ray of (point, sector, sample) ----

@@ -53,6 +53,21 @@ class PathTracer {
         return casts;
     }
 
+    // draw with next-event estimation (rt_render_nee; GPU preset): flags 0 or RT_NEE_DIRECT_ONLY;
+    // stats: [2] paths and zero-contribution paths, or NULL
+    uint64_t draw_next_event(SDLScreen& screen, const Camera& camera, const rt_params& params, int flags,
+                             uint64_t* stats = nullptr) {
+        if (!scene_) throw std::runtime_error("PathTracer: no scene");
+        rgb_.resize((size_t)screen.width * screen.height * 3);
+        const rt_camera cam = camera.to_rt();
+        uint64_t casts = 0;
+        if (rt_render_nee(ctx_, scene_, &cam, &params, flags, 0, 0, screen.width, screen.height, rgb_.data(), &casts,
+                          stats) != RT_OK)
+            throw std::runtime_error(rt_last_error());
+        screen.PutFrame(rgb_.data());
+        return casts;
+    }
+
     const std::vector<float>& radiance() const { return rgb_; }
     int scene_uploads() const { return uploads_; }
 

@@ -56,6 +56,7 @@ RT_GLYPH_SECTORS = 144
 RT_GLYPH_TRIS = 288
 RT_GLYPH_RATIO = 0
 RT_GLYPH_MAGNITUDE = 1
+RT_NEE_DIRECT_ONLY = 1
 
 # every symbol include/rtmi.h declares (checked by tests/test_abi.py)
 EXPORTS = (
@@ -90,6 +91,7 @@ EXPORTS = (
     "rt_rect_candidates_forms",
     "rt_selected_read", "rt_glyph_mesh", "rt_glyph_colours", "rt_glyphs_create", "rt_glyphs_create_sized", "rt_glyphs_destroy",
     "rt_glyphs_set_colours", "rt_glyphs_info", "rt_render_glyph_view", "rt_render_glyph_view_tiles_device",
+    "rt_render_nee", "rt_render_nee_tiles_device", "rt_nee_light_table", "rt_nee_sample",
 )
 
 
@@ -280,6 +282,12 @@ def _declare(lib):
         "rt_render_glyph_view_tiles_device": (i, [_P, _P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams),
                                                   ctypes.POINTER(RtGlyphViewOpts), ctypes.c_uint32, _P, _IP, i, i,
                                                   _P, _P]),
+        "rt_render_nee": (i, [_P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams), i, i, i, i, i,
+                              _FP, _U64P, _U64P]),
+        "rt_render_nee_tiles_device": (i, [_P, _P, ctypes.POINTER(RtCamera), ctypes.POINTER(RtParams), i,
+                                           _IP, i, i, _P, _P, _P, _P]),
+        "rt_nee_light_table": (i, [_FP, _FP, i, _FP, _FP]),
+        "rt_nee_sample": (i, [_FP, _FP, i, ctypes.c_uint64, _UP, _UP, _IP, i, _IP, _FP]),
         "rt_ktime_enable": (i, [i]),
         "rt_ktime_read": (i, [i, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]),
         "rt_ktime_name": (ctypes.c_char_p, [i]),

@@ -302,6 +302,65 @@ def render_tiles_device(ctx: Context, scene: Scene, cam: RtCamera, params: RtPar
                                        ctypes.c_void_p(stream)))
 
 
+def render_nee(ctx: Context, scene: Scene, cam: RtCamera, params: RtParams, flags: int = 0,
+               rect: Optional[Tuple[int, int, int, int]] = None, stats: bool = False):
+    """rt_render_nee: render() with next-event estimation (a shadow ray towards one sampled light
+    point at every surface hit; GPU preset).  flags: 0 or RT_NEE_DIRECT_ONLY.  Returns the image
+    and the ray casts (shadow casts included); with stats also {"paths", "zero_paths"}."""
+    x0, y0, w, h = rect if rect is not None else (0, 0, params.width, params.height)
+    out = np.zeros((h, w, 3), np.float32)
+    casts = ctypes.c_uint64(0)
+    st = (ctypes.c_uint64 * 2)(0, 0)
+    check(lib().rt_render_nee(ctx.handle, scene.handle, ctypes.byref(cam), ctypes.byref(params), int(flags),
+                              x0, y0, w, h, _fp(out), ctypes.byref(casts), st if stats else None))
+    if stats:
+        return out, int(casts.value), {"paths": int(st[0]), "zero_paths": int(st[1])}
+    return out, int(casts.value)
+
+
+def render_nee_tiles_device(ctx: Context, scene: Scene, cam: RtCamera, params: RtParams, flags: int,
+                            tiles: np.ndarray, tile_size: int, out_ptr: int, casts_ptr: int, stats_ptr: int,
+                            stream: int) -> None:
+    """Asynchronous tile-list render into device memory (rt_render_nee_tiles_device); casts_ptr
+    (uint64) and stats_ptr (uint64[2]) are accumulated into and may be 0."""
+    t = np.ascontiguousarray(tiles, np.int32).reshape(-1, 2)
+    check(lib().rt_render_nee_tiles_device(ctx.handle, scene.handle, ctypes.byref(cam), ctypes.byref(params),
+                                           int(flags), _ip(t), t.shape[0], tile_size, ctypes.c_void_p(out_ptr),
+                                           ctypes.c_void_p(casts_ptr), ctypes.c_void_p(stats_ptr),
+                                           ctypes.c_void_p(stream)))
+
+
+def nee_light_table(geom: Geometry) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_nee_light_table of the geometry's lights (host only): (cdf, k), float32 (n_light,)."""
+    lv = np.ascontiguousarray(geom.light, np.float32).reshape(-1, 9)
+    em = np.ascontiguousarray(geom.emission, np.float32).reshape(-1, 3)
+    n = lv.shape[0]
+    cdf, k = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    check(lib().rt_nee_light_table(_fp(lv), _fp(em), n, _fp(cdf), _fp(k)))
+    return cdf, k
+
+
+def nee_sample(light: np.ndarray, cdf: np.ndarray, seed: int, pix, s, depth) -> Tuple[np.ndarray, np.ndarray]:
+    """rt_nee_sample (host only): the light (n,) int32 (-1: the cdf has no weight) and the point
+    (n, 3) float32 the direct term of (pix, s, depth) samples on the light triangles (n_light, 9)."""
+    lv = np.ascontiguousarray(light, np.float32).reshape(-1, 9)
+    c = np.ascontiguousarray(cdf, np.float32).ravel()
+    if c.shape[0] != lv.shape[0]:
+        raise ValueError("cdf: one entry per light")
+    px = np.ascontiguousarray(pix, np.uint32).ravel()
+    ss = np.ascontiguousarray(s, np.uint32).ravel()
+    dp = np.ascontiguousarray(depth, np.int32).ravel()
+    n = px.shape[0]
+    if ss.shape[0] != n or dp.shape[0] != n:
+        raise ValueError("pix, s and depth: one entry per draw")
+    li = np.zeros(n, np.int32)
+    y = np.zeros((n, 3), np.float32)
+    u32 = ctypes.POINTER(ctypes.c_uint32)
+    check(lib().rt_nee_sample(_fp(lv), _fp(c), lv.shape[0], int(seed), px.ctypes.data_as(u32), ss.ctypes.data_as(u32),
+                              _ip(dp), n, _ip(li), _fp(y)))
+    return li, y
+
+
 def filter_records(tri_all: np.ndarray) -> np.ndarray:
     """Filter records of the two-phase hit test for a triangle soup (n, 9): (n, 20) float32."""
     t = np.ascontiguousarray(tri_all, np.float32).reshape(-1, 9)
